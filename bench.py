@@ -98,6 +98,8 @@ WEIGHT_SEED = 99
 FINAL_SCALE = 0.25     # last Linear layer of every net scaled by this so |s| stays O(1) over 16 half-steps
 PEAK_FP32_MATRIX_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 peak
 PEAK_HBM_GBS = 8000.0
+DUMP_ARRAY_BYTES = 12 << 20   # --dump-outputs: per array; a dump holds at most five arrays, so it stays under 64 MB
+DUMP_SEED = 4321
 
 
 # Sources of the kernels each workload's launches live in: what a PMC pass under profiles/ is evidence FOR.  An entry of
@@ -172,6 +174,23 @@ def secondary_entry(d):
         e["train_frac"] = tr["frac"]
         e["frac_note"] = "`frac` / `kernel_us` are the forward flow alone inside the trainer step; `train_frac` is the whole step"
     return e
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as <out_dir>/<name>.npy in its own precision (float32 or float64).  One
+    larger than DUMP_ARRAY_BYTES is stored as a fixed sample: the elements of its flattened form at the sorted positions
+    default_rng(DUMP_SEED) draws without replacement, the same positions in every run.  Returns {name: {shape, stored}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach()
+        keep = DUMP_ARRAY_BYTES // a.element_size()
+        if a.numel() > keep:
+            pos = np.sort(np.random.default_rng(DUMP_SEED).choice(a.numel(), keep, replace=False))
+            a = a.reshape(-1)[torch.as_tensor(pos, device=a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+        written[name] = {"shape": list(t.shape), "stored": int(a.numel())}
+    return written
 
 
 def percentiles(ms):
@@ -411,7 +430,12 @@ def main():
     ap.add_argument("--secondary-steps", type=int, default=0, help="steps per timed region of the secondary workloads (0: --steps, capped at 40)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + GNF_BENCH_ONE_DEVICE=1 runs several ranks on ONE GPU to exercise the N>1 logic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step returned as DIR/<name>.npy (rank 0: its "
+                         "shard's nodes and the reduced sums; training workloads also the parameters and gradient)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global WORKLOAD, GRAPHS_PER_GPU
     WORKLOAD = WORKLOADS[args.workload]
     GRAPHS_PER_GPU = args.graphs_per_gpu or WORKLOAD["graphs"]
@@ -492,17 +516,17 @@ def main():
     state0 = None
 
     def step(i):
+        """One step; returns what the path hands its caller (the trainer's values_map, g's graph, or f's nodes z - the
+        forward sums land in host[i])."""
         if trainer is not None:   # gradient all-reduce (one flat RCCL all-reduce) when sharded
-            trainer.step(graph, all_reduce=multi)
-            return
+            return trainer.step(graph, all_reduce=multi)
         if inverse:   # config 4: sampling direction g (gnn.py:343-373); no scalar comes back
-            net(graph, inverse=False)
-            return
+            return net(graph, inverse=False)
         if multi:
             # two alternating sum buffers: batch i's 3-scalar all-reduce runs on RCCL's stream while batch i + 1 is
             # already computing; its result is read (stream-ordered wait, pinned-host copy) one step later
             buf = sums_pair[i & 1]
-            _, s3 = forward_shard_sums(net, graph, buf)
+            z, s3 = forward_shard_sums(net, graph, buf)
             s3[2] = float(n_local)           # all-reduce sums in place: restore this rank's count first
             pending.append((all_reduce_shard_sums_async(s3, force=args.force_dist), s3, i))
             if len(pending) > 1 or args.sync_each_step:
@@ -510,9 +534,10 @@ def main():
         else:
             # one GPU: the final reduction kernel writes the two batch scalars straight into this step's row of the
             # pinned host buffer (device-visible host memory; no device-to-host copy node behind the flow)
-            forward_shard_sums(net, graph, host[i])
+            z, _ = forward_shard_sums(net, graph, host[i])
         if args.sync_each_step:
             torch.cuda.current_stream().synchronize()
+        return z
 
     sums_pair = [torch.zeros(3, dtype=torch.float64, device=dev) for _ in range(2)]
     pending = []
@@ -543,6 +568,8 @@ def main():
     drain(len(pending))
     torch.cuda.synchronize()
 
+    last_result = [None]      # what the last step of the latest timed region returned
+
     def timed_region():
         """EXACTLY args.steps steps between barrier + synchronize on both sides; MAX over ranks.  Every step of a region
         writes the same host rows (args.warmup + i): the rows are results, not a log."""
@@ -552,8 +579,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(args.steps - 1):
             step(args.warmup + i)
+        last_result[0] = step(args.warmup + args.steps - 1)
         t_enq = time.perf_counter() - t0      # the host has handed over every step (not a result: says whether the
                                               # loop is bound by the device or by the host's launch rate)
         drain(len(pending))                   # inside the timed region: every batch's log-prob has reached the host buffer
@@ -585,6 +613,17 @@ def main():
     last = ({"log_prob_xs_per_node": None} if inverse else
             log_prob_from_sums(host[args.warmup + args.steps - 1].tolist(), HP["D"]))
     value = n_global * HP["T"] * args.steps / elapsed
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        res, row = last_result[0], host[args.warmup + args.steps - 1]
+        if trainer is not None:   # values_map, and the variables and gradient the step left behind
+            arrays = {"z": res["z_graph"].nodes, "reconstruction": res["reconstruction"], "sums": row,
+                      "theta": trainer.theta, "grad": trainer.grad}
+        elif inverse:
+            arrays = {"x": res.nodes}
+        else:                     # sums = [log_det_jacobian, sum z^2, num_nodes], reduced over the ranks when sharded
+            arrays = {"z": res, "sums": row}
+        dumped = dump_outputs(args.dump_outputs, arrays)
 
     # ---- secondary figure: the same step when the batch's topology is new every step (training loop
     # of run_grevnet.py:440-447 draws a fresh batch per step): CSR rebuilt on device inside the step
@@ -884,6 +923,8 @@ def main():
         "roofline": roofline,
         "kernel_a": kernel_a,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
 
     if trainer is not None:
         # one trainer step = forward + dL/dx chain + weight gradients: 3 x the forward's algorithmic flops (what tf.gradients

@@ -5,6 +5,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 import bench
 
@@ -49,6 +50,42 @@ def test_make_batch_shards_cover_the_global_batch():
         assert sum(len(d["senders"]) for d in d1) == e1
     finally:
         bench.GRAPHS_PER_GPU = 64
+
+
+@pytest.mark.parametrize("workload,graphs_per_rank", [("config2", 16), ("config5", 8), ("default_flags", 16)])
+def test_make_batch_deals_eight_ranks_whole_graphs_in_balance(workload, graphs_per_rank):
+    """The global batches of tests/test_multirank_gpu.py's sharded runs dealt to EIGHT ranks, the rank count BASELINE.json's
+    north_star names (on one device the GPU test runs fewer): every graph on exactly one rank, nodes and edges within 5 %
+    of the mean per rank."""
+    saved = bench.WORKLOAD, bench.GRAPHS_PER_GPU
+    bench.WORKLOAD, bench.GRAPHS_PER_GPU = bench.WORKLOADS[workload], graphs_per_rank
+    try:
+        shards = [bench.make_batch(8, rank) for rank in range(8)]
+    finally:
+        bench.WORKLOAD, bench.GRAPHS_PER_GPU = saved
+    n_global, e_global = shards[0][1], shards[0][2]
+    nodes = [sum(d["n_node"] for d in dicts) for dicts, _, _ in shards]
+    edges = [sum(len(d["senders"]) for d in dicts) for dicts, _, _ in shards]
+    assert sum(len(dicts) for dicts, _, _ in shards) == 8 * graphs_per_rank
+    assert sum(nodes) == n_global and sum(edges) == e_global
+    assert max(nodes) * 8 <= 1.05 * n_global and max(edges) * 8 <= 1.05 * e_global, (nodes, edges)
+
+
+def test_dump_outputs_keeps_precision_and_samples_large_arrays_at_fixed_positions(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 arrays are stored as they are; one larger than DUMP_ARRAY_BYTES becomes
+    the same seeded sample in every run; five arrays at the cap stay within 64 MB."""
+    import torch
+    assert 5 * bench.DUMP_ARRAY_BYTES <= 64 << 20
+    sums = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    big = torch.arange(bench.DUMP_ARRAY_BYTES // 4 + 1000, dtype=torch.float32)      # value = position
+    w = bench.dump_outputs(str(tmp_path / "a"), {"sums": sums, "theta": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"theta": big})
+    s = np.load(tmp_path / "a" / "sums.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, sums.numpy())
+    a, b = np.load(tmp_path / "a" / "theta.npy"), np.load(tmp_path / "b" / "theta.npy")
+    assert a.dtype == np.float32 and a.nbytes == bench.DUMP_ARRAY_BYTES and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0)                 # distinct positions, ascending
+    assert w == {"sums": {"shape": [3, 4], "stored": 12}, "theta": {"shape": [big.numel()], "stored": a.size}}
 
 
 def test_workload_table():
