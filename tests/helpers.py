@@ -71,3 +71,52 @@ def graph_from_arrays(n_node, n_edge, senders, receivers, x, device="cpu"):
                        globals=torch.zeros(len(n_node)).to(device),
                        n_node=torch.as_tensor(np.asarray(n_node, np.int32)).to(device),
                        n_edge=torch.as_tensor(np.asarray(n_edge, np.int32)).to(device))
+
+
+# ---- guard-banded node buffers: the ABI's [N, D] window with leading dimension ld >= D (include/gnf.h) -------------------
+SENTINEL_BITS = 0x7FC0DEAD   # a quiet NaN whose payload no kernel arithmetic produces
+
+
+class GuardBanded:
+    """An [n, d] fp32 window inside a device buffer of (n + 2 guard) rows x ld columns: rows [guard, guard + n), columns
+    [c0, c0 + d), leading dimension ld.  Everything outside the window holds the SENTINEL_BITS NaN, so a kernel that reads
+    past the window multiplies NaN into its result, and one that writes past it changes bits check_guard() looks at.  An odd
+    c0 leaves the window's base pointer off 16-byte alignment."""
+
+    def __init__(self, n, d, ld, c0=0, guard=16, device="cuda:0", fill=None):
+        import torch
+        assert ld >= c0 + d, (ld, c0, d)
+        self.n, self.d, self.ld, self.c0, self.guard = n, d, ld, c0, guard
+        self.bits = torch.full((n + 2 * guard, ld), SENTINEL_BITS, dtype=torch.int32, device=device)
+        self.window = self.bits.view(torch.float32)[guard:guard + n, c0:c0 + d]
+        if fill is not None:
+            self.window.copy_(torch.as_tensor(np.asarray(fill, np.float32)).to(device))
+
+    def ptr(self, col=0):
+        """Device address of column `col` of the window's first row (a ctypes void pointer)."""
+        import ctypes as C
+        return C.c_void_p(self.window.data_ptr() + 4 * col)
+
+    def aligned(self):
+        """Does this layout take the same vector / scalar load decisions as a contiguous [n, d] buffer?"""
+        return self.ld % 4 == 0 and self.c0 % 4 == 0 and self.d % 4 == 0
+
+    def numpy(self):
+        return self.window.cpu().numpy()
+
+    def check_guard(self, max_chunk_bytes=1 << 28):
+        """Every element outside the window still holds the exact sentinel bits (row blocks: bounded temporaries)."""
+        b, g, n, c0, d = self.bits, self.guard, self.n, self.c0, self.d
+        rows = max(1, max_chunk_bytes // (4 * self.ld))
+        regions = [("rows above", b[:g]), ("rows below", b[g + n:]),
+                   ("columns left", b[g:g + n, :c0]), ("columns right", b[g:g + n, c0 + d:])]
+        for name, reg in regions:
+            for r0 in range(0, reg.shape[0], rows):
+                blk = reg[r0:r0 + rows]
+                if blk.numel() == 0:
+                    continue
+                bad = int((blk != SENTINEL_BITS).sum())
+                assert bad == 0, f"{bad} guard elements changed ({name} of the window, row block {r0})"
+
+    def release(self):
+        self.window = self.bits = None
