@@ -32,7 +32,8 @@ def main():
     ap.add_argument("--num_coupling_layers", type=int, default=12)
     ap.add_argument("--weight_sharing", action="store_true")
     ap.add_argument("--make_gnn_fn", default="dm_self_attn",
-                    choices=["dm_self_attn", "avg_then_mlp", "avg_concat_then_mlp", "sum_concat_then_mlp"])
+                    choices=["dm_self_attn", "self_attn", "multihead_self_attn", "avg_then_mlp", "avg_concat_then_mlp",
+                             "sum_concat_then_mlp"])
     ap.add_argument("--gnn_num_layers", type=int, default=5)
     ap.add_argument("--gnn_latent_dim", type=int, default=256)
     ap.add_argument("--gnn_bias_init_stddev", type=float, default=0.1)
@@ -80,6 +81,12 @@ def main():
         "dm_self_attn": partial(gnn.dm_self_attn_gnn, kq_dim=F.attn_kq_dim, v_dim=F.attn_v_dim, make_mlp_fn=mlp(gnn.relu),
                                 num_heads=F.attn_num_heads, concat_heads_output_dim=F.attn_concat_heads_output_dim,
                                 concat=not F.no_attn_concat, residual=F.attn_residual, layer_norm=F.attn_layer_norm),
+        # run_grevnet.py:214-237: whole-graph attention, relu MLP, kq_dim_division
+        "self_attn": partial(gnn.self_attn_gnn, kq_dim=F.attn_kq_dim, v_dim=F.attn_v_dim, make_mlp_fn=mlp(gnn.relu),
+                             kq_dim_division=True),
+        "multihead_self_attn": partial(gnn.multihead_self_attn_gnn, kq_dim=F.attn_kq_dim, v_dim=F.attn_v_dim,
+                                       concat_heads_output_dim=F.attn_concat_heads_output_dim, make_mlp_fn=mlp(gnn.relu),
+                                       num_heads=F.attn_num_heads, kq_dim_division=True),
         "avg_then_mlp": partial(gnn.avg_then_mlp_gnn, mlp(gnn.leaky_relu), F.gnn_avg_then_mlp_epsilon),
         "avg_concat_then_mlp": partial(gnn.avg_concat_then_mlp_gnn, mlp(gnn.leaky_relu)),
         "sum_concat_then_mlp": partial(gnn.sum_concat_then_mlp_gnn, mlp(gnn.leaky_relu)),

@@ -57,7 +57,7 @@ def main():
     ap.add_argument("--weight_sharing", action="store_true")
     # the reference's defaults (train_grevnet_with_data.py:40-46): dm_attn, one head, kq = v = 64, C = 64
     # ("avg_then_mlp" is not a choice of the reference's ATTN_MAP; kept here as the message-passing alternative)
-    ap.add_argument("--attn_type", default="dm_attn", choices=["dm_attn", "avg_then_mlp"])
+    ap.add_argument("--attn_type", default="dm_attn", choices=["dm_attn", "singlehead_my_attn", "multihead_my_attn", "avg_then_mlp"])
     ap.add_argument("--use_layer_norm", action="store_true")
     ap.add_argument("--attn_kq_dim", type=int, default=64)
     ap.add_argument("--attn_v_dim", type=int, default=64)
@@ -101,6 +101,12 @@ def main():
         "dm_attn": partial(gnn.dm_self_attn_gnn, kq_dim=F.attn_kq_dim, v_dim=F.attn_v_dim, make_mlp_fn=make_mlp_fn,
                            num_heads=F.attn_num_heads, concat_heads_output_dim=F.attn_concat_heads_output_dim,
                            kq_dim_division=True, layer_norm=F.use_layer_norm),
+        # train_grevnet_with_data.py:289-302: whole-graph attention
+        "singlehead_my_attn": partial(gnn.self_attn_gnn, kq_dim=F.attn_kq_dim, v_dim=F.attn_v_dim, make_mlp_fn=make_mlp_fn,
+                                      kq_dim_division=True),
+        "multihead_my_attn": partial(gnn.multihead_self_attn_gnn, kq_dim=F.attn_kq_dim, v_dim=F.attn_v_dim,
+                                     concat_heads_output_dim=F.attn_concat_heads_output_dim, make_mlp_fn=make_mlp_fn,
+                                     num_heads=F.attn_num_heads, kq_dim_division=True, layer_norm=F.use_layer_norm),
     }[F.attn_type]
     grevnet = gnn.GRevNet(make_gnn_fn, F.num_coupling_layers, F.node_embedding_dim,
                           use_batch_norm=not F.no_batch_norm, weight_sharing=F.weight_sharing)

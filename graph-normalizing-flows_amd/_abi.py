@@ -8,12 +8,13 @@ import ctypes as C
 import os
 
 GNF_MAX_LAYERS = 8
-GNF_ABI_VERSION = 9
+GNF_ABI_VERSION = 10
 
 GNF_AGG_SUM, GNF_AGG_MEAN = 0, 1
 GNF_COMBINE_EPS, GNF_COMBINE_CONCAT = 0, 1
 GNF_ACT_RELU, GNF_ACT_LEAKY_RELU = 0, 1
 GNF_FORWARD, GNF_INVERSE = 0, 1
+GNF_ATTN_EDGES, GNF_ATTN_GRAPH = 0, 1   # GnfAttn.scope (ABI v10)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNF_LIB_PATH: developer override (a library built from another checkout, for A/B runs); still a HIP build
@@ -26,14 +27,16 @@ class GnfError(RuntimeError):
 
 class GnfCsr(C.Structure):
     _fields_ = [("rowptr", C.c_void_p), ("col", C.c_void_p), ("n_nodes", C.c_int64),
-                ("n_edges", C.c_int64)]
+                ("n_edges", C.c_int64),
+                ("node_offsets", C.c_void_p), ("n_graphs", C.c_int64)]   # ABI v10: graph-scope attention
 
 
 class GnfAttn(C.Structure):
     _fields_ = [("num_heads", C.c_int32), ("kq_dim", C.c_int32), ("v_dim", C.c_int32), ("out_dim", C.c_int32),
                 ("concat", C.c_int32), ("kq_dim_division", C.c_int32), ("residual", C.c_int32),
                 ("layer_norm", C.c_int32), ("Wq", C.c_void_p), ("Wk", C.c_void_p), ("Wv", C.c_void_p),
-                ("Wo", C.c_void_p), ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p)]
+                ("Wo", C.c_void_p), ("ln_gamma", C.c_void_p), ("ln_beta", C.c_void_p),
+                ("scope", C.c_int32)]   # ABI v10: GNF_ATTN_EDGES / GNF_ATTN_GRAPH
 
 
 class GnfMlp(C.Structure):

@@ -89,6 +89,16 @@ static int validate_csr(const GnfCsr* c) {
     return GNF_OK;
 }
 
+// a graph-scope attention net reads the batch's graph boundaries (GnfCsr.node_offsets, ABI v10)
+static int validate_node_offsets(const GnfCsr* c, const GnfMlp* net, const char* what) {
+    if (!net || !attn_is_graph(net->attn) || c->n_nodes == 0) return GNF_OK;
+    if (!c->node_offsets || c->n_graphs < 1 || c->n_graphs >= INT32_MAX) {
+        set_error("%s: graph-scope attention needs GnfCsr.node_offsets (device int32 [n_graphs + 1]) and n_graphs >= 1; got node_offsets=%p n_graphs=%lld", what, (const void*)c->node_offsets, (long long)c->n_graphs);
+        return GNF_EINVAL;
+    }
+    return GNF_OK;
+}
+
 // s/t nets of one half-step must agree with H and the combine mode (gnn.py:107-126: the MLP input
 // is [x|agg] (2H) or eps*x+agg (H); its output feeds exp(s) / +t on an H-wide half, gnn.py:323).
 static int validate_pair(const GnfMlp* s, const GnfMlp* t, const GnfGnnSpec* g, int32_t H) {
@@ -105,7 +115,8 @@ static int validate_pair(const GnfMlp* s, const GnfMlp* t, const GnfGnnSpec* g, 
         if (rc) return rc;
         rc = validate_attn(t->attn, t, H, "t_net");
         if (rc) return rc;
-        if (memcmp(s->attn, t->attn, 8 * sizeof(int32_t))) {  // one make_gnn_fn builds both nets (gnn.py:288-296)
+        if (memcmp(s->attn, t->attn, 8 * sizeof(int32_t)) || s->attn->scope != t->attn->scope ||
+            (attn_is_graph(s->attn) && (s->attn->Wo == nullptr) != (t->attn->Wo == nullptr))) {  // one make_gnn_fn builds both nets (gnn.py:288-296)
             set_error("s_net and t_net attention front-ends must have identical hyper-parameters");
             return GNF_ESHAPE;
         }
@@ -194,6 +205,17 @@ int validate_flow_call(const GnfCsr* csr, const GnfFlow* flow, int64_t ld, int32
             set_error("%s: net %d has different layer widths than net 0", what, q);
             return GNF_ESHAPE;
         }
+        // the backward plan and the front-end's scratch follow net 0: one scope (and one projection shape) for all
+        const GnfAttn *aq = flow->s_nets[q].attn, *a0 = flow->s_nets[0].attn;
+        if ((attn_is_graph(aq) || attn_is_graph(a0)) &&
+            (!aq || !a0 || (aq->scope != a0->scope || memcmp(aq, a0, 8 * sizeof(int32_t)) || (aq->Wo == nullptr) != (a0->Wo == nullptr)))) {
+            set_error("%s: net %d has another attention front-end than net 0", what, q);
+            return GNF_ESHAPE;
+        }
+    }
+    if (n_nets > 0) {
+        rc = validate_node_offsets(csr, &flow->s_nets[0], what);
+        if (rc) return rc;
     }
     return GNF_OK;
 }
@@ -297,6 +319,8 @@ int gnf_gnn_apply_f32(const GnfCsr* csr, const GnfMlp* mlp, const GnfGnnSpec* gn
     if (mlp->attn) {
         rc = validate_attn(mlp->attn, mlp, H, "gnf_gnn_apply_f32");
         if (rc) return rc;
+        rc = validate_node_offsets(csr, mlp, "gnf_gnn_apply_f32");
+        if (rc) return rc;
     }
     const int in0 = mlp->attn ? mlp->dims[0] : ((gnn->combine == GNF_COMBINE_CONCAT) ? 2 * H : H);
     const int od = mlp->dims[mlp->num_layers];
@@ -316,7 +340,7 @@ int gnf_gnn_apply_f32(const GnfCsr* csr, const GnfMlp* mlp, const GnfGnnSpec* gn
         return GNF_EWORKSPACE;
     }
     return launch_gnn_layered(csr->rowptr, csr->col, csr->n_nodes, x, ldx, H, *gnn, mlp, out, ldo,
-                              (float*)ws, (hipStream_t)stream);
+                              (float*)ws, (hipStream_t)stream, csr->node_offsets, csr->n_graphs);
 }
 
 size_t gnf_workspace_bytes(int64_t n_nodes, int32_t D, const GnfFlow* flow) {
@@ -340,6 +364,8 @@ int gnf_coupling_half_f32(const GnfCsr* csr, const GnfMlp* s_net, const GnfMlp* 
     }
     rc = validate_pair(s_net, t_net, gnn, H);
     if (rc) return rc;
+    rc = validate_node_offsets(csr, s_net, "gnf_coupling_half_f32");
+    if (rc) return rc;
     if (direction != GNF_FORWARD && direction != GNF_INVERSE) {
         set_error("gnf_coupling_half_f32: direction=%d", direction);
         return GNF_EINVAL;
@@ -358,6 +384,7 @@ int gnf_coupling_half_f32(const GnfCsr* csr, const GnfMlp* s_net, const GnfMlp* 
     int32_t nparts = 0;
     HalfStep hs{csr->rowptr, csr->col, csr->n_nodes, x_cond, x_upd, ld, H, direction, *gnn,
                 s_net, t_net, (double*)ws, &nparts, nullptr, csr->n_edges};
+    hs.node_offsets = csr->node_offsets, hs.n_graphs = csr->n_graphs;
     rc = run_half(hs, (float*)((char*)ws + p.partial_bytes), st);
     if (rc) return rc;
     if (logdet_accum)
@@ -453,6 +480,7 @@ int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_
         }
     }
     auto mark_attn = [&](HalfStep& hs, int half, int i) {
+        hs.node_offsets = csr->node_offsets, hs.n_graphs = csr->n_graphs;   // (graph-scope attention nets)
         if (!attn_pack) return;
         const int q = flow->weight_sharing ? half : half * T + i;
         hs.attn_packed[0] = attn_pack + (size_t)q * p.attn_pack_per_net;

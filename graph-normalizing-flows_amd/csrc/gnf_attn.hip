@@ -337,7 +337,46 @@ __global__ __launch_bounds__(512) void k_attn_agg(const AttnArgs a, int RB) {
         }
 }
 
+// the graph scope's rules (include/gnf.h, GnfAttnScope)
+static int validate_attn_graph(const GnfAttn* at, const GnfMlp* mlp, int32_t H, const char* what) {
+    if (!at->concat || at->residual) {
+        set_error("%s: graph-scope attention concatenates the node's features and has no residual (concat=%d residual=%d)",
+                  what, at->concat, at->residual);
+        return GNF_EINVAL;
+    }
+    if (at->out_dim < 1 || !attn_graph_geometry_ok(at->num_heads, at->kq_dim, at->v_dim)) {
+        set_error("%s: graph-scope attention dims heads=%d kq=%d v=%d out=%d outside heads in 1..%d, heads*kq <= %d, "
+                  "heads*v <= %d, out >= 1", what, at->num_heads, at->kq_dim, at->v_dim, at->out_dim, kAttnMaxHeads,
+                  kAttnMaxWidth, kAttnMaxWidth);
+        return GNF_ESHAPE;
+    }
+    if (!at->Wo && (at->num_heads != 1 || at->out_dim != at->v_dim)) {
+        set_error("%s: graph-scope attention without Wo needs one head and out_dim == v_dim (heads=%d out=%d v=%d)", what,
+                  at->num_heads, at->out_dim, at->v_dim);
+        return GNF_ESHAPE;
+    }
+    if (!at->Wq || !at->Wk || !at->Wv) {
+        set_error("%s: null attention weight pointer", what);
+        return GNF_EINVAL;
+    }
+    if (mlp->dims[0] != H + at->out_dim) {
+        set_error("%s: MLP input width %d but the attention front-end produces %d (H=%d, out_dim=%d)", what, mlp->dims[0],
+                  H + at->out_dim, H, at->out_dim);
+        return GNF_ESHAPE;
+    }
+    if (at->layer_norm && (!at->ln_gamma || !at->ln_beta)) {
+        set_error("%s: layer_norm needs ln_gamma and ln_beta", what);
+        return GNF_EINVAL;
+    }
+    return GNF_OK;
+}
+
 int validate_attn(const GnfAttn* at, const GnfMlp* mlp, int32_t H, const char* what) {
+    if (at->scope != GNF_ATTN_EDGES && at->scope != GNF_ATTN_GRAPH) {
+        set_error("%s: unknown attention scope %d", what, at->scope);
+        return GNF_EINVAL;
+    }
+    if (at->scope == GNF_ATTN_GRAPH) return validate_attn_graph(at, mlp, H, what);
     if (at->out_dim < 1 || !attn_geometry_ok(at->num_heads, at->kq_dim, at->v_dim, H)) {
         set_error("%s: attention dims heads=%d kq=%d v=%d out=%d on H=%d outside heads in 1..%d, heads*kq <= %d, heads*v <= %d, "
                   "pad16(2 heads kq + v) + pad16(H) + H <= %d, out >= 1",
@@ -561,7 +600,7 @@ __global__ __launch_bounds__(512) void k_attn_fwd_rows(const AttnArgs a, int win
 
 size_t attn_scratch_floats(const GnfAttn* at, int64_t n_nodes, int32_t in0) {
     if (!at) return 0;
-    const size_t P = 2 * (size_t)at->num_heads * at->kq_dim + at->v_dim;
+    const size_t P = (size_t)attn_qkv_width(at);
     // [2][n][P] q|k|v, [2][n][in0] h0, [2][n][heads*v] attended values, [2][n][3*heads] softmax statistics
     return 2 * (size_t)n_nodes * (P + (size_t)in0 + (size_t)at->num_heads * at->v_dim + 3 * (size_t)at->num_heads);
 }
@@ -569,6 +608,7 @@ size_t attn_scratch_floats(const GnfAttn* at, int64_t n_nodes, int32_t in0) {
 size_t attn_stash_slot_floats(const GnfFlow* flow, int64_t n_nodes) {
     const GnfMlp* net = flow && flow->s_nets ? &flow->s_nets[0] : nullptr;
     if (!net || !net->attn || n_nodes <= 0) return 0;
+    if (attn_is_graph(net->attn)) return 0;   // (the graph scope declines the stash: its backward recomputes the front-end)
     return attn_scratch_floats(net->attn, n_nodes, net->dims[0]);
 }
 

@@ -405,7 +405,7 @@ __global__ __launch_bounds__(256) void k_attn_proj_mfma(const AttnProjArgs a) {
 }
 
 int launch_attn_proj_mfma(const GnfAttn* const* at, int nets, int64_t n, const float* x, int64_t ldx, int32_t H, float* const* qkv,
-                          hipStream_t st, float* const* h0_concat, int32_t in0) {
+                          hipStream_t st, float* const* h0_concat, int32_t in0, int32_t v_width) {
     if (n == 0) return GNF_OK;
     AttnProjArgs a;
     for (int q = 0; q < 2; ++q) {
@@ -414,7 +414,7 @@ int launch_attn_proj_mfma(const GnfAttn* const* at, int nets, int64_t n, const f
         a.h0[q] = h0_concat ? h0_concat[q < nets ? q : 0] : nullptr;
     }
     a.in0 = in0;
-    a.x = x, a.ldx = ldx, a.n = (int32_t)n, a.H = H, a.nq = at[0]->num_heads * at[0]->kq_dim, a.v = at[0]->v_dim;
+    a.x = x, a.ldx = ldx, a.n = (int32_t)n, a.H = H, a.nq = at[0]->num_heads * at[0]->kq_dim, a.v = v_width > 0 ? v_width : at[0]->v_dim;
     hipLaunchKernelGGL(k_attn_proj_mfma, dim3((unsigned)((n + kPjRows - 1) / kPjRows), (unsigned)nets), dim3(256), 0, st, a);
     GNF_LAUNCH_CHECK("k_attn_proj_mfma");
     return GNF_OK;

@@ -26,7 +26,7 @@
 namespace gnf {
 
 size_t attn_pack_floats(const GnfAttn* at, int32_t H) {
-    if (!at) return 0;
+    if (!at || attn_is_graph(at)) return 0;
     return front_pack_floats(front_dims(H, at->num_heads, at->kq_dim, at->v_dim, at->out_dim));
 }
 
@@ -146,7 +146,7 @@ bool attn_front_fixed_geometry(const FrontDims& d) { return d.H == 32 && d.nh ==
 
 // does the one-launch front-end handle this head geometry? (else: the two-launch kernels)
 bool attn_front_fused_ok(const GnfAttn* at, int32_t H) {
-    if (!at) return false;
+    if (!at || attn_is_graph(at)) return false;   // (the edge scope's front-end only)
     const FrontDims d = front_dims(H, at->num_heads, at->kq_dim, at->v_dim, at->out_dim);
     if (kFrRows * d.nh > 256 || d.vd > 16 || d.kq > 16 || d.Hp > 128 || d.NVp > 256) return false;
     return (size_t)front_lds(d).total * sizeof(float) <= (size_t)160 * 1024;

@@ -59,6 +59,9 @@ struct HalfStep {
     const float* attn_packed[2] = {nullptr, nullptr};
     // ... and the sender window (lo, hi) of every 16-row tile of the batch (launch_attn_tiles, once per flow call), or NULL
     const int32_t* attn_tiles = nullptr;
+    // graph-scope attention nets (GnfAttn.scope == GNF_ATTN_GRAPH): GnfCsr.node_offsets / n_graphs of the batch
+    const int32_t* node_offsets = nullptr;
+    int64_t n_graphs = 0;
     // large-batch kernel, split row tiles (gnf_fused_big.hip): > 0 = the caller zeroed big_split_flags(scratch, ...) at the
     // start of its call and hands every half-step launch a value of its own (1, 2, ...); 0 = no split tiles
     int32_t split_epoch = 0;
@@ -175,7 +178,7 @@ int launch_half_layered(const HalfStep& hs, float* scratch, hipStream_t st);
 int launch_attn_pair(const HalfStep& hs, float* scratch, float** h0_pair, hipStream_t st);
 int launch_gnn_layered(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, const float* x,
                        int64_t ldx, int32_t H, const GnfGnnSpec& g, const GnfMlp* mlp, float* out,
-                       int64_t ldo, float* scratch, hipStream_t st);
+                       int64_t ldo, float* scratch, hipStream_t st, const int32_t* node_offsets = nullptr, int64_t n_graphs = 0);
 int launch_aggregate(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, const float* x,
                      int64_t ldx, int32_t H, int32_t mean, int32_t mode, float eps, float* out,
                      int64_t ldo, hipStream_t st);
@@ -293,6 +296,28 @@ inline bool attn_geometry_ok(int heads, int kq, int v, int H) {
            ((P + 15) & ~(int64_t)15) + ((H + 15) & ~15) + H <= kAttnMaxRowFloats;
 }
 int validate_attn(const GnfAttn* at, const GnfMlp* mlp, int32_t H, const char* what);
+// graph-scope attention (GnfAttn.scope == GNF_ATTN_GRAPH; include/gnf.h): its own limit (no row-width clause: its kernels
+// hold any H) and its own q | k | v row, 2 heads kq + heads v (the edge scope's is 2 heads kq + v)
+inline bool attn_is_graph(const GnfAttn* at) { return at && at->scope == GNF_ATTN_GRAPH; }
+inline bool attn_graph_geometry_ok(int heads, int kq, int v) {
+    return heads >= 1 && heads <= kAttnMaxHeads && kq >= 1 && v >= 1 && (int64_t)heads * kq <= kAttnMaxWidth &&
+           (int64_t)heads * v <= kAttnMaxWidth;
+}
+inline int64_t attn_qkv_width(const GnfAttn* at) {
+    return 2 * (int64_t)at->num_heads * at->kq_dim + (attn_is_graph(at) ? (int64_t)at->num_heads : 1) * at->v_dim;
+}
+// graph-scope front-end (gnf_attn_graph.hip): q | k | v of net q at scratch + q n P, h0[q] = [x || new]; agg_out / mz_out as
+// launch_attn_front's (a block without Wo leaves its attended values in h0[q][:, H:) whatever agg_out says)
+int launch_attn_graph_front(const GnfAttn* const* at, int nets, int64_t n, const float* x, int64_t ldx, int32_t H, int32_t in0,
+                            const int32_t* node_offsets, int64_t n_graphs, float* scratch, float* const* h0_out, hipStream_t st,
+                            float* const* agg_out = nullptr, float* const* mz_out = nullptr);
+// ... and backwards (gnf_attn_graph_bwd.hip): dq | dk | dv of both nets, then g_cond += dqkv [Wq | Wk | Wv]^T + dh0[:, :H)
+// of both nets; xc_dst != NULL: also copies x_cond [n, H] there for the weight-gradient GEMMs
+int launch_attn_graph_backward(const GnfAttn* const* at, int64_t n, int32_t H, int32_t in0, const int32_t* node_offsets,
+                               int64_t n_graphs, const float* const* qkv, const float* const* dagg, int64_t dagg_ld,
+                               const float* const* agg, int64_t agg_ld, float* const* stats, float* const* dqkv,
+                               const float* const* dh0, float* g_cond, int64_t ldg, const float* xc_src, int64_t xc_ld,
+                               float* xc_dst, hipStream_t st);
 size_t attn_scratch_floats(const GnfAttn* at, int64_t n_nodes, int32_t in0);
 // need_qkv: the caller reads the per-node q | k | v block of `scratch` afterwards (backward pass, attention stash)
 int launch_attn_front(const int32_t* rowptr, const int32_t* col, int64_t n, const float* x, int64_t ldx,
@@ -311,8 +336,9 @@ int launch_attn_core(const GnfAttn* a0, int nets, const int32_t* rowptr, const i
                      hipStream_t st);
 // q | k | v = x [Wq | Wk | Wv] of 1 or 2 nets on the matrix cores, any widths (gnf_attn_core.hip); qkv[q]: [N, P]
 // h0_concat != NULL: h0_concat[q][r, 0:H) = x[r, :] rides along (the concat half of a block's layer-0 rows, row stride in0)
+// v_width > 0: Wv has that many columns (the graph scope's heads * v) instead of v_dim
 int launch_attn_proj_mfma(const GnfAttn* const* at, int nets, int64_t n, const float* x, int64_t ldx, int32_t H, float* const* qkv,
-                          hipStream_t st, float* const* h0_concat = nullptr, int32_t in0 = 0);
+                          hipStream_t st, float* const* h0_concat = nullptr, int32_t in0 = 0, int32_t v_width = 0);
 // one-launch front-end for sparse batches (gnf_attn_front.hip), weights pre-packed into fragment order once per flow call
 bool attn_front_fused_ok(const GnfAttn* at, int32_t H);
 size_t attn_pack_floats(const GnfAttn* at, int32_t H);

@@ -633,7 +633,7 @@ static int lmax_of(const GnfMlp* m) {
 // One GNN module call: scratch = h0 [N, in0] | bufA [N, Lmax] | bufB [N, Lmax] | (s, t unused) | attention region
 int launch_gnn_layered(const int32_t* rowptr, const int32_t* col, int64_t n, const float* x,
                        int64_t ldx, int32_t H, const GnfGnnSpec& g, const GnfMlp* mlp, float* out,
-                       int64_t ldo, float* scratch, hipStream_t st) {
+                       int64_t ldo, float* scratch, hipStream_t st, const int32_t* node_offsets, int64_t n_graphs) {
     const int in0 = mlp->dims[0];
     const int lmax = lmax_of(mlp);
     float* h0 = scratch;
@@ -644,7 +644,9 @@ int launch_gnn_layered(const int32_t* rowptr, const int32_t* col, int64_t n, con
         float* attn_scratch = scratch + (size_t)n * (size_t)(in0 + kLayeredActBufs * lmax + 2 * H);
         const GnfAttn* at[1] = {mlp->attn};
         float* h0s[1] = {h0};
-        rc = launch_attn_front(rowptr, col, n, x, ldx, H, at, 1, in0, attn_scratch, h0s, st);
+        rc = attn_is_graph(mlp->attn)
+                 ? launch_attn_graph_front(at, 1, n, x, ldx, H, in0, node_offsets, n_graphs, attn_scratch, h0s, st)
+                 : launch_attn_front(rowptr, col, n, x, ldx, H, at, 1, in0, attn_scratch, h0s, st);
     } else {
         rc = launch_aggregate(rowptr, col, n, x, ldx, H, g.agg == GNF_AGG_MEAN,
                               g.combine == GNF_COMBINE_CONCAT ? 1 : 0, g.epsilon, h0, in0, st);
@@ -760,10 +762,16 @@ int launch_attn_pair(const HalfStep& hs, float* scratch, float** h0_pair, hipStr
     float* region = hs.attn_region ? hs.attn_region
                                    : scratch + (size_t)n * (size_t)(in0 + kLayeredActBufs * lmax + 2 * hs.H);
     const GnfAttn* a0 = hs.s_net->attn;
+    const GnfAttn* at[2] = {hs.s_net->attn, hs.t_net->attn};
+    if (attn_is_graph(a0)) {   // (no stash slot: attn_region is NULL for this scope)
+        const size_t Pg = (size_t)attn_qkv_width(a0);
+        h0_pair[0] = region + 2 * (size_t)n * Pg;
+        h0_pair[1] = h0_pair[0] + (size_t)n * in0;
+        return launch_attn_graph_front(at, 2, n, hs.x_cond, hs.ld, hs.H, in0, hs.node_offsets, hs.n_graphs, region, h0_pair, st);
+    }
     const size_t P = 2 * (size_t)a0->num_heads * a0->kq_dim + a0->v_dim;
     h0_pair[0] = region + 2 * (size_t)n * P;
     h0_pair[1] = h0_pair[0] + (size_t)n * in0;
-    const GnfAttn* at[2] = {hs.s_net->attn, hs.t_net->attn};
     // a stash slot also keeps the attended values and the softmax statistics (attn_scratch_floats' layout)
     const size_t NV = (size_t)a0->num_heads * a0->v_dim;
     float* agg0 = h0_pair[1] + (size_t)n * in0;

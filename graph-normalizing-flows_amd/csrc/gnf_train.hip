@@ -1064,7 +1064,7 @@ static BwdPlan plan_backward(int64_t n, int32_t D, const GnfMlp* net, int n_sets
     if (net->attn) {
         const GnfAttn* at = net->attn;
         p.nh = at->num_heads, p.kq = at->kq_dim, p.vd = at->v_dim, p.C = at->out_dim;
-        p.P = 2 * p.nh * p.kq + p.vd;
+        p.P = (int)attn_qkv_width(at);   // (2 heads kq + v; the graph scope's values are per head: 2 heads kq + heads v)
         p.NV = p.nh * p.vd;
         wsum += (int64_t)p.H * p.P + (int64_t)p.NV * p.C;
     }
@@ -1783,6 +1783,18 @@ static int weight_grad_jobs(const BwdPlan& p, const BwdOperands& o, const GnfMlp
             jobs[nj++] = WGJob{o.hin[e], o.ldh[e], o.dPs[e], o.lddp[e], nets[q]->dims[j], nets[q]->dims[j + 1],
                                const_cast<float*>(grads[q]->W[j]), const_cast<float*>(grads[q]->b[j])};
         }
+    if (attn_is_graph(nets[0]->attn)) {   // Wv is [H, heads v]; no Wo job for a block without an output projection
+        for (int q = 0; q < 2; ++q) {
+            const GnfAttn* ga = grads[q]->attn;
+            const int nq = p.nh * p.kq;
+            jobs[nj++] = WGJob{o.xc, p.H, o.dqkv[q], p.P, p.H, nq, const_cast<float*>(ga->Wq), nullptr};
+            jobs[nj++] = WGJob{o.xc, p.H, o.dqkv[q] + nq, p.P, p.H, nq, const_cast<float*>(ga->Wk), nullptr};
+            jobs[nj++] = WGJob{o.xc, p.H, o.dqkv[q] + 2 * nq, p.P, p.H, p.NV, const_cast<float*>(ga->Wv), nullptr};
+            if (nets[q]->attn->Wo)
+                jobs[nj++] = WGJob{o.agg[q], p.NV, o.dh0[q] + p.H, p.in0, p.NV, p.C, const_cast<float*>(ga->Wo), nullptr};
+        }
+        return nj;
+    }
     if (nets[0]->attn)
         for (int q = 0; q < 2; ++q) {
             const GnfAttn* ga = grads[q]->attn;
@@ -2040,7 +2052,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
         const GnfMlp* pairs[2][2] = {{&flow->s_nets[q], &grad->s_nets[q]}, {&flow->t_nets[q], &grad->t_nets[q]}};
         for (auto& pr : pairs) {
             if (pr[0]->attn && (!pr[1]->attn || !pr[1]->attn->Wq || !pr[1]->attn->Wk || !pr[1]->attn->Wv ||
-                                !pr[1]->attn->Wo)) {
+                                (pr[0]->attn->Wo && !pr[1]->attn->Wo))) {
                 set_error("gnf_grevnet_backward_f32: grad net %d needs a GnfAttn with Wq / Wk / Wv / Wo gradient buffers", q);
                 return GNF_EINVAL;
             }
@@ -2105,9 +2117,11 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
                     const size_t nq = (size_t)fa->num_heads * fa->kq_dim;
                     GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wq), 0, sizeof(float) * H * nq, st));
                     GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wk), 0, sizeof(float) * H * nq, st));
-                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wv), 0, sizeof(float) * H * fa->v_dim, st));
-                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wo), 0,
-                                               sizeof(float) * fa->num_heads * fa->v_dim * fa->out_dim, st));
+                    const size_t wv_cols = (size_t)(attn_is_graph(fa) ? fa->num_heads : 1) * fa->v_dim;   // (graph scope: per head)
+                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wv), 0, sizeof(float) * H * wv_cols, st));
+                    if (fa->Wo)   // (a graph-scope block may have no output projection)
+                        GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wo), 0,
+                                                   sizeof(float) * fa->num_heads * fa->v_dim * fa->out_dim, st));
                     if (fa->layer_norm) {
                         GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->ln_gamma), 0, sizeof(float) * H, st));
                         GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->ln_beta), 0, sizeof(float) * H, st));
@@ -2159,7 +2173,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
     // kernel then forms dagg = dnew Wo^T itself (its last table row) and the GEMM launch in front of the edge kernels
     // goes (7.7 us per half-step on the config-2 batch).
     bool wot_packed = false;
-    if (flow->s_nets[0].attn) {
+    if (flow->s_nets[0].attn && !attn_is_graph(flow->s_nets[0].attn)) {   // (edge scope only: the graph scope's dagg is a GEMM)
         for (int k0 = 0; k0 < n_nets_each; k0 += 32) {  // (64 pointers per array in the kernel's arguments: 32 nets of each kind a launch)
             const int cnt = n_nets_each - k0 < 32 ? n_nets_each - k0 : 32;
             PackWot pw;
@@ -2221,7 +2235,8 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
                                   const float* x_cond_, bool have_dagg = false, const float* const* wct_ = nullptr) -> int {
         const GnfAttn* at[2] = {nets_[0]->attn, nets_[1]->attn};
         const int off = at[0]->concat ? D / 2 : 0;
-        if (!have_dagg) {  // (else: the backward tile kernel's last table row has written it)
+        const bool graph = attn_is_graph(at[0]);
+        if (!have_dagg && (!graph || at[0]->Wo)) {  // (else: the backward tile kernel's last table row has written it)
             GemmJob jobs[2];
             for (int q = 0; q < 2; ++q) jobs[q] = GemmJob{o_.dh0[q] + off, at[q]->Wo, o_.dagg[q], nullptr, nullptr};
             GemmShape sh;
@@ -2230,6 +2245,16 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
             sh.M = n, sh.K = p.C, sh.N = p.NV, sh.chunks = 1, sh.kchunk = TGK;
             const int rc_ = launch_gemm<OPND_KC, OPND_KC, EPI_MASK>(jobs, 2, sh, st);
             if (rc_) return rc_;
+        }
+        if (graph) {   // the graph scope's two passes + dL/dx_cond (gnf_attn_graph_bwd.hip); no batch-norm moments left behind
+            const bool proj = at[0]->Wo != nullptr;   // (without Wo the attended values and their gradient live in h0 / dh0[:, H:))
+            const float* dg[2] = {proj ? o_.dagg[0] : o_.dh0[0] + off, proj ? o_.dagg[1] : o_.dh0[1] + off};
+            const float* ag[2] = {proj ? o_.agg[0] : o_.h0[0] + off, proj ? o_.agg[1] : o_.h0[1] + off};
+            const float* qk[2] = {o_.qkv[0], o_.qkv[1]};
+            const float* dh[2] = {o_.dh0[0], o_.dh0[1]};
+            if (bnf && bnf->n_parts) *bnf->n_parts = 0;
+            return launch_attn_graph_backward(at, n, D / 2, p.in0, csr->node_offsets, csr->n_graphs, qk, dg, proj ? p.NV : p.in0, ag,
+                                              proj ? p.NV : p.in0, o_.stats, o_.dqkv, dh, g_cond, D, x_cond_, ld, o_.xc, st);
         }
         return launch_attn_backward(at, n, D / 2, p.in0, csr->rowptr, csr->col, csr_t->rowptr, csr_t->col, o_.qkv, o_.dh0, o_.gst,
                                     o_.dqkv, o_.agg, o_.dagg, o_.stats, g_cond, D, st, csr->n_edges, bnf, x_cond_, ld, o_.xc, wct_);
@@ -2288,8 +2313,11 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
             if (attn) {   // recompute the attention front-end of both nets (q | k | v kept for the way back)
                 const GnfAttn* at[2] = {nets[0]->attn, nets[1]->attn};
                 if (!stashed) {
-                    rc = launch_attn_front(csr->rowptr, csr->col, n, x_cond, ld, H, at, 2, p.in0, o.qkv[0], o.h0, st,
-                                           csr->n_edges, true, nullptr, o.agg, o.stats);
+                    rc = attn_is_graph(at[0])
+                             ? launch_attn_graph_front(at, 2, n, x_cond, ld, H, p.in0, csr->node_offsets, csr->n_graphs, o.qkv[0], o.h0,
+                                                       st, o.agg, o.stats)
+                             : launch_attn_front(csr->rowptr, csr->col, n, x_cond, ld, H, at, 2, p.in0, o.qkv[0], o.h0, st,
+                                                 csr->n_edges, true, nullptr, o.agg, o.stats);
                     if (rc) return rc;
                 }
                 // (the conditioning half as the dW GEMMs of Wq / Wk / Wv read it, o.xc, is copied by the attention

@@ -11,10 +11,19 @@ def make_gnn_fn(hp):
     """hp: D, latent, K, activation ("relu" | "leaky_relu"), then either
          agg ("sum" | "mean"), combine ("agg" | "concat"), epsilon             (run_grevnet.py:154-180)
        or attn = dict(num_heads, kq_dim, v_dim, out_dim, concat, kq_dim_division, residual[, layer_norm])
-                                                                                (run_grevnet.py:199-211)."""
+                                                                                (run_grevnet.py:199-211)
+       or attn = dict(scope="graph", kq_dim, v_dim[, num_heads, out_dim, kq_dim_division, layer_norm]): whole-graph
+          attention, MultiheadSelfAttention - or SelfAttention without out_dim (run_grevnet.py:214-237)."""
     act = gnn.leaky_relu if hp["activation"] == "leaky_relu" else gnn.relu
     mk_mlp = partial(gnn.make_mlp_model, hp["latent"], hp["D"] / 2, hp["K"], act, 0.01, hp.get("bias_init_stddev", 0.1))
     a = hp.get("attn")
+    if a and a.get("scope") == "graph":   # whole-graph attention (run_grevnet.py:214-237): no out_dim = SelfAttention
+        if a.get("out_dim") is None:
+            return partial(gnn.self_attn_gnn, kq_dim=a["kq_dim"], v_dim=a["v_dim"], make_mlp_fn=mk_mlp,
+                           kq_dim_division=a.get("kq_dim_division", True))
+        return partial(gnn.multihead_self_attn_gnn, kq_dim=a["kq_dim"], v_dim=a["v_dim"], concat_heads_output_dim=a["out_dim"],
+                       make_mlp_fn=mk_mlp, num_heads=a.get("num_heads", 1), kq_dim_division=a.get("kq_dim_division", True),
+                       layer_norm=a.get("layer_norm", False))
     if a:
         return partial(gnn.dm_self_attn_gnn, kq_dim=a["kq_dim"], v_dim=a["v_dim"], make_mlp_fn=mk_mlp,
                        num_heads=a["num_heads"], concat_heads_output_dim=a["out_dim"], concat=a["concat"],

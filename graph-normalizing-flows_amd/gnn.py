@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .graphs import GraphsTuple, csr_of
+from .graphs import GraphsTuple, csr_desc, csr_of
 
 # ----------------------------------------------------------------------------------------------
 # tokens standing in for tf.unsorted_segment_{sum,mean} (gnn.py:239,245,251,256) and tf.nn.*
@@ -195,6 +195,7 @@ def make_mlp_model(latent_dim, output_dim, num_layers, activation=relu, l2_regul
 # ----------------------------------------------------------------------------------------------
 class _NodeBlock:
     combine = None
+    graph_scope = False   # True: the block's attention reads the batch's graph boundaries (GnfCsr.node_offsets)
 
     def spec(self):
         return _abi.GnfGnnSpec(self._agg, self.combine, float(getattr(self, "epsilon", 0.0)),
@@ -230,12 +231,12 @@ class _NodeBlock:
         if attn is not None:
             desc.attn = C.pointer(attn)
         spec = self.spec()
-        csr = csr_of(graph)
+        csr = csr_desc(graph, csr_of(graph), self.graph_scope)
         out = torch.empty(n, mlp.layer_sizes[-1], dtype=torch.float32, device=x.device)
         ws_bytes = lib.gnf_gnn_workspace_bytes(n, h, C.byref(desc), spec.combine)
         ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=x.device)
         with torch.cuda.device(x.device):
-            _abi.check(lib.gnf_gnn_apply_f32(C.byref(csr.desc), C.byref(desc), C.byref(spec), _abi.ptr(x),
+            _abi.check(lib.gnf_gnn_apply_f32(C.byref(csr), C.byref(desc), C.byref(spec), _abi.ptr(x),
                                              x.stride(0), h, _abi.ptr(out), out.stride(0), _abi.ptr(ws),
                                              ws_bytes, _abi.stream_ptr(x.device)), "gnf_gnn_apply_f32")
         return graph.replace(nodes=out)
@@ -262,6 +263,61 @@ class AggThenMLPBlock(_NodeBlock):
         self._mlp = make_mlp_fn()
         self.epsilon = epsilon
         self.name = name
+
+
+class _AttentionParams:
+    """Parameter plumbing shared by the attention blocks: attn_params {key: fp32 tensor [in, out] (or [out] for the
+    layer norm)} in _shapes() order, created at first connection like Sonnet does (_init_weight), set / get as dicts."""
+
+    def attn_version(self):
+        return self._attn_version
+
+    def attn_keys(self):
+        return tuple(self._shapes(0))
+
+    def ensure_attn_built(self, h, device):
+        if self.attn_params is None:
+            p = {}
+            for key, shp in self._shapes(h).items():
+                if len(shp) == 1:               # snt.LayerNorm: gamma = 1, beta = 0
+                    p[key] = torch.ones(shp) if key == "ln_gamma" else torch.zeros(shp)
+                    continue
+                p[key] = self._init_weight(key, *shp)
+            self.attn_params = p
+            self._attn_version += 1
+            _touch()
+        for key, shp in self._shapes(h).items():
+            if tuple(self.attn_params[key].shape) != shp:
+                raise ValueError(f"{self.name}: {key} has shape {tuple(self.attn_params[key].shape)}, expected {shp}")
+        if self.attn_params["wq"].device != torch.device(device):
+            self.attn_params = {k: v.to(device) for k, v in self.attn_params.items()}
+            self._attn_version += 1
+            _touch()
+        return self
+
+    def set_attn_params(self, attn):
+        """attn: dict with the block's attn_keys() (numpy or torch, [in, out]; ln_gamma, ln_beta [MLP output width]);
+        other keys are ignored."""
+        p = {}
+        for key in self.attn_keys():
+            w = attn[key]
+            w = torch.as_tensor(np.asarray(w) if not isinstance(w, torch.Tensor) else w).to(torch.float32).contiguous()
+            if w.ndim != (1 if key.startswith("ln_") else 2):
+                raise ValueError(f"{self.name}: {key} must be " + ("1-D [out]" if key.startswith("ln_") else "2-D [in, out]"))
+            p[key] = w
+        self.attn_params = p
+        self._attn_version += 1
+        _touch()
+        return self
+
+    def get_attn_params(self):
+        return None if self.attn_params is None else {k: v.detach().cpu().numpy().copy() for k, v in self.attn_params.items()}
+
+
+def _xavier_uniform(fi, fo):
+    """tf.contrib.layers.xavier_initializer(uniform=True)"""
+    a = math.sqrt(6.0 / (fi + fo))
+    return torch.empty(fi, fo).uniform_(-a, a, generator=_GEN)
 
 
 class DMSelfAttentionMLP(_NodeBlock):
@@ -376,6 +432,86 @@ def dm_self_attn_gnn(kq_dim, v_dim, make_mlp_fn, num_heads, concat_heads_output_
     return DMSelfAttentionMLP(kq_dim=kq_dim, v_dim=v_dim, make_mlp_fn=make_mlp_fn, num_heads=num_heads,
                               concat_heads_output_dim=concat_heads_output_dim, concat=concat,
                               residual=residual, layer_norm=layer_norm, kq_dim_division=kq_dim_division)
+
+
+class MultiheadSelfAttention(_AttentionParams, _NodeBlock):
+    """gnn.py:576-660: whole-graph ("graph transformer") multi-head self-attention - every node attends to every node of
+    its own graph, itself included, whatever the edge list says - heads concatenated and projected to
+    `concat_heads_output_dim`, concatenated with the node's own features, then the MLP (optionally followed by
+    snt.LayerNorm).  No residual.  Weights (all [in, out], no bias, all xavier-uniform - Wo included):
+    wq, wk [H, heads*kq], wv [H, heads*v] (one value projection PER HEAD, unlike DMSelfAttentionMLP's shared one),
+    wo [heads*v, C]; layer_norm=True adds ln_gamma (ones) / ln_beta (zeros) of the MLP's output width.
+    The reference's dense [N, N] masked softmax over the batch is computed per graph (include/gnf.h, GnfAttn.scope):
+    the library reads the batch's graph boundaries (GnfCsr.node_offsets) and never the edges."""
+    combine = _abi.GNF_COMBINE_EPS   # unused by attention nets
+    _agg = _abi.GNF_AGG_SUM          # unused by attention nets
+    graph_scope = True
+    _project = True                  # False: no output projection (SelfAttention)
+
+    def __init__(self, kq_dim, v_dim, concat_heads_output_dim, make_mlp_fn, num_heads=1, kq_dim_division=True,
+                 layer_norm=False, name="multihead_self_attention"):
+        self.kq_dim = int(kq_dim)
+        self.v_dim = int(v_dim)
+        self.concat_heads_output_dim = int(concat_heads_output_dim)
+        self.mlp = make_mlp_fn()
+        self._mlp = self.mlp
+        self.num_heads = int(num_heads)
+        self.kq_dim_division = bool(kq_dim_division)
+        self.layer_norm = bool(layer_norm)
+        self.name = name
+        self.attn_params = None     # {"wq", "wk", "wv"[, "wo"][, "ln_gamma", "ln_beta"]} fp32 tensors
+        self._attn_version = 0
+
+    def in_dim(self, h):
+        return h + self.concat_heads_output_dim
+
+    def signature(self):
+        return (type(self).__name__, self.num_heads, self.kq_dim, self.v_dim, self.concat_heads_output_dim,
+                self.layer_norm, self.kq_dim_division, self._mlp.act_code, self._mlp.alpha)
+
+    def _shapes(self, h):
+        nq, nv = self.num_heads * self.kq_dim, self.num_heads * self.v_dim
+        shapes = {"wq": (h, nq), "wk": (h, nq), "wv": (h, nv)}
+        if self._project:
+            shapes["wo"] = (nv, self.concat_heads_output_dim)
+        if self.layer_norm:
+            w_out = self._mlp.layer_sizes[-1]
+            shapes.update(ln_gamma=(w_out,), ln_beta=(w_out,))
+        return shapes
+
+    def _init_weight(self, key, fi, fo):
+        return _xavier_uniform(fi, fo)
+
+    def attn_desc(self, h, device):
+        self.ensure_attn_built(h, device)
+        p = self.attn_params
+        return _abi.GnfAttn(self.num_heads, self.kq_dim, self.v_dim, self.concat_heads_output_dim,
+                            1, int(self.kq_dim_division), 0, int(self.layer_norm),
+                            p["wq"].data_ptr(), p["wk"].data_ptr(), p["wv"].data_ptr(),
+                            p["wo"].data_ptr() if self._project else 0,
+                            p["ln_gamma"].data_ptr() if self.layer_norm else 0,
+                            p["ln_beta"].data_ptr() if self.layer_norm else 0, _abi.GNF_ATTN_GRAPH)
+
+
+class SelfAttention(MultiheadSelfAttention):
+    """gnn.py:681-735: MultiheadSelfAttention with one head and NO output projection - the MLP input is
+    [x || attended], of width H + v_dim - and no layer norm.  Weights wq, wk [H, kq], wv [H, v] (xavier-uniform)."""
+    _project = False
+
+    def __init__(self, kq_dim, v_dim, make_mlp_fn, kq_dim_division, name="self_attention"):
+        super().__init__(kq_dim, v_dim, v_dim, make_mlp_fn, num_heads=1, kq_dim_division=kq_dim_division,
+                         layer_norm=False, name=name)
+
+
+def multihead_self_attn_gnn(kq_dim, v_dim, concat_heads_output_dim, make_mlp_fn, num_heads=1, kq_dim_division=True,
+                            layer_norm=False):                                                   # gnn.py:662-677
+    return MultiheadSelfAttention(kq_dim=kq_dim, v_dim=v_dim, concat_heads_output_dim=concat_heads_output_dim,
+                                  make_mlp_fn=make_mlp_fn, num_heads=num_heads, kq_dim_division=kq_dim_division,
+                                  layer_norm=layer_norm)
+
+
+def self_attn_gnn(kq_dim, v_dim, make_mlp_fn, kq_dim_division):                               # gnn.py:738-739
+    return SelfAttention(kq_dim, v_dim, make_mlp_fn, kq_dim_division)
 
 
 class IdentityModule:
@@ -578,7 +714,7 @@ class GRevNet:
     def get_params(self):
         out = {}
         for kind in ("s", "t"):
-            flat = [({"attn": b.get_attn_params(), "mlp": b._mlp.get_params()} if isinstance(b, DMSelfAttentionMLP)
+            flat = [({"attn": b.get_attn_params(), "mlp": b._mlp.get_params()} if hasattr(b, "get_attn_params")
                      else b._mlp.get_params()) for b in self.blocks(kind)]
             t = self.num_timesteps
             out[kind] = flat if self.weight_sharing else [flat[:t], flat[t:]]
@@ -589,6 +725,11 @@ class GRevNet:
     def repack(self):
         """Call after mutating weight tensors in place (the packed MFMA copies are stale otherwise)."""
         self._cache = None
+
+    def graph_scope(self):
+        """Do the nets attend within whole graphs (MultiheadSelfAttention / SelfAttention)?  Then every library call
+        gets the batch's graph boundaries (GnfCsr.node_offsets)."""
+        return self._block_of(self._gnns("s")[0]).graph_scope if self._gnns("s") else False
 
     def _flow(self, hdim, device):
         fast = (str(device), hdim, bool(self.fused), self._bn_sync_key(), _EPOCH[0])
@@ -713,7 +854,7 @@ class GRevNet:
         if n == 0 and self._bn_sync_world() > 1:
             raise ValueError("sync_batch_norm: a rank with an empty shard cannot take part in the cross-rank moments "
                              "(every rank must make the same sequence of all-reduce calls)")
-        csr = csr_of(graph)
+        csr = csr_desc(graph, csr_of(graph), self.graph_scope())
         with torch.cuda.device(dev):   # (the planners read the CURRENT device's CU count: size and launch on the same one)
             ws_bytes = lib.gnf_workspace_bytes(n, d, C.byref(flow))
         ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
@@ -722,7 +863,7 @@ class GRevNet:
             # sums_out: caller-owned fp64 buffer whose first two slots receive [logdet, sum z^2]
             sums = sums_out if sums_out is not None else torch.empty(2, dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
-            _abi.check(lib.gnf_grevnet_from_f32(C.byref(csr.desc), C.byref(flow), _abi.ptr(src), src.stride(0) if n else d,
+            _abi.check(lib.gnf_grevnet_from_f32(C.byref(csr), C.byref(flow), _abi.ptr(src), src.stride(0) if n else d,
                                                 _abi.ptr(out), d, d, direction, _abi.ptr(sums), _abi.ptr(ws), ws_bytes,
                                                 _abi.stream_ptr(dev)), "gnf_grevnet_from_f32")
         return out, sums

@@ -178,3 +178,46 @@ def csr_of(graph, by_sender=False):
 
 def clear_csr_cache():
     _CSR_CACHE.clear()
+
+
+# ----------------------------------------------------------------------------------------------
+# Graph boundaries (GnfCsr.node_offsets, ABI v10): what the graph-scope attention nets read
+# ----------------------------------------------------------------------------------------------
+_OFFSETS_CACHE = collections.OrderedDict()
+_OFFSETS_CACHE_MAX = 16
+
+
+def node_offsets_of(graph):
+    """Exclusive prefix sum of n_node, int32 [n_graphs + 1] on the nodes' device (computed there with torch.cumsum),
+    cached on the identity of the n_node tensor - a cache of its own, so csr_of's key and behaviour stay as they are."""
+    nn = graph.n_node
+    dev = graph.nodes.device
+    key = (nn.data_ptr(), int(nn.shape[0]), str(nn.device), str(dev))
+    hit = _OFFSETS_CACHE.get(key)
+    if hit is not None:
+        _OFFSETS_CACHE.move_to_end(key)
+        return hit[0]
+    off = torch.zeros(int(nn.shape[0]) + 1, dtype=torch.int32, device=dev)
+    if nn.shape[0]:
+        off[1:] = torch.cumsum(nn.to(device=dev, dtype=torch.int64), 0).to(torch.int32)
+    _OFFSETS_CACHE[key] = (off, nn)   # (n_node kept alive: its data_ptr cannot be recycled while cached)
+    while len(_OFFSETS_CACHE) > _OFFSETS_CACHE_MAX:
+        _OFFSETS_CACHE.popitem(last=False)
+    return off
+
+
+def csr_desc(graph, csr, node_offsets=False):
+    """The GnfCsr handed to the library for `graph`: csr.desc itself, or (node_offsets=True: a net of the call has
+    graph-scope attention) a copy of it with node_offsets / n_graphs filled in; the copy holds the offsets tensor."""
+    if not node_offsets:
+        return csr.desc
+    off = node_offsets_of(graph)
+    d = _abi.GnfCsr.from_buffer_copy(csr.desc)
+    d.node_offsets = off.data_ptr()
+    d.n_graphs = int(off.shape[0]) - 1
+    d._keep = off
+    return d
+
+
+def clear_node_offsets_cache():
+    _OFFSETS_CACHE.clear()

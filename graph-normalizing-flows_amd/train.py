@@ -26,7 +26,7 @@ import torch
 from . import _abi
 from .gnn import _touch as _gnn_touch
 from .flow import LN_2PI
-from .graphs import csr_of
+from .graphs import csr_desc, csr_of
 
 
 class _StepTerms(dict):
@@ -202,13 +202,14 @@ class GRevNetTrainer:
                 ga = gattn[q]
                 ga.num_heads, ga.kq_dim, ga.v_dim, ga.out_dim = blk.num_heads, blk.kq_dim, blk.v_dim, blk.concat_heads_output_dim
                 ga.layer_norm = int(blk.layer_norm)
-                ptrs = []
+                ga.scope = _abi.GNF_ATTN_GRAPH if blk.graph_scope else _abi.GNF_ATTN_EDGES
+                ptrs = {}
                 for k in blk.attn_keys():
-                    ptrs.append(self.grad.data_ptr() + 4 * off)
+                    ptrs[k] = self.grad.data_ptr() + 4 * off
                     off += blk.attn_params[k].numel()
-                ga.Wq, ga.Wk, ga.Wv, ga.Wo = ptrs[:4]
+                ga.Wq, ga.Wk, ga.Wv, ga.Wo = ptrs["wq"], ptrs["wk"], ptrs["wv"], ptrs.get("wo", 0)   # (SelfAttention: no wo)
                 if blk.layer_norm:
-                    ga.ln_gamma, ga.ln_beta = ptrs[4:]
+                    ga.ln_gamma, ga.ln_beta = ptrs["ln_gamma"], ptrs["ln_beta"]
                 arr = gs if q < n else gt
                 arr[q % n].attn = C.cast(C.byref(gattn, q * C.sizeof(_abi.GnfAttn)), C.POINTER(_abi.GnfAttn))
         spec = net.blocks("s")[0].spec()
@@ -332,7 +333,7 @@ class GRevNetTrainer:
         net.last_sums = sums
         z_graph = graph.replace(nodes=z)
         flow = net._flow(d // 2, dev)
-        csr, csr_t = csr_of(graph), csr_of(graph, by_sender=True)
+        csr, csr_t = csr_desc(graph, csr_of(graph), net.graph_scope()), csr_of(graph, by_sender=True)
         ws_bytes = lib.gnf_backward_workspace_bytes(n, d, C.byref(flow))
         if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != dev:
             self._ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
@@ -342,7 +343,7 @@ class GRevNetTrainer:
             self._aux = None
         state = z_graph.nodes.clone()                             # z in, x (reconstructed) out
         with torch.cuda.device(dev):
-            _abi.check(lib.gnf_grevnet_backward_f32(C.byref(csr.desc), C.byref(csr_t.desc), C.byref(flow),
+            _abi.check(lib.gnf_grevnet_backward_f32(C.byref(csr), C.byref(csr_t.desc), C.byref(flow),
                                                     C.byref(self._grad_flow), _abi.ptr(state), state.stride(0), d,
                                                     _abi.ptr(self._ws), ws_bytes, _abi.stream_ptr(dev),
                                                     C.c_void_p(self._aux.cuda_stream if self._aux is not None else 0)),

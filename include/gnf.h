@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define GNF_ABI_VERSION 9
+#define GNF_ABI_VERSION 10
 #define GNF_MAX_LAYERS 8 /* Linear layers per MLP (gnn.py:165-166 builds num_layers of them) */
 
 typedef void* gnf_stream_t; /* hipStream_t */
@@ -69,6 +69,13 @@ typedef struct GnfCsr {
     const int32_t* col;    /* [n_edges] sender node ids */
     int64_t n_nodes;       /* N = sum(n_node)  (run_grevnet.py:298) */
     int64_t n_edges;       /* E = sum(n_edge), self loops included */
+    /* ABI v10: where each graph of the batch starts - device int32 [n_graphs + 1], the exclusive prefix sum of n_node
+     * (node_offsets[0] = 0, node_offsets[n_graphs] = n_nodes).  Read by the graph-scope attention nets only (GnfAttn.scope
+     * == GNF_ATTN_GRAPH): NULL / 0 is allowed unless a net of the call has that scope (GNF_EINVAL then).  Every entry point
+     * that takes a CSR and a net reads them from its csr argument (gnf_grevnet_backward_f32: from csr, not csr_t).
+     * Offsets that do not describe the batch give wrong numbers, never an access outside the node arrays. */
+    const int32_t* node_offsets;
+    int64_t n_graphs;
 } GnfCsr;
 
 /* Optional attention front-end of a net: DMSelfAttentionMLP (gnn.py:480-553) around DMSelfAttention
@@ -83,6 +90,27 @@ typedef struct GnfCsr {
  * the block's output after the residual add (gnn.py:550-552): (h - mean) / sqrt(var + GNF_LN_EPS) * ln_gamma
  * + ln_beta with the biased per-row variance; ln_gamma / ln_beta have the MLP's output width. */
 #define GNF_LN_EPS 1e-5f
+/* ABI v10, GnfAttn.scope: which nodes a node attends to.
+ *   GNF_ATTN_EDGES (0, the default of a zeroed struct): the senders of its incoming edges - DMSelfAttention as above.
+ *   GNF_ATTN_GRAPH (1): every node of its own graph, itself included, whatever the edge list says (an edgeless batch is
+ *     valid) - MultiheadSelfAttention / SelfAttention (gnn.py:576-738, the "graph transformer" choices self_attn /
+ *     multihead_self_attn of run_grevnet.py and singlehead_my_attn / multihead_my_attn of train_grevnet_with_data.py):
+ *       q = x Wq, k = x Wk [N, heads, kq];  v = x Wv [N, heads, v] - one value projection PER HEAD, Wv is [H, heads*v];
+ *       logit[h, i, j] = <q[i, h], k[j, h]> (/ sqrt(kq) if kq_dim_division) - the ATTENDING node's q, the reverse of the
+ *       edge scope's orientation; softmax over the j of i's graph (GnfCsr.node_offsets); attended[i, h*v + c];
+ *       new = attended Wo ([heads*v, out_dim], no bias), or attended itself when Wo == NULL (SelfAttention: needs
+ *       num_heads == 1 and out_dim == v_dim, GNF_ESHAPE otherwise); the MLP input is [x || new].
+ *     The reference forms a dense [N, N] logit matrix over the whole batch, subtracts 100000 * (1 - loss_mask) and takes a
+ *     row softmax over the batch (gnn.py:620-631, loss.py:131-151).  In fp32 exp(l - 1e5 - max) is exactly 0 whenever a
+ *     row's logits span less than about 1e5 (the whole range of the drivers' nets by many orders of magnitude), so that
+ *     softmax IS the per-graph softmax computed here: O(sum n_g^2) work, O(N) memory, nothing of size [N, N].
+ *     concat must be 1 and residual 0 (GNF_EINVAL otherwise); layer_norm is snt.LayerNorm on the MLP output as above.
+ *     Limit (forward, inverse and backward alike): num_heads in 1..64, num_heads * kq_dim <= 256, num_heads * v_dim <= 256,
+ *     any H (GNF_ESHAPE otherwise) - both drivers' defaults (8 heads of 10 / 10, C = 80, H = 1; 1 head of 64 / 64, C = 64,
+ *     H = 100) are inside it.  GnfFlow.attn_stash is declined: gnf_attn_stash_bytes() returns 0 for such a flow and the
+ *     backward pass recomputes the front-end.
+ *   Any other value: GNF_EINVAL.  The s and t nets of one flow must have the same scope. */
+enum GnfAttnScope { GNF_ATTN_EDGES = 0, GNF_ATTN_GRAPH = 1 };
 typedef struct GnfAttn {
     /* ONE limit, checked by every entry point that takes the block (forward, inverse, backward): num_heads in 1..64 and
      * num_heads * kq_dim <= 256 and num_heads * v_dim <= 256 and, with H = D / 2 the width of the conditioning half,
@@ -102,10 +130,11 @@ typedef struct GnfAttn {
     int32_t layer_norm;
     const float* Wq; /* [H, num_heads*kq_dim] */
     const float* Wk; /* [H, num_heads*kq_dim] */
-    const float* Wv; /* [H, v_dim] */
-    const float* Wo; /* [num_heads*v_dim, out_dim] */
+    const float* Wv; /* [H, v_dim]; GNF_ATTN_GRAPH: [H, num_heads*v_dim] */
+    const float* Wo; /* [num_heads*v_dim, out_dim]; GNF_ATTN_GRAPH: may be NULL (no output projection) */
     const float* ln_gamma; /* [MLP output width], read when layer_norm != 0 (else may be NULL) */
     const float* ln_beta;  /* [MLP output width] */
+    int32_t scope;         /* ABI v10: GnfAttnScope */
 } GnfAttn;
 
 /* One snt.nets.MLP (gnn.py:159-180): num_layers Linear layers, y = x @ W + b, W row-major [in,out];
