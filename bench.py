@@ -16,6 +16,11 @@ with the path's single collective: one all-reduce of [logdet, sum z^2, num_nodes
 
 Prints ONE JSON line (rank 0).  `value` = node-updates/s over all GPUs, one node-update = one node
 through one GRevNet timestep (both half couplings), SURVEY.md 8d.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line; nothing else.
+`--full` adds every figure that takes runs of its own after the timed regions: the kernel-timing leg and roofline,
+kernel A, the latency / CSR-rebuild / host-fed / two-stream / graph-replay / D = 100 legs, the inverse round trip, the
+CPU baseline and (config 2) the other workloads as `secondary_workloads`.
 """
 import argparse
 import json
@@ -409,6 +414,9 @@ def main():
                     help="device pre-warm in front of the W warmup steps: the same step in a loop for this long (a fresh "
                          "process runs its first ~100 iterations up to 8 %% slower - clocks, first touches); 0 = off")
     ap.add_argument("--layered", action="store_true", help="run the generic layered kernels instead of the fused one")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions also measure everything beyond the headline (roofline, kernel A, secondary "
+                         "legs, CPU baseline, secondary workloads); the --no-* / *-steps options below select among these")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary legs (CSR rebuild per step, host_fed, two_streams): what the rocprofv3 "
@@ -424,7 +432,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5,
                     help="timed regions of --steps steps each, back to back: the line reports the median one (+ spread)")
     ap.add_argument("--no-secondary-workloads", action="store_true",
-                    help="the default config2 run on one GPU also runs config4, config5, config2_attn and default_flags as child "
+                    help="a --full config2 run on one GPU also runs config4, config5, config2_attn and default_flags as child "
                          "processes (3 timed regions each) and attaches their headline fields as secondary_workloads - the "
                          "at-scale roofline fractions in the same driver-timed line; this flag (or --no-secondary) turns that off")
     ap.add_argument("--secondary-steps", type=int, default=0, help="steps per timed region of the secondary workloads (0: --steps, capped at 40)")
@@ -624,6 +632,55 @@ def main():
         else:                     # sums = [log_det_jacobian, sum z^2, num_nodes], reduced over the ranks when sharded
             arrays = {"z": res, "sums": row}
         dumped = dump_outputs(args.dump_outputs, arrays)
+
+    out = {
+        "metric": ("node-updates/sec (fwd+logdet) on community_medium batch" if args.workload == "config2" else
+                   f"node-updates/sec ({'inverse' if inverse else 'fwd+logdet'}) on {args.workload}"), "value": round(value, 1),
+        "unit": "node-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "spread": spread, "prewarm_steps": prewarm_steps, "host_enqueue_ms_per_step": round(1e3 * t_enqueued / args.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {WORKLOAD['desc']} batch={GRAPHS_PER_GPU}/GPU ({GRAPHS_PER_GPU * world} graphs total), "
+                               f"{HP['T']}-step GRevNet {'inverse (sampling)' if inverse else 'fwd+logdet'}, D={HP['D']} L={HP['latent']} K={HP['K']} "
+                               + ("dm_self_attn GNN relu" if HP.get("attn") else "avg_then_mlp eps=1 leaky_relu(0.2)")
+                               + (", fully connected topology" if WORKLOAD["fc"] else ", sparse topology+self loops"),
+                   "nodes_total": n_global, "edges_total": e_global, "nodes_rank0": n_local, "edges_rank0": e_local,
+                   "weights": f"N(0,2/(fan_in+fan_out)), seed {WEIGHT_SEED}, last layer x{FINAL_SCALE}",
+                   "parallelism": f"graph-shard dp{world}, 1 all-reduce of 3xfp64 per step (async: overlapped with the next batch's forward)" if multi else "single GPU",
+                   "path": "fused MFMA half-step kernel" if net.fused else "layered kernels",
+                   "csr": f"built on device once per batch before the timed region (gnf_build_csr: {csr_ms:.3f} ms wall incl. host launch), cached",
+                   "host_sync": "every step" if args.sync_each_step else "results copied to pinned host memory each step; one sync at end"},
+        "log_prob_xs_per_node": last["log_prob_xs_per_node"],
+        "steps_landed_on_host": int(torch.isfinite(host[args.warmup:args.warmup + args.steps, :2]).all(dim=1).sum()) if trainer is None and not inverse else None,
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if trainer is not None:
+        out["train_state"] = ("variables and optimiser state restored to the initial ones before every timed region (outside it): "
+                              "log_prob_xs_per_node is the value after exactly `steps` steps on the one fixed batch")
+    if multi:   # how evenly the shards came out (whole graphs per rank, greedy balance): every rank's nodes / edges
+        shard = torch.tensor([n_local, e_local], dtype=torch.int64, device=dev if args.dist_backend == "nccl" else "cpu")
+        allsh = [torch.zeros_like(shard) for _ in range(world)]
+        dist.all_gather(allsh, shard)
+        nodes_r, edges_r = [int(t[0]) for t in allsh], [int(t[1]) for t in allsh]
+        out["nccl_ranks_seen"] = dist.get_world_size()      # what the process group itself says after init
+        out["dist_backend"] = dist.get_backend()
+        out["launcher"] = "bench.py itself (one child process per GPU)" if os.environ.get("GNF_BENCH_SELF_LAUNCHED") else "external (torch.distributed.run)"
+        out["config"]["nodes_per_rank"] = nodes_r
+        out["config"]["edges_per_rank"] = edges_r
+        out["config"]["shard_imbalance_max_over_mean"] = {"nodes": round(max(nodes_r) * world / max(1, sum(nodes_r)), 4),
+                                                           "edges": round(max(edges_r) * world / max(1, sum(edges_r)), 4)}
+
+    def finish():
+        out["consistency"] = line_consistency_errors(out)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if multi:
+            dist.destroy_process_group()
+
+    if not args.full:         # the headline line is complete: a plain run ends here
+        finish()
+        return
 
     # ---- secondary figure: the same step when the batch's topology is new every step (training loop
     # of run_grevnet.py:440-447 draws a fresh batch per step): CSR rebuilt on device inside the step
@@ -895,37 +952,8 @@ def main():
                 "algorithmic_flops_per_launch": flops, "algorithmic_bytes_per_launch": abytes,
                 "hbm_floor_us": round(abytes / (PEAK_HBM_GBS * 1e3), 3)}
 
-    out = {
-        "metric": ("node-updates/sec (fwd+logdet) on community_medium batch" if args.workload == "config2" else
-                   f"node-updates/sec ({'inverse' if inverse else 'fwd+logdet'}) on {args.workload}"), "value": round(value, 1),
-        "unit": "node-updates/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "spread": spread, "prewarm_steps": prewarm_steps, "host_enqueue_ms_per_step": round(1e3 * t_enqueued / args.steps, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {WORKLOAD['desc']} batch={GRAPHS_PER_GPU}/GPU ({GRAPHS_PER_GPU * world} graphs total), "
-                               f"{HP['T']}-step GRevNet {'inverse (sampling)' if inverse else 'fwd+logdet'}, D={HP['D']} L={HP['latent']} K={HP['K']} "
-                               + ("dm_self_attn GNN relu" if HP.get("attn") else "avg_then_mlp eps=1 leaky_relu(0.2)")
-                               + (", fully connected topology" if WORKLOAD["fc"] else ", sparse topology+self loops"),
-                   "nodes_total": n_global, "edges_total": e_global, "nodes_rank0": n_local, "edges_rank0": e_local,
-                   "weights": f"N(0,2/(fan_in+fan_out)), seed {WEIGHT_SEED}, last layer x{FINAL_SCALE}",
-                   "parallelism": f"graph-shard dp{world}, 1 all-reduce of 3xfp64 per step (async: overlapped with the next batch's forward)" if multi else "single GPU",
-                   "path": "fused MFMA half-step kernel" if net.fused else "layered kernels",
-                   "csr": f"built on device once per batch before the timed region (gnf_build_csr: {csr_ms:.3f} ms wall incl. host launch), cached",
-                   "host_sync": "every step" if args.sync_each_step else "results copied to pinned host memory each step; one sync at end"},
-        "log_prob_xs_per_node": last["log_prob_xs_per_node"],
-        "steps_landed_on_host": int(torch.isfinite(host[args.warmup:args.warmup + args.steps, :2]).all(dim=1).sum()) if trainer is None and not inverse else None,
-        "latency": latency,
-        "graph_replay": graph_replay,
-        "secondary_D100": d100,
-        "with_csr_rebuild_each_step": rebuild,
-        "two_streams": two_streams,
-        "host_fed": host_fed,
-        "roofline": roofline,
-        "kernel_a": kernel_a,
-    }
-    if dumped is not None:
-        out["dumped_outputs"] = dumped
-
+    out.update(latency=latency, graph_replay=graph_replay, secondary_D100=d100, with_csr_rebuild_each_step=rebuild,
+               two_streams=two_streams, host_fed=host_fed, roofline=roofline, kernel_a=kernel_a)
     if trainer is not None:
         # one trainer step = forward + dL/dx chain + weight gradients: 3 x the forward's algorithmic flops (what tf.gradients
         # executes; the reversible walk's recompute, where a stash does not replace it, is NOT counted as useful work)
@@ -936,8 +964,6 @@ def main():
                                  "traffic": traffic, "traffic_kernel": traffic_kernel,
                                  "note": "3 x the forward's algorithmic flops per step (forward, dX chain, dW) / ms_per_step: the whole "
                                          "step incl. Adam, the re-pack and every small launch; `roofline` above is the forward flow alone"}
-        out["train_state"] = ("variables and optimiser state restored to the initial ones before every timed region (outside it): "
-                              "log_prob_xs_per_node is the value after exactly `steps` steps on the one fixed batch")
     if inverse:   # round-trip check f(g(z)) = z on the device (size-independent property)
         zg = net(graph, inverse=False)
         back, _ = net(zg, inverse=True)
@@ -949,18 +975,6 @@ def main():
         out["cpu_baseline"] = cb
         out["speedup_vs_cpu_baseline"] = round(value / cb["value"], 2)
         out["log_prob_delta_vs_cpu_fp32"] = abs(last["log_prob_xs_per_node"] - ref["log_prob_xs_per_node"])
-    if multi:   # how evenly the shards came out (whole graphs per rank, greedy balance): every rank's nodes / edges
-        shard = torch.tensor([n_local, e_local], dtype=torch.int64, device=dev if args.dist_backend == "nccl" else "cpu")
-        allsh = [torch.zeros_like(shard) for _ in range(world)]
-        dist.all_gather(allsh, shard)
-        nodes_r, edges_r = [int(t[0]) for t in allsh], [int(t[1]) for t in allsh]
-        out["nccl_ranks_seen"] = dist.get_world_size()      # what the process group itself says after init
-        out["dist_backend"] = dist.get_backend()
-        out["launcher"] = "bench.py itself (one child process per GPU)" if os.environ.get("GNF_BENCH_SELF_LAUNCHED") else "external (torch.distributed.run)"
-        out["config"]["nodes_per_rank"] = nodes_r
-        out["config"]["edges_per_rank"] = edges_r
-        out["config"]["shard_imbalance_max_over_mean"] = {"nodes": round(max(nodes_r) * world / max(1, sum(nodes_r)), 4),
-                                                           "edges": round(max(edges_r) * world / max(1, sum(edges_r)), 4)}
     if (rank == 0 and not multi and args.workload == "config2" and not args.layered and not args.no_secondary
             and not args.no_secondary_workloads and not args.sync_each_step):
         import subprocess
@@ -969,12 +983,12 @@ def main():
         torch.cuda.synchronize()
         # forward workloads at --secondary-steps; the two trainer workloads (run_grevnet.py:344-377,440-447 on the config-2 batch;
         # train_grevnet_with_data.py:380,478-554 with that driver's literal defaults) with their own step caps: the
-        # whole default run has to stay within a minute or so
+        # whole --full run has to stay within a minute or so
         children = [(wl, ksteps) for wl in ("config4", "config5", "config2_attn", "default_flags", "data_default_flags")]
         children += [("config2_train", min(ksteps, 20)), ("data_default_flags_train", min(ksteps, 6))]
         for wl, wsteps in children:
             cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", str(wsteps), "--warmup", str(min(args.warmup, 10 if wsteps > 6 else 2)),
-                   "--repeats", "3", "--no-cpu-baseline", "--no-secondary", "--latency-steps", "0"]
+                   "--repeats", "3", "--full", "--no-cpu-baseline", "--no-secondary", "--latency-steps", "0"]
             if wl == "data_default_flags_train":
                 cmd += ["--prewarm-ms", "100"]
             try:
@@ -989,11 +1003,7 @@ def main():
                 sec[wl] = {"error": err}
         out["secondary_workloads"] = sec
         out["secondary_workloads_wall_s"] = round(time.perf_counter() - t_sec, 1)
-    out["consistency"] = line_consistency_errors(out)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if multi:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

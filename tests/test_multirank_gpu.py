@@ -87,11 +87,11 @@ def test_bench_four_ranks_on_one_device_match_one_rank(workload, graphs_per_rank
 def test_bench_gpus_2_launches_its_own_ranks():
     """The driver's command shape for N > 1 is `python bench.py --gpus N --steps K --warmup W` with NO launcher in front:
     bench.py starts its N ranks itself (bench.self_launch).  On the one-GPU box the two ranks share cuda:0 and talk over
-    gloo; everything else is the default line (no flags switching legs off)."""
+    gloo; with --full and no flags switching legs off, so that `consistency` also covers the kernel-timing leg."""
     env = dict(os.environ, GNF_BENCH_ONE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--dist-backend", "gloo"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--dist-backend", "gloo"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1000, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
@@ -130,7 +130,7 @@ def test_bench_one_rank_through_the_rccl_branch_of_the_sharded_path():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--dist-backend", "nccl", "--steps", "6",
-           "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--latency-steps", "0", "--kernel-timing-steps", "1", "--repeats", "2"]
+           "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary", "--latency-steps", "0", "--kernel-timing-steps", "1", "--repeats", "2"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 wl=${1:-config4}
 for g in ${2:-16 32 64 128 256}; do
   for sh in ${3:-0 22 20 40}; do
-    GNF_OPTIONS="force_shape=$sh" python bench.py --workload $wl --graphs-per-gpu $g --steps 10 --warmup 3 --prewarm-ms 50 --no-cpu-baseline \
+    GNF_OPTIONS="force_shape=$sh" python bench.py --full --workload $wl --graphs-per-gpu $g --steps 10 --warmup 3 --prewarm-ms 50 --no-cpu-baseline \
         --no-secondary --latency-steps 0 --kernel-timing-steps 5 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:

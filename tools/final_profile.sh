@@ -4,7 +4,8 @@
 #   tools/final_profile.sh pmc <tag> [workloads]   PMC / kernel-stat passes (tools/pmc_shape.sh) of the forward workloads (kernel A
 #                                       reported next to the dominant kernel), the training workloads and the wide layers
 #     -> here: for w in ...; do python tools/summarize_profile.py --pmc-shape gpurun_out/pmc_<tag>_$w $w; done; commit
-#   tools/final_profile.sh bench <tag>  one un-profiled bench line per workload + the driver-shaped default run
+#   tools/final_profile.sh bench <tag> [dir]  one un-profiled --full bench line per workload + the --full default run, into dir
+#                                       (default: profiles/, where they are committed)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 phase=${1:-pmc}; tag=${2:-r4z}
 cd $R
@@ -24,9 +25,12 @@ if [ "$phase" = pmc ]; then
     want $w && timeout 900 bash tools/pmc_shape.sh ${tag}_$w $w "" k_linear_short,k_gemm,k_attn,k_adam,k_pack,k_bn,k_coupling,k_aggregate > gpurun_out/pmc_${tag}_$w.log 2>&1
   done
 else
+  dst=${3:-profiles}
   for w in config2_fc config2_attn default_flags config4 config5 wide_fc config2_train default_flags_train data_default_flags data_default_flags_train wide_fc_train; do
-    timeout 300 python bench.py --workload $w --no-cpu-baseline --no-secondary --latency-steps 0 2>/dev/null | tail -1 > gpurun_out/${tag}_bench_$w.json
+    timeout 300 python bench.py --full --workload $w --no-cpu-baseline --no-secondary --latency-steps 0 2>/dev/null | tail -1 > $dst/${tag}_bench_$w.json
   done
-  ( time timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 ) 2> gpurun_out/${tag}_bench_config2_default_run.time | tail -1 > gpurun_out/${tag}_bench_config2_default_run.json
+  ( time timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 ) 2> $dst/${tag}_bench_config2_default_run.time | tail -1 > $dst/${tag}_bench_config2_default_run.json
+  ls $dst | grep $tag
+  exit
 fi
 ls gpurun_out | grep $tag

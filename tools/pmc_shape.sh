@@ -9,7 +9,7 @@ tag=$1; wl=$2; export GNF_OPTIONS=$3; also=$4
 out=$R/gpurun_out/pmc_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --workload $wl --no-cpu-baseline --no-secondary --latency-steps 0 --prewarm-ms 0"
+B="python $R/bench.py --full --workload $wl --no-cpu-baseline --no-secondary --latency-steps 0 --prewarm-ms 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o kt -- $B --steps 20 --warmup 5 > $out/bench_under_rocprof.log 2>&1
 python -c "import sys; sys.path.insert(0, '$R'); import bench; print(bench.kernel_source_stamp('$wl'), ' '.join(sorted(set(bench.WORKLOAD_SOURCES['$wl']))))" > $out/source_stamp.txt
 python $R/tools/kstats.py $out/trace 6 > $out/kernel_stats.txt

@@ -72,10 +72,10 @@ def merge_pmc_shape(src, workload, dst):
             short = re.sub(r"^(void )?gnf::", "", name).split("(")[0]
             dom["kernels"][short] = entry(name, avg_us, vals)
     merge_traffic(os.path.join(dst, "pmc_traffic.json"), stamp, sources, workload, dom)
-    lines = [f"# tools/pmc_shape.sh {tag} {workload}: rocprofv3 --kernel-trace --stats of bench.py --workload {workload} --steps 20 "
+    lines = [f"# tools/pmc_shape.sh {tag} {workload}: rocprofv3 --kernel-trace --stats of bench.py --full --workload {workload} --steps 20 "
              "--warmup 5 --no-cpu-baseline --no-secondary --latency-steps 0 --prewarm-ms 0, then one --pmc pass per counter group",
              open(os.path.join(src, "kernel_stats.txt")).read(), txt,
-             f"# bench.py --workload {workload} --steps 50 --warmup 10 on the same box, un-profiled:",
+             f"# bench.py --full --workload {workload} --steps 50 --warmup 10 on the same machine, un-profiled:",
              open(os.path.join(src, "bench.json")).read().strip().split("\n")[-1]]
     open(os.path.join(dst, f"{tag}_rocprof_summary.txt"), "w").write("\n".join(lines) + "\n")
 
