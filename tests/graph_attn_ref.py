@@ -4,7 +4,8 @@ for the tests of the graph-scope attention (GnfAttn.scope == GNF_ATTN_GRAPH).
 `GraphAttnGather` is the oracle's Fp32Gather with attn_gnn taking the graph scope: every node attends to every node of its
 own graph, the softmax per graph (the library's form).  `literal_attended` transcribes the reference's own op order - dense
 [N, N] logits over the whole batch, loss_mask, `logits -= 100000 * (1 - mask)`, row softmax over the batch - which the CPU
-tests pin the restatement against.  Parameters: {"attn": {scope: "graph", num_heads, kq_dim, v_dim, kq_dim_division,
+tests pin the restatement against.  `per_graph=True` takes the softmax block by block instead of over dense [heads, N, N]
+logits (O(sum n_g^2): large batches); the CPU tests pin it to both.  Parameters: {"attn": {scope: "graph", num_heads, kq_dim, v_dim, kq_dim_division,
 layer_norm, wq, wk, wv[, wo][, ln_gamma, ln_beta]}, "mlp": [(W, b), ...]}: no "wo" = SelfAttention."""
 import math
 
@@ -26,11 +27,13 @@ def _keys(attn):
 class GraphAttnGather(O.Fp32Gather):
     """Fp32Gather (default float64 here) with the graph scope; n_node gives the graphs of the batch."""
 
-    def __init__(self, senders, receivers, n_node, dtype=None, **kw):
+    def __init__(self, senders, receivers, n_node, dtype=None, per_graph=False, **kw):
         import torch
         n_node = np.asarray(n_node, np.int64)
         super().__init__(senders, receivers, int(n_node.sum()), dtype=dtype or torch.float64, **kw)
         self.graph_id = torch.as_tensor(np.repeat(np.arange(len(n_node)), n_node))
+        self.n_node = n_node
+        self.per_graph = per_graph   # True: attended_per_graph, O(sum n_g^2) instead of the dense [heads, N, N]
 
     def prep_params(self, params):
         def conv(m):
@@ -48,6 +51,8 @@ class GraphAttnGather(O.Fp32Gather):
 
     def attended(self, x, a):
         """[N, heads v] attended values, softmax over each node's own graph (columns h v + c)"""
+        if self.per_graph:
+            return self.attended_per_graph(x, a)
         torch = self.torch
         nh, kq, vd = int(a["num_heads"]), int(a["kq_dim"]), int(a["v_dim"])
         n = x.shape[0]
@@ -60,6 +65,38 @@ class GraphAttnGather(O.Fp32Gather):
         same = self.graph_id[:, None] == self.graph_id[None, :]
         w = torch.softmax(logits.masked_fill(~same, -float("inf")), dim=-1)
         return torch.einsum("hij,jhc->ihc", w, v).reshape(n, nh * vd)
+
+    def attended_per_graph(self, x, a):
+        """attended() block by block: the graphs of one size are stacked into [G, n_g, heads, .] and attend among
+        themselves; empty graphs are skipped, a one-node graph's row is its own v (a softmax over one key is 1)."""
+        torch = self.torch
+        nh, kq, vd = int(a["num_heads"]), int(a["kq_dim"]), int(a["v_dim"])
+        n = x.shape[0]
+        q = (x @ a["wq"]).reshape(n, nh, kq)
+        k = (x @ a["wk"]).reshape(n, nh, kq)
+        v = (x @ a["wv"]).reshape(n, nh, vd)
+        off = np.concatenate([[0], np.cumsum(self.n_node)])
+        rows, parts = [], []
+        for size in sorted(set(int(m) for m in self.n_node if m > 0)):
+            idx = np.stack([np.arange(off[g], off[g] + size) for g in np.nonzero(self.n_node == size)[0]])   # [G, size]
+            it = torch.as_tensor(idx.ravel())
+            if size == 1:
+                parts.append(v.index_select(0, it))
+            else:
+                qg = q.index_select(0, it).reshape(len(idx), size, nh, kq)
+                kg = k.index_select(0, it).reshape(len(idx), size, nh, kq)
+                vg = v.index_select(0, it).reshape(len(idx), size, nh, vd)
+                logits = torch.einsum("gihd,gjhd->ghij", qg, kg)
+                if a.get("kq_dim_division", True):
+                    logits = logits / math.sqrt(kq)
+                w = torch.softmax(logits, dim=-1)
+                parts.append(torch.einsum("ghij,gjhc->gihc", w, vg).reshape(-1, nh, vd))
+            rows.append(idx.ravel())
+        if not parts:
+            return x.new_zeros((n, nh * vd))
+        inv = np.empty(n, np.int64)
+        inv[np.concatenate(rows)] = np.arange(n)
+        return torch.cat(parts).index_select(0, torch.as_tensor(inv)).reshape(n, nh * vd)
 
     def attn_gnn(self, x, net):
         a = net["attn"]
@@ -182,9 +219,13 @@ def loss_and_grads(n_node, senders, receivers, x, params, num_timesteps, weight_
             return [(w.clone().requires_grad_(True), b.clone().requires_grad_(True)) for (w, b) in m]
         return [mark(q) for q in m]
 
+    def _grad(w):   # (None: the loss does not reach w - wq, wk of a batch of one-node graphs in the per-graph form)
+        return w.grad.numpy().copy() if w.grad is not None else np.zeros(tuple(w.shape), np.float64 if w.dtype == o.torch.float64
+                                                                           else np.float32)
+
     def grads_of(m):
         if isinstance(m, dict) and "attn" in m:
-            return {"attn": {k: m["attn"][k].grad.numpy().copy() for k in _keys(m["attn"])}, "mlp": grads_of(m["mlp"])}
+            return {"attn": {k: _grad(m["attn"][k]) for k in _keys(m["attn"])}, "mlp": grads_of(m["mlp"])}
         if isinstance(m, dict) and "gamma" in m:
             return {"gamma": m["gamma"].grad.numpy().copy(), "beta": m["beta"].grad.numpy().copy()}
         if isinstance(m, list) and m and isinstance(m[0], tuple):

@@ -30,6 +30,46 @@ def test_restatement_equals_the_literal_masked_batch_softmax(heads, kq, v, div):
     np.testing.assert_allclose(got[0], (x[0] @ a["wv"]), rtol=0, atol=1e-12)
 
 
+N_NODE_EMPTIES = np.array([0, 3, 1, 0, 0, 6, 1, 1, 4, 0])   # empty graphs leading, interior (in a row), trailing
+
+
+@pytest.mark.parametrize("heads,kq,v,div", [(3, 4, 5, True), (1, 6, 6, False)])
+def test_per_graph_form_equals_the_dense_form_and_the_literal(heads, kq, v, div):
+    """The per-graph oracle (GraphAttnGather(per_graph=True), O(sum n_g^2)) against the dense [heads, N, N] form and the
+    reference's literal op order, forward and float64 autograd gradients of a whole flow, on a batch with empty and one-node
+    graphs."""
+    rng = np.random.default_rng(heads * 10 + kq)
+    h = 5
+    n = int(N_NODE_EMPTIES.sum())
+    x = rng.standard_normal((n, h))
+    a = R.make_graph_attn_net_params(rng, h, 8, 2, num_heads=heads, kq_dim=kq, v_dim=v, out_dim=4 if heads > 1 else None,
+                                     kq_dim_division=div, dtype=np.float64)["attn"]
+    s, r = np.zeros(0, np.int32), np.zeros(0, np.int32)
+    outs = []
+    for per_graph in (False, True):
+        o = R.GraphAttnGather(s, r, N_NODE_EMPTIES, per_graph=per_graph)
+        pa = o.prep_params({"s": [{"attn": a, "mlp": []}]})["s"][0]["attn"]
+        outs.append(o.attended(o.to_t(x), pa).numpy())
+    np.testing.assert_allclose(outs[1], outs[0], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(outs[1], R.literal_attended(x, a, N_NODE_EMPTIES), rtol=0, atol=1e-12)
+    for i in np.cumsum(N_NODE_EMPTIES)[N_NODE_EMPTIES == 1] - 1:       # one-node graphs: exactly their own v
+        np.testing.assert_allclose(outs[1][i], x[i] @ a["wv"], rtol=0, atol=1e-14)
+    # a whole flow: log-prob, z, inverse and every gradient
+    d, t = 6, 2
+    kw = dict(num_heads=heads, kq_dim=kq, v_dim=v, kq_dim_division=div)
+    if heads > 1:
+        kw.update(out_dim=4, layer_norm=True)
+    p = R.make_graph_attn_grevnet_params(21, d // 2, 8, 2, t, dtype=np.float64, final_scale=0.25, **kw)
+    x = rng.standard_normal((n, d))
+    dense, per = (R.loss_and_grads(N_NODE_EMPTIES, s, r, x, p, t, activation="relu", per_graph=pg) for pg in (False, True))
+    assert abs(per["total_loss"] - dense["total_loss"]) <= 1e-10 * max(1.0, abs(dense["total_loss"]))
+    np.testing.assert_allclose(per["z"], dense["z"], rtol=1e-12, atol=1e-12)
+    for gp, gd in zip(_flat(per["grads"]), _flat(dense["grads"])):
+        np.testing.assert_allclose(gp, gd, rtol=1e-10, atol=1e-11)
+    np.testing.assert_allclose(R.inverse(N_NODE_EMPTIES, s, r, per["z"], p, t, activation="relu", per_graph=True), x,
+                               rtol=0, atol=1e-10)
+
+
 def _flat(g):
     out = []
     if isinstance(g, dict):

@@ -52,10 +52,11 @@ def _net(p, d, latent, k, t, ws=False):
     return make_product_grevnet(R.hp_of(p, d, latent, k, t, ws), p)
 
 
-def _check_flow(net, nn, ne, s, r, x, p, t, ws=False, lp_tol=1e-4, z_tol=3e-4):
+def _check_flow(net, nn, ne, s, r, x, p, t, ws=False, lp_tol=1e-4, z_tol=3e-4, per_graph=False):
+    """per_graph: the oracle's block-diagonal form (large batches; the same numbers as the dense one)"""
     from gnf_amd.flow import log_prob_terms
     n, d = x.shape
-    ref = R.log_prob(nn, s, r, x, p, t, ws, activation="relu")
+    ref = R.log_prob(nn, s, r, x, p, t, ws, activation="relu", per_graph=per_graph)
     graph = graph_from_arrays(nn, ne, s, r, x, DEV)
     out = log_prob_terms(net, graph)
     torch.cuda.synchronize()
@@ -67,7 +68,8 @@ def _check_flow(net, nn, ne, s, r, x, p, t, ws=False, lp_tol=1e-4, z_tol=3e-4):
         np.testing.assert_allclose(back, x, atol=z_tol, rtol=z_tol)
     zs = np.random.default_rng(5).standard_normal((n, d)).astype(np.float32)
     xg = net(graph.replace(nodes=torch.as_tensor(zs).to(DEV)), inverse=False).nodes.cpu().numpy()
-    np.testing.assert_allclose(xg, R.inverse(nn, s, r, zs, p, t, ws, activation="relu"), atol=z_tol, rtol=z_tol)
+    np.testing.assert_allclose(xg, R.inverse(nn, s, r, zs, p, t, ws, activation="relu", per_graph=per_graph), atol=z_tol,
+                               rtol=z_tol)
     return graph
 
 
@@ -202,18 +204,21 @@ def _check_all_grads(got, ref, scale, ref32=None):
         assert err <= tol, f"{name}: max err {err:.3e} > {tol:.3e} (max|g| {np.abs(b).max():.3e})"
 
 
-def _train_check(p, nn, ne, s, r, x, d, latent, k, t, ws=False, scale=5e-4, l2=None):
+def _train_check(p, nn, ne, s, r, x, d, latent, k, t, ws=False, scale=5e-4, l2=None, per_graph=False, setup=None):
+    """per_graph: as in _check_flow; setup(trainer) runs before the step (e.g. to choose the backward walk)"""
     from gnf_amd.train import GRevNetTrainer
     net = _net(p, d, latent, k, t, ws)
     graph = graph_from_arrays(nn, ne, s, r, x, DEV)
-    ref = R.loss_and_grads(nn, s, r, x, p, t, ws, activation="relu")
+    ref = R.loss_and_grads(nn, s, r, x, p, t, ws, activation="relu", per_graph=per_graph)
     tr = GRevNetTrainer(net)
+    if setup is not None:
+        setup(tr)
     out = tr.loss_and_grads(graph)
     torch.cuda.synchronize()
     n = int(nn.sum())
     assert abs(float(out["total_loss"]) - ref["total_loss"]) <= 1e-4 * n
     np.testing.assert_allclose(out["reconstruction"].cpu().numpy(), x, atol=3e-4, rtol=3e-4)
-    r32 = R.loss_and_grads(nn, s, r, x, p, t, ws, activation="relu", dtype=torch.float32)
+    r32 = R.loss_and_grads(nn, s, r, x, p, t, ws, activation="relu", dtype=torch.float32, per_graph=per_graph)
     _check_all_grads(tr.named_gradients(), ref["grads"], scale, r32["grads"])
     if l2 is not None:
         gb = _flat_all(ref["grads"])

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import graph_attn_ref as R
 from helpers import GuardBanded, graph_from_arrays, make_product_grevnet
 from oracle import gnf_oracle as O
 
@@ -94,19 +95,19 @@ def _assert_same_or_close(got, want, same, atol, rtol, what):
 def _flow_call(net, graph, dst, direction, src=None):
     """gnf_grevnet_from_f32 on `dst`'s window, reading `src`'s window (None: in place, gnf_grevnet_f32).  Returns sums."""
     from gnf_amd import _abi
-    from gnf_amd.graphs import csr_of
+    from gnf_amd.graphs import csr_desc, csr_of
     lib = _lib()
     n, d = dst.n, dst.d
     flow = net._flow(d // 2, torch.device(DEV))
-    csr = csr_of(graph)
+    csr = csr_desc(graph, csr_of(graph), net.graph_scope())
     ws_bytes = lib.gnf_workspace_bytes(n, d, C.byref(flow))
     ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=DEV)
     sums = torch.full((2,), float("nan"), dtype=torch.float64, device=DEV)
     if src is None:
-        rc = lib.gnf_grevnet_f32(C.byref(csr.desc), C.byref(flow), dst.ptr(), dst.ld, d, direction, _abi.ptr(sums),
+        rc = lib.gnf_grevnet_f32(C.byref(csr), C.byref(flow), dst.ptr(), dst.ld, d, direction, _abi.ptr(sums),
                                  _abi.ptr(ws), ws_bytes, _stream())
     else:
-        rc = lib.gnf_grevnet_from_f32(C.byref(csr.desc), C.byref(flow), src.ptr(), src.ld, dst.ptr(), dst.ld, d, direction,
+        rc = lib.gnf_grevnet_from_f32(C.byref(csr), C.byref(flow), src.ptr(), src.ld, dst.ptr(), dst.ld, d, direction,
                                       _abi.ptr(sums), _abi.ptr(ws), ws_bytes, _stream())
     _check(rc, "gnf_grevnet_from_f32")
     torch.cuda.synchronize()
@@ -129,6 +130,28 @@ ATTN_DEFAULT = dict(num_heads=8, kq_dim=10, v_dim=10, out_dim=80, concat=True, k
 ATTN_DATA = dict(num_heads=1, kq_dim=64, v_dim=64, out_dim=64, concat=True, kq_dim_division=True, residual=False)
 ATTN_LN = dict(num_heads=3, kq_dim=7, v_dim=5, out_dim=20, concat=False, kq_dim_division=True, residual=True, layer_norm=True)
 ATTN_RES = dict(num_heads=3, kq_dim=7, v_dim=5, out_dim=20, concat=False, kq_dim_division=True, residual=True)
+# graph-scope attention (tests/graph_attn_ref.py): multi-head with Wo and layer norm at <1,1,8>; SelfAttention (no Wo) at <4,4,8>
+GATTN_I1 = dict(scope="graph", num_heads=4, kq_dim=6, v_dim=5, out_dim=12, kq_dim_division=True, layer_norm=True)
+GATTN_I4 = dict(scope="graph", num_heads=1, kq_dim=64, v_dim=64, kq_dim_division=True, layer_norm=False)
+
+
+def _ghp(d, latent, k, t, attn, ws=False):
+    """a graph-scope flow's hyper-parameters (graph_attn_ref.hp_of)"""
+    return dict(D=d, latent=latent, K=k, T=t, agg="sum", combine="agg", epsilon=0.0, activation="relu", weight_sharing=ws,
+                attn=attn)
+
+
+def _is_graph(hp):
+    return hp.get("attn", {}).get("scope") == "graph"
+
+
+def _graph_params(seed, hp):
+    a = hp["attn"]
+    kw = {k: a[k] for k in ("num_heads", "kq_dim", "v_dim", "kq_dim_division", "layer_norm")}
+    if "out_dim" in a:
+        kw["out_dim"] = a["out_dim"]
+    return R.make_graph_attn_grevnet_params(seed, hp["D"] // 2, hp["latent"], hp["K"], hp["T"],
+                                            weight_sharing=hp["weight_sharing"], final_scale=0.3, **kw)
 
 FLOW_CASES = {
     # k_half_fused at its forced shapes, both message-passing reductions and both combines
@@ -159,6 +182,9 @@ FLOW_CASES = {
     "odd_D2": (_hp(2, 16, 3, 2), "gs", None, {}, True),
     "odd_D6": (_hp(6, 20, 1, 2, agg="sum", combine="concat", eps=0.0), "gs", None, {}, True),
     "odd_D14": (_hp(14, 32, 2, 3), "gs", None, {}, True),
+    # graph-scope attention: the front-end reads x at ldx
+    "graph_attn_multihead_ln_I1": (_ghp(16, 48, 2, 2, GATTN_I1), "cm", [3, 50, 77], {}, True),
+    "graph_attn_single_I4_h7": (_ghp(14, 48, 2, 1, GATTN_I4), "cm", [3, 50, 77], {}, True),
 }
 
 
@@ -173,6 +199,13 @@ def _flow_problem(name):
     rng = np.random.default_rng(sum(map(ord, name)))
     x = rng.standard_normal((n, d)).astype(np.float32)
     zs = rng.standard_normal((n, d)).astype(np.float32)
+    if _is_graph(hp):
+        x *= 0.5
+        zs *= 0.5
+        p = _graph_params(d + 3, hp)
+        ref = R.log_prob(nn, s, r, x, p, t, ws, activation="relu")
+        xg = R.inverse(nn, s, r, zs, p, t, ws, activation="relu")
+        return dict(hp=hp, nn=nn, ne=ne, s=s, r=r, n=n, x=x, zs=zs, p=p, ref=ref, xg=xg)
     if "attn" in hp:
         x *= 0.3 if hp["attn"]["residual"] else 0.5          # (a residual block adds x to s: |z| grows with it)
         zs *= 0.3 if hp["attn"]["residual"] else 0.5
@@ -240,7 +273,11 @@ def test_flow_forward_and_inverse(options, name, layout, mode):
         np.testing.assert_array_equal(sums, s0)
     # the float64 oracle (tolerances of test_parity_gpu.py)
     lp_tol = 1e-4
-    if pr["hp"].get("attn", {}).get("layer_norm"):
+    if pr["hp"].get("attn", {}).get("layer_norm") and _is_graph(pr["hp"]):
+        r32 = R.log_prob(pr["nn"], pr["s"], pr["r"], x, pr["p"], pr["hp"]["T"], pr["hp"]["weight_sharing"], activation="relu",
+                         dtype=torch.float32)
+        lp_tol = 1e-4 + 6.0 * abs(r32["log_prob_xs_per_node"] - pr["ref"]["log_prob_xs_per_node"])
+    elif pr["hp"].get("attn", {}).get("layer_norm"):
         o32 = O.Fp32Gather(pr["s"], pr["r"], n, activation="relu")
         r32 = o32.log_prob(o32.to_t(x), o32.prep_params(pr["p"]), pr["hp"]["T"], pr["hp"]["weight_sharing"])
         lp_tol = 1e-4 + 6.0 * abs(r32["log_prob_xs_per_node"] - pr["ref"]["log_prob_xs_per_node"])
@@ -345,7 +382,7 @@ def test_aggregate(layout, h, agg):
 def _gnn_apply(mod, graph, xb, ob):
     """gnf_gnn_apply_f32 with the caller's strides: the module call of gnn.py (_NodeBlock._build) on explicit buffers."""
     from gnf_amd import _abi
-    from gnf_amd.graphs import csr_of
+    from gnf_amd.graphs import csr_desc, csr_of
     lib = _lib()
     h = xb.d
     mlp = mod._node_block._mlp if hasattr(mod, "_node_block") else mod._mlp
@@ -357,11 +394,11 @@ def _gnn_apply(mod, graph, xb, ob):
     if attn is not None:
         desc.attn = C.pointer(attn)
     spec = blk.spec()
-    csr = csr_of(graph)
+    csr = csr_desc(graph, csr_of(graph), blk.graph_scope)
     n = xb.n
     ws_bytes = lib.gnf_gnn_workspace_bytes(n, h, C.byref(desc), spec.combine)
     ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=DEV)
-    _check(lib.gnf_gnn_apply_f32(C.byref(csr.desc), C.byref(desc), C.byref(spec), xb.ptr(), xb.ld, h, ob.ptr(), ob.ld,
+    _check(lib.gnf_gnn_apply_f32(C.byref(csr), C.byref(desc), C.byref(spec), xb.ptr(), xb.ld, h, ob.ptr(), ob.ld,
                                  _abi.ptr(ws), ws_bytes, _stream()), "gnf_gnn_apply_f32")
     torch.cuda.synchronize()
     xb.check_guard()
@@ -369,7 +406,8 @@ def _gnn_apply(mod, graph, xb, ob):
     return ob.numpy()
 
 
-GNN_APPLY_CASES = ["agg_narrow", "concat_wide", "attention", "attention_layer_norm"]
+GNN_APPLY_CASES = ["agg_narrow", "concat_wide", "attention", "attention_layer_norm", "graph_attn_multihead_ln_I1",
+                   "graph_attn_single_I4_h13"]
 
 
 @pytest.mark.parametrize("case", GNN_APPLY_CASES)
@@ -379,7 +417,7 @@ def test_gnn_apply(layout, case):
     from test_parity_gpu import _hub_graphs
     nn, ne, s, r = _hub_graphs(11)
     n = int(nn.sum())
-    h, od = 12, 7
+    h, od = (13 if case.endswith("_h13") else 12), 7
     x = np.random.default_rng(5).standard_normal((n, h)).astype(np.float32)
     graph = graph_from_arrays(nn, ne, s, r, x, DEV)
     if case in ("agg_narrow", "concat_wide"):
@@ -393,6 +431,22 @@ def test_gnn_apply(layout, case):
                         combine="concat" if case == "concat_wide" else "agg", epsilon=0.5)
         want = o.gnn(x.astype(np.float64), layers)
         tol = 2e-4
+    elif case.startswith("graph_attn"):
+        single = case.endswith("_h13")
+        g = {k: v for k, v in (GATTN_I4 if single else GATTN_I1).items() if k != "scope"}
+        net = R.make_graph_attn_net_params(np.random.default_rng(1), h, 16, 2, **g)
+        net["mlp"] = O.make_mlp_params(np.random.default_rng(2), h + (g["v_dim"] if single else g["out_dim"]), 16, od, 2)
+        if not single:                                                 # (layer norm over the MLP's od outputs)
+            net["attn"].update(ln_gamma=np.linspace(0.5, 1.5, od).astype(np.float32),
+                               ln_beta=np.linspace(-0.3, 0.3, od).astype(np.float32))
+        mk = partial(gnn.make_mlp_model, 16, od, 2, gnn.relu)
+        mod = gnn.self_attn_gnn(g["kq_dim"], g["v_dim"], mk, True) if single else \
+            gnn.multihead_self_attn_gnn(g["kq_dim"], g["v_dim"], g["out_dim"], mk, num_heads=g["num_heads"], layer_norm=True)
+        mod.set_attn_params(net["attn"])
+        mod._mlp.set_params(net["mlp"])
+        o = R.GraphAttnGather(s, r, nn, activation="relu")
+        want = o.attn_gnn(o.to_t(x), o.prep_params({"n": [net]})["n"][0]).numpy()
+        tol = 1e-4
     else:
         ln = case == "attention_layer_norm"
         net = O.make_attn_net_params(np.random.default_rng(1), h, 16, 2, num_heads=4, kq_dim=3, v_dim=2, out_dim=5)
@@ -467,7 +521,7 @@ def _strided_loss_and_grads(tr, graph, src, z):
     """GRevNetTrainer.loss_and_grads / _loss_and_grads (train.py), with the forward pass reading `src`'s window and leaving
     z in `z`'s window, and the backward walk run in place on that window.  The gradient lands in tr.grad; returns sums."""
     from gnf_amd import _abi
-    from gnf_amd.graphs import csr_of
+    from gnf_amd.graphs import csr_desc, csr_of
     lib = _lib()
     net = tr.net
     n, d = z.n, z.d
@@ -487,11 +541,11 @@ def _strided_loss_and_grads(tr, graph, src, z):
     try:
         sums = _flow_call(net, graph, z, _abi.GNF_FORWARD, src)
         flow = net._flow(d // 2, dev)
-        csr, csr_t = csr_of(graph), csr_of(graph, by_sender=True)
+        csr, csr_t = csr_desc(graph, csr_of(graph), net.graph_scope()), csr_of(graph, by_sender=True)
         ws_bytes = lib.gnf_backward_workspace_bytes(n, d, C.byref(flow))
         ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
         aux = torch.cuda.Stream(device=dev) if tr.overlap_weight_grads else None
-        _check(lib.gnf_grevnet_backward_f32(C.byref(csr.desc), C.byref(csr_t.desc), C.byref(flow), C.byref(tr._grad_flow),
+        _check(lib.gnf_grevnet_backward_f32(C.byref(csr), C.byref(csr_t.desc), C.byref(flow), C.byref(tr._grad_flow),
                                             z.ptr(), z.ld, d, _abi.ptr(ws), ws_bytes, _stream(),
                                             C.c_void_p(aux.cuda_stream if aux is not None else 0)),
                "gnf_grevnet_backward_f32")
@@ -539,6 +593,9 @@ BWD_CASES = {
     "attn_stash": (_hp(12, 32, 3, 1, attn=ATTN_RES), "cm", [3, 50, 77], {}, True, True, False),
     "attn_recompute_rows": (_hp(16, 48, 2, 2, attn=ATTN_DEFAULT), "cm", [3, 50, 77], {"attn_kernel": 1}, True, False, False),
     "wide_dw": (_hp(14, 1280, 3, 1), "cm", list(range(24)), {"dw_wide_units": 64}, True, True, False),
+    # graph-scope attention: the front-end reads x at ldx, the dL/dx kernel reads x_cond at xc_ld and adds into g at ldg
+    "graph_attn_multihead_ln_I1": (_ghp(16, 48, 2, 2, GATTN_I1), "cm", [3, 50, 77], {}, True, True, False),
+    "graph_attn_single_I4_h7": (_ghp(14, 48, 2, 1, GATTN_I4), "cm", [3, 50, 77], {}, True, False, False),
 }
 
 
@@ -551,7 +608,11 @@ def _bwd_problem(name):
     n = int(nn.sum())
     rng = np.random.default_rng(sum(map(ord, name)) + 1)
     x = rng.standard_normal((n, d)).astype(np.float32)
-    if "attn" in hp:
+    if _is_graph(hp):
+        x *= 0.3
+        p = _graph_params(d + 1, hp)
+        ref = R.loss_and_grads(nn, s, r, x, p, t, ws, activation="relu")
+    elif "attn" in hp:
         x *= 0.3
         p = O.make_attn_grevnet_params(d + 1, d // 2, hp["latent"], k, t, weight_sharing=ws, final_scale=0.3, **hp["attn"])
         ref = O.loss_and_grads(s, r, n, x, p, t, ws, activation="relu")

@@ -2,7 +2,8 @@
 """Randomised parity sweep on the GPU: random flow hyper-parameters x random batches (ragged graph sizes,
 isolated nodes, duplicated and directed edges) through forward / inverse / gradients, fused and layered / GEMM
 paths, against the float64 oracle.  `python tools/fuzz_parity.py --cases 200 --seed 0`; exits non-zero on the
-first mismatch and prints the failing configuration (re-run it with --only <index>)."""
+first mismatch and prints the failing configuration (re-run it with --only <index>).  --graph draws graph-scope attention
+flows instead (tests/graph_attn_ref.py), from a random stream of their own."""
 import argparse
 import os
 import sys
@@ -314,6 +315,69 @@ def _run_wide_case(idx, seed, verbose=False, big=False):
     return "ok"
 
 
+def random_graph_case(rng):
+    """--graph: a graph-scope attention flow (MultiheadSelfAttention / SelfAttention) at one of the three kernel instances
+    (launch_attn_graph_front: kq, v <= 16 / <= 64 / above; CH = 128, 128, 64 keys per window chunk)"""
+    inst = int(rng.integers(0, 3))
+    wide = (16, 64, 256)[inst]
+    low = (1, 17, 65)[inst]
+    wo = rng.random() < 0.7
+    heads = int(rng.integers(1, max(2, min(8, 256 // wide)) + 1)) if wo else 1
+    big = int(rng.integers(low, wide + 1))
+    other = int(rng.integers(1, wide + 1))
+    kq, v = (big, other) if rng.random() < 0.5 else (other, big)
+    kq, v = min(kq, 256 // heads), min(v, 256 // heads)
+    geom = dict(num_heads=heads, kq_dim=kq, v_dim=v, kq_dim_division=bool(rng.integers(0, 2)))
+    if wo:
+        geom.update(out_dim=int(rng.integers(1, 40)), layer_norm=bool(rng.random() < 0.3))
+    d = int(2 * rng.integers(1, 6))
+    hp = dict(D=d, latent=int(rng.integers(16, 65)), K=int(rng.integers(1, 4)), T=int(rng.integers(1, 4)),
+              weight_sharing=bool(rng.random() < 0.3))
+    ch = 64 if inst == 2 else 128
+    sizes = []
+    for _ in range(int(rng.integers(2, 8))):
+        kind = int(rng.integers(0, 4))   # empty, one node, small, larger than a window chunk
+        sizes.append((0, 1, int(rng.integers(2, 64)), int(rng.integers(ch + 1, 2 * ch + 2)))[kind])
+    if sum(sizes) < 2:
+        sizes.append(int(rng.integers(2, 40)))
+    return geom, hp, sizes, bool(rng.random() < 0.3)
+
+
+def _run_graph_case(idx, seed, verbose=False, perturb=0.0):
+    import graph_attn_ref as R
+    from test_graph_attn_gpu import _batch, _check_flow, _net, _train_check
+    rng = np.random.default_rng([seed, idx, 31])
+    geom, hp, sizes, use_bn = random_graph_case(rng)
+    d, latent, k, t, ws = hp["D"], hp["latent"], hp["K"], hp["T"], hp["weight_sharing"]
+    p = R.make_graph_attn_grevnet_params(idx, d // 2, latent, k, t, weight_sharing=ws, final_scale=0.25, **geom)
+    if use_bn:
+        p["bn"] = O.make_bn_params(idx + 7, d // 2, t)
+    nn, ne, s, r = _batch(sizes, rng)
+    x = (rng.standard_normal((int(nn.sum()), d)) * 0.8).astype(np.float32)
+    if perturb:
+        x = (x + perturb * np.random.default_rng(99).standard_normal(x.shape)).astype(np.float32)
+    desc = f"graph case {idx}: {geom} {hp} bn={use_bn} n_node={sizes}"
+    if verbose:
+        print(desc, flush=True)
+    try:
+        _check_flow(_net(p, d, latent, k, t, ws), nn, ne, s, r, x, p, t, ws, per_graph=True)
+        _train_check(p, nn, ne, s, r, x, d, latent, k, t, ws, per_graph=True)
+    except AssertionError as e:
+        raise AssertionError(f"{desc}\n{e}") from None
+    return "ok"
+
+
+def run_graph_case(idx, seed, verbose=False):
+    """A gradient mismatch is re-tried once on a slightly perturbed input (relu kinks: run_case)."""
+    try:
+        return _run_graph_case(idx, seed, verbose)
+    except AssertionError as e:
+        if "max err" not in str(e):
+            raise
+        res = _run_graph_case(idx, seed, verbose, perturb=1e-3)
+        return "ok (activation-kink coincidence, passes perturbed)" if res == "ok" else res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=100)
@@ -321,6 +385,8 @@ def main():
     ap.add_argument("--only", type=int, default=None)
     ap.add_argument("--wide", action="store_true", help="the layered path's kernels: nets too wide for the fused kernels on batches of thousands of nodes")
     ap.add_argument("--big", action="store_true", help="the fused kernels' large-batch forms: nets they hold on batches of 4 000 - 12 000 nodes")
+    ap.add_argument("--graph", action="store_true", help="graph-scope attention flows: all three kernel instances, empty, "
+                    "one-node and multi-chunk graphs")
     args = ap.parse_args()
     idxs = [args.only] if args.only is not None else range(args.cases)
     counts = {}
@@ -347,7 +413,8 @@ def main():
                 os.environ.pop("FUZZ_PERTURB", None)
         raise AssertionError(first)
     for i in idxs:
-        res = (wide if args.wide or args.big else run_case)(i, args.seed, verbose=args.only is not None or args.wide or args.big)
+        run = run_graph_case if args.graph else wide if args.wide or args.big else run_case
+        res = run(i, args.seed, verbose=args.only is not None or args.wide or args.big)
         counts[res] = counts.get(res, 0) + 1
     print("fuzz parity:", counts)
 
