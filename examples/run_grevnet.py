@@ -118,6 +118,11 @@ def main():
                   f"{torch.cuda.max_memory_allocated(dev) / 2**20:.1f} MiB peak")
             if not np.isfinite(float(v["total_loss"])):
                 raise SystemExit("loss is not finite")
+    # held-out likelihood per GRAPH: one more batch, one forward pass (the moments of the batch-norm bijectors are the batch's)
+    from gnf_amd.flow import log_prob_per_graph
+    nll = -log_prob_per_graph(grevnet, dataset.get_next_batch(F.train_batch_size, dev))["log_prob_xs_per_node"]
+    print(f"per-node NLL over the {nll.shape[0]} graphs of one batch: min {float(nll.min()):.4f} mean {float(nll.mean()):.4f} "
+          f"max {float(nll.max()):.4f}")
     out = sample(grevnet, dataset.get_next_batch(F.train_batch_size, dev))     # run_grevnet.py:304-311
     x = out["grevnet_top_nodes"]
     print("*" * 50)

@@ -124,6 +124,12 @@ def main():
                   f"batch nodes {graph.nodes.shape[0]}")
             if not np.isfinite(float(v["total_loss"])):
                 raise SystemExit("loss is not finite")
+    # held-out likelihood per GRAPH: one more batch, one forward pass (the moments of the batch-norm bijectors are the batch's)
+    from gnf_amd.flow import log_prob_per_graph
+    z, n_node = data.train_batch()
+    nll = -log_prob_per_graph(grevnet, D.transform_example(z, n_node, dev))["log_prob_xs_per_node"]
+    print(f"per-node NLL over the {nll.shape[0]} graphs of one batch: min {float(nll.min()):.4f} mean {float(nll.mean()):.4f} "
+          f"max {float(nll.max()):.4f}")
     # ---- sampling pipeline (train_grevnet_with_data.py:397-416, 526-540) ---------------------------------------
     n_node = np.asarray(random.sample(list(data.n_node) * F.sample_size, F.sample_size), np.int32)
     shell = D.transform_example(np.zeros((int(n_node.sum()), F.node_embedding_dim), np.float32), n_node, dev)

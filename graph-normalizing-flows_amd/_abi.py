@@ -96,6 +96,10 @@ _SIGNATURES = {
                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnf_grevnet_from_f32": (C.c_int, [C.POINTER(GnfCsr), C.POINTER(GnfFlow), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # added within ABI v10: per-graph log-likelihood terms from one batched forward pass
+    "gnf_per_graph_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(GnfFlow)]),
+    "gnf_grevnet_per_graph_f32": (C.c_int, [C.POINTER(GnfCsr), C.POINTER(GnfFlow), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnf_pred_adj_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "gnf_pred_adj_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

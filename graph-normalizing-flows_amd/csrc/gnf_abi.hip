@@ -397,8 +397,13 @@ int gnf_grevnet_f32(const GnfCsr* csr, const GnfFlow* flow, float* x, int64_t ld
     return gnf_grevnet_from_f32(csr, flow, nullptr, 0, x, ld, D, direction, sums, ws, ws_bytes, stream);
 }
 
-int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
-                         int32_t D, int32_t direction, double* sums, void* ws, size_t ws_bytes, gnf_stream_t stream) {
+// The walk over the flow's half-steps behind gnf_grevnet_from_f32 and gnf_grevnet_per_graph_f32.  row_ld (forward only;
+// NULL for the former): 2T slots of n doubles - half-step idx leaves sum_j s[r, j] of every row in slot idx, through the
+// ROWLD instance of whichever kernel runs it; bn_c: 2T doubles, bijector idx's per-node log-det term.  With both NULL the
+// launch sequence is the one it always was.
+static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
+                       int32_t D, int32_t direction, double* sums, void* ws, size_t ws_bytes, gnf_stream_t stream,
+                       double* row_ld, double* bn_c) {
     int rc = validate_flow_call(csr, flow, ld, D, "gnf_grevnet_f32");
     if (rc) return rc;
     if (x_src == x) x_src = nullptr;
@@ -563,6 +568,7 @@ int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_
                     if (split_epoch) hs.split_epoch = split_epoch++;
                     if (mstash) hs.mlp_stash = mstash + (size_t)(2 * i + half) * mstash_slot;
                     const int idx = 2 * i + half;
+                    if (row_ld) hs.row_logdet = row_ld + (size_t)idx * (size_t)n;
                     if (flow->bns && idx == 0) {
                         // decided once, for every half-step of the walk: ALL net pairs must fit the attention instance (a
                         // C-ABI caller's nets may differ from pair to pair when weight_sharing = 0), else the separate passes
@@ -579,7 +585,7 @@ int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_
                     double* const bn_rows_out = partials + (!(idx & 1) && bn_on_load ? p.bn_offset2 : p.bn_offset);
                     if (flow->bns && !bn_on_load) {
                         rc = launch_bn_normalize(flow, &flow->bns[half * T + i], half == 0 ? half0 : half1, ld, n, H,
-                                                 partials + p.bn_offset, bn_slot, st, bn_pre);
+                                                 partials + p.bn_offset, bn_slot, st, bn_pre, bn_c ? bn_c + idx : nullptr);
                         if (rc) return rc;
                         bn_pre = 0;
                     } else if (flow->bns) {
@@ -592,6 +598,7 @@ int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_
                         hs.bnc = &flow->bns[half * T + i];
                         hs.bnc_part = bn_rows_in, hs.bnc_nparts = rows;
                         hs.bnc_logdet = bn_slot;
+                        hs.bnc_c = bn_c ? bn_c + idx : nullptr;
                         hs.bnc_const = consts + (size_t)idx * 2 * H;
                         hs.bnu_const = idx > 0 ? consts + (size_t)(idx - 1) * 2 * H : nullptr;
                         bn_pre = 0;
@@ -661,6 +668,61 @@ int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_
         return launch_finalize(partials, used, gpart, ng, sums, 0, 1, st);
     }
     return GNF_OK;
+}
+
+int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
+                         int32_t D, int32_t direction, double* sums, void* ws, size_t ws_bytes, gnf_stream_t stream) {
+    return grevnet_run(csr, flow, x_src, ld_src, x, ld, D, direction, sums, ws, ws_bytes, stream, nullptr, nullptr);
+}
+
+// workspace of the per-graph entry point: [ gnf_workspace_bytes (256-aligned) | row log-dets [2T][n] fp64 | bijector terms [2T] fp64 ]
+static size_t per_graph_base_bytes(int64_t n_nodes, int32_t D, const GnfFlow* flow) {
+    return (gnf_workspace_bytes(n_nodes, D, flow) + 255) / 256 * 256;
+}
+
+size_t gnf_per_graph_workspace_bytes(int64_t n_nodes, int64_t n_graphs, int32_t D, const GnfFlow* flow) {
+    if (n_nodes < 0 || n_graphs < 0 || D < 2 || !flow || !flow->s_nets) return 0;
+    const size_t slots = 2 * (size_t)(flow->num_timesteps > 0 ? flow->num_timesteps : 1);
+    return per_graph_base_bytes(n_nodes, D, flow) + (slots * (size_t)n_nodes + slots) * sizeof(double);
+}
+
+int gnf_grevnet_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
+                              int32_t D, double* sums, double* graph_out, void* ws, size_t ws_bytes, gnf_stream_t stream) {
+    int rc = validate_flow_call(csr, flow, ld, D, "gnf_grevnet_per_graph_f32");
+    if (rc) return rc;
+    const int64_t n = csr->n_nodes, B = csr->n_graphs;
+    // every GNN family needs the graph boundaries here, not only graph-scope attention
+    if (B < 0 || B >= INT32_MAX || (n > 0 && B < 1) || ((n > 0 || B > 0) && !csr->node_offsets)) {
+        set_error("gnf_grevnet_per_graph_f32: needs GnfCsr.node_offsets (device int32 [n_graphs + 1]) and n_graphs >= 1; got node_offsets=%p n_graphs=%lld", (const void*)csr->node_offsets, (long long)B);
+        return GNF_EINVAL;
+    }
+    if (!sums || (B > 0 && !graph_out)) {
+        set_error("gnf_grevnet_per_graph_f32: null sums / graph_out");
+        return GNF_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {  // nothing to transform: zeros in sums and in every graph's entries (no graphs: no device work at all)
+        if (B > 0) {
+            GNF_HIP_TRY(hipMemsetAsync(sums, 0, 2 * sizeof(double), st));
+            GNF_HIP_TRY(hipMemsetAsync(graph_out, 0, (size_t)B * 2 * sizeof(double), st));
+        }
+        return GNF_OK;
+    }
+    const size_t need = gnf_per_graph_workspace_bytes(n, B, D, flow);
+    if (!ws || ws_bytes < need) {
+        set_error("gnf_grevnet_per_graph_f32: workspace %zu < %zu bytes (gnf_per_graph_workspace_bytes)", ws_bytes, need);
+        return ws ? GNF_EWORKSPACE : GNF_EINVAL;
+    }
+    const int T = flow->num_timesteps;
+    const size_t base = per_graph_base_bytes(n, D, flow);
+    double* row_ld = reinterpret_cast<double*>((char*)ws + base);
+    double* bn_c = row_ld + (size_t)2 * (T > 0 ? T : 1) * (size_t)n;
+    // the inference walk: the training stashes are not written by this entry point
+    GnfFlow fl = *flow;
+    fl.attn_stash = nullptr, fl.attn_stash_bytes = 0, fl.mlp_stash = nullptr, fl.mlp_stash_bytes = 0;
+    rc = grevnet_run(csr, &fl, x_src, ld_src, x, ld, D, GNF_FORWARD, sums, ws, base, stream, row_ld, flow->bns ? bn_c : nullptr);
+    if (rc) return rc;
+    return launch_per_graph(row_ld, 2 * T, n, bn_c, flow->bns ? 2 * T : 0, x, ld, D, csr->node_offsets, B, graph_out, st);
 }
 
 int gnf_gauss_sumsq_f32(const float* z, int64_t n_nodes, int32_t D, int64_t ld, double* out,

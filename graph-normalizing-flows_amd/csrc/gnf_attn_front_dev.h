@@ -104,7 +104,8 @@ static __host__ __device__ inline FrontLds front_lds(const FrontDims& d) {
 // (a branch around every group of four MFMAs otherwise).
 template <bool HOIST, int KQM, int VDM, int EU, bool EXACT, bool TO_LDS, bool FIXED, class Hook>
 __device__ __forceinline__ void attn_front_tile(const FrontArgs& a, float* __restrict__ lds, const int row0, float* h0_lds0,
-                                                float* h0_lds1, const int h0_ls, Hook&& before_out, float* bn_lds = nullptr) {
+                                                float* h0_lds1, const int h0_ls, Hook&& before_out, float* bn_lds = nullptr,
+                                                double* bn_c_out = nullptr) {
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int net = wave >> 2, wn = wave & 3;  // waves 0-3: s-net, 4-7: t-net
@@ -216,6 +217,7 @@ __device__ __forceinline__ void attn_front_tile(const FrontArgs& a, float* __res
                     double tot = 0.0;
                     for (int f = 0; f < H; ++f) tot += red[f];
                     *a.bn_logdet_out = (double)a.n_nodes * tot;
+                    if (bn_c_out) *bn_c_out = tot;  // (the ROWLD instances of the fused kernel only: a constant NULL elsewhere)
                 }
             }
             __syncthreads();

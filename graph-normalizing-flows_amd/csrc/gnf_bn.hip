@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(float* __restrict__ x, int64_t
                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                                   float eps, float* __restrict__ batch_mean,
                                                   float* __restrict__ batch_var, double* __restrict__ logdet_slot,
-                                                  const double* __restrict__ n_moments) {
+                                                  const double* __restrict__ n_moments, double* __restrict__ c_slot) {
     extern __shared__ float ss[];  // scale[H] | shift[H]
     __shared__ double red[256];
     __shared__ double gsum[512];   // [G][H][2] group sums of the partials (G * H <= 256)
@@ -168,7 +168,10 @@ __global__ __launch_bounds__(256) void k_bn_apply(float* __restrict__ x, int64_t
             if (tid < o) red[tid] += red[tid + o];
             __syncthreads();
         }
-        if (tid == 0) *logdet_slot = (double)n * red[0];
+        if (tid == 0) {
+            *logdet_slot = (double)n * red[0];
+            if (c_slot) *c_slot = red[0];  // the per-node term itself (per-graph log-likelihoods: n_g times it)
+        }
     }
     __syncthreads();
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
@@ -217,7 +220,7 @@ int bn_blocks(int64_t n, int64_t* rows_per_block) {
 // pre_parts > 0: `part` already holds that many [H][2] partial rows of sum / sum of squares over x's rows (left by the
 // fused kernel of the half-step that produced x): no moment pass
 int launch_bn_normalize(const GnfFlow* flow, const GnfBatchNorm* bn, float* x, int64_t ld, int64_t n, int32_t H,
-                        double* part, double* logdet_slot, hipStream_t st, int pre_parts) {
+                        double* part, double* logdet_slot, hipStream_t st, int pre_parts, double* c_slot) {
     if (n == 0) return GNF_OK;
     int64_t rpb;
     int blocks = pre_parts > 0 ? pre_parts : bn_blocks(n, &rpb);
@@ -237,7 +240,7 @@ int launch_bn_normalize(const GnfFlow* flow, const GnfBatchNorm* bn, float* x, i
     const int64_t ablocks = (n + arows - 1) / arows;
     hipLaunchKernelGGL(k_bn_apply, dim3((unsigned)ablocks), dim3(256), 2 * H * sizeof(float), st, x, ld, n, H, arows, part,
                        blocks, bn->gamma, bn->beta, bn->epsilon, bn->batch_mean, bn->batch_variance, logdet_slot,
-                       n_moments);
+                       n_moments, c_slot);
     GNF_LAUNCH_CHECK("k_bn_apply");
     return GNF_OK;
 }

@@ -89,6 +89,12 @@ struct HalfStep {
     // inverse pass, the same idea: the bijector behind the PREVIOUS half-step of the walk, applied where this one reads the
     // half it rewrites (moving statistics: no moments to gather), or NULL
     const GnfBatchNorm* bnu_inv = nullptr;
+    // per-graph log-likelihoods (gnf_grevnet_per_graph_f32, forward only): this half-step's slot of the per-row log-det
+    // buffer - row_logdet[r] = sum_j s[r, j] in fp64, n_nodes values, written (not accumulated) by the workgroup that owns
+    // the row.  Not NULL selects the ROWLD instance of whichever epilogue kernel runs the half-step; NULL launches exactly
+    // the instances of a call without it.  bnc_c: with the bijector on load (bnc), where its per-node log-det term c goes.
+    double* row_logdet = nullptr;
+    double* bnc_c = nullptr;
 };
 // may a forward flow with batch-norm bijectors hand them to the half-step kernels this way? (the first half-step decides)
 bool fused_bn_on_load_ok(const HalfStep& hs);
@@ -162,7 +168,7 @@ static constexpr int kBigSplitMax = 128;
 inline size_t big_split_offset(int64_t n_nodes, int in0) { return ((size_t)n_nodes * (size_t)in0 + 63) / 64 * 64; }
 inline size_t big_split_floats() { return (size_t)kBigSplitMax + (size_t)kBigSplitMax * 16 * 128; }
 int big_plan(int64_t n_nodes, int cus, int cap, int32_t* seg_n, int32_t* seg_sz, int32_t* seg_kind = nullptr, int32_t* xg0 = nullptr);  // -> workgroups; runs of (count, row tiles)
-int launch_half_big(FusedArgs& a, int64_t n_nodes, int cap, hipStream_t st, int* n_wg_out);
+int launch_half_big(FusedArgs& a, int64_t n_nodes, int cap, hipStream_t st, int* n_wg_out, double* row_logdet = nullptr);
 // s, t as the last layer's partial products (launch_linear_big_fused): n_slab dense [N, H] slabs `stride` floats apart
 // behind the s / t pointers, + the layer's bias; s_out / t_out (nullable): where the summed rows are also written (the
 // training forward's stash).  n_slab == 0: s, t are the finished rows.
@@ -187,6 +193,10 @@ int launch_gauss_partials(const float* z, int64_t n_nodes, int32_t D, int64_t ld
 // out[0] (+)= sum of a[0..na) ; out[1] = sum of b[0..nb)   (fixed order, fp64, single workgroup)
 int launch_finalize(const double* a, int64_t na, const double* b, int64_t nb, double* out,
                     int accumulate_a, int write_b, hipStream_t st);
+// per-graph reduction behind a forward flow (gnf_per_graph.hip): graph_out[g] = { sum over the graph's rows of the n_slots
+// per-row log-det slots (row_ld[slot * n + r]) + n_g * sum of the n_c bijector terms bn_c[], sum_rows sum_j z[r, j]^2 }
+int launch_per_graph(const double* row_ld, int n_slots, int64_t n, const double* bn_c, int n_c, const float* z, int64_t ld,
+                     int32_t D, const int32_t* node_offsets, int64_t n_graphs, double* graph_out, hipStream_t st);
 int launch_copy_rows(const float* src, int64_t lds_, float* dst, int64_t ldd, int64_t n, int32_t W, hipStream_t st);
 int launch_pack_mlp(const GnfMlp* mlp, float* packed, hipStream_t st);
 int64_t packed_floats(const GnfMlp* mlp);
@@ -274,7 +284,7 @@ int validate_bn(const GnfBatchNorm* bn, int direction, const char* what, int q);
 int bn_sync_exchange(const GnfFlow* flow, const double* part, int nparts, int64_t n, int32_t H, double* local_copy,
                      hipStream_t st);
 int launch_bn_normalize(const GnfFlow* flow, const GnfBatchNorm* bn, float* x, int64_t ld, int64_t n, int32_t H,
-                        double* part, double* logdet_slot, hipStream_t st, int pre_parts = 0);
+                        double* part, double* logdet_slot, hipStream_t st, int pre_parts = 0, double* c_slot = nullptr);
 int launch_bn_denormalize(const GnfBatchNorm* bn, float* z, int64_t ld, int64_t n, int32_t H, hipStream_t st);
 
 // batch-norm bijector, backwards (gnf_bn_bwd.hip).  pre_parts > 0: `part` already holds that many [H][2] partial rows

@@ -120,10 +120,13 @@ namespace gnf {
 // kernel's prologue and leaves the layer-0 input rows of both nets in the activation buffers - no launch boundary, no
 // trip of those rows through global memory.  Its staging area (x rows, q | v of the sender window: 149 KB at the
 // reference's head geometry) ALIASES the activation buffers; bias / reduction scratch / layer table sit behind it.
-template <int MT, int NETS, bool STASH = false, bool FRONT = false, bool FIXED = false>
-__global__ __launch_bounds__(kFusedThreads) void k_half_fused(const FusedArgs a, const FrontArgs fa) {
+// ROWLD (NETS = 2, forward): the coupling epilogue also leaves every row's sum_j s[r, j] in rla.row (per-graph
+// log-likelihoods, gnf_grevnet_per_graph_f32) - instances of their own, so that the plain ones carry none of it.
+template <int MT, int NETS, bool STASH = false, bool FRONT = false, bool FIXED = false, bool ROWLD = false>
+__global__ __launch_bounds__(kFusedThreads) void k_half_fused(const FusedArgs a, const FrontArgs fa, const RowLdArgs rla) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     static_assert(!FRONT || (MT == 1 && NETS == 2), "the attention prologue exists for the 16-row both-nets shape");
+    static_assert(!ROWLD || (NETS == 2 && !STASH), "per-row log-det: the both-nets inference instances (one net per workgroup couples in k_coupling)");
     constexpr int TM = 16 * MT;
     constexpr int WPN = 8 / NETS;  // waves per net
     const int LS = a.LS;
@@ -279,7 +282,7 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused(const FusedArgs a,
         }
         attn_front_tile<true, 10, 10, 4, true, true, FIXED>(fa, smem, row0, buf(0, 0), buf(1, 0), LS,
                                                             [&] { prefetch_chunk(cur, WPN, voff, b_pre, thin_for(cur.layer)); },
-                                                            bn_lds);
+                                                            bn_lds, ROWLD ? rla.bn_c : nullptr);
         if (a.bnu_const) {  // the previous bijector's (scale, shift), for the coupling stage below
             const int HPb = (H + 15) & ~15;
             for (int i = tid; i < 2 * H; i += kFusedThreads) bn_lds[2 * HPb + (i < H ? i : HPb + (i - H))] = a.bnu_const[i];
@@ -474,6 +477,7 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused(const FusedArgs a,
                 a.x_upd[(int64_t)r * a.ld + f] = xn;
                 local += (double)sv;
                 local2 += (double)xn * (double)xn;
+                if constexpr (ROWLD) buf(0, pp)[rl * LS + f] = sv;  // (what the coupling used: a residual block's x_cond is in)
                 if (a.bn_part) xn_lds[rl * LS + f] = xn;
                 if constexpr (STASH) {  // (what the coupling used: a residual block's x_cond is already in)
                     a.stash_st[0][(int64_t)r * H + f] = sv;
@@ -511,6 +515,15 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused(const FusedArgs a,
                 for (int w = 0; w < kFusedThreads / 64; ++w) tot += red[w];
                 a.sq_partials[tile] = tot;
             }
+        }
+        if constexpr (ROWLD) {  // sum_j s[r, j] of the tile's rows: 512 / TM threads per row, fixed order, fp64
+            __syncthreads();
+            constexpr int TPR = kFusedThreads / TM;
+            const int rl = tid / TPR, l = tid % TPR;
+            double acc = 0.0;
+            for (int f = l; f < H; f += TPR) acc += (double)s_lds[rl * LS + f];
+            for (int off = TPR / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, TPR);
+            if (l == 0 && row0 + rl < a.n_nodes) rla.row[row0 + rl] = acc;
         }
     }
 }
@@ -626,13 +639,16 @@ static int choose_big(const HalfStep& hs) {
     return big_q < old_q ? 4 : 0;
 }
 
-template <int MT, int NETS, bool STASH = false, bool FRONT = false, bool FIXED = false>
-static int launch_shape(const FusedArgs& a, unsigned grid, size_t lds, hipStream_t st, const FrontArgs* fa = nullptr) {
-    GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_fused<MT, NETS, STASH, FRONT, FIXED>),
+template <int MT, int NETS, bool STASH = false, bool FRONT = false, bool FIXED = false, bool ROWLD = false>
+static int launch_shape(const FusedArgs& a, unsigned grid, size_t lds, hipStream_t st, const FrontArgs* fa = nullptr,
+                        const RowLdArgs* rla = nullptr) {
+    GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_fused<MT, NETS, STASH, FRONT, FIXED, ROWLD>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit)));
     FrontArgs none;
     memset(&none, 0, sizeof(none));
-    hipLaunchKernelGGL((k_half_fused<MT, NETS, STASH, FRONT, FIXED>), dim3(grid), dim3(kFusedThreads), lds, st, a, fa ? *fa : none);
+    const RowLdArgs no_rows{nullptr, nullptr};
+    hipLaunchKernelGGL((k_half_fused<MT, NETS, STASH, FRONT, FIXED, ROWLD>), dim3(grid), dim3(kFusedThreads), lds, st, a, fa ? *fa : none,
+                       rla ? *rla : no_rows);
     GNF_LAUNCH_CHECK("k_half_fused");
     return GNF_OK;
 }
@@ -776,6 +792,13 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
     FrontArgs fa;
     memset(&fa, 0, sizeof(fa));
     const bool fold = s->attn && MT == 1 && NETS == 2 && !choose_big(hs) && front_fold_ok(hs, &fa);
+    // per-graph log-likelihoods: the same shape choice, the ROWLD instance of it
+    const bool rowld = hs.row_logdet != nullptr;
+    const RowLdArgs rla{hs.row_logdet, hs.bnc_c};
+    if (rowld && (hs.direction != GNF_FORWARD || hs.mlp_stash)) {
+        set_error("internal: per-row log-det on an inverse half-step or beside the MLP-row stash");
+        return GNF_EINVAL;
+    }
     if (hs.bnu_inv) {
         if (!fold || hs.direction != GNF_INVERSE) {
             set_error("internal: batch norm on load (inverse) handed to a half-step that does not run the fused attention instance");
@@ -867,7 +890,7 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
             }
         }
         int n_wg = 0;
-        rc = launch_half_big(a, hs.n_nodes, big, st, &n_wg);
+        rc = launch_half_big(a, hs.n_nodes, big, st, &n_wg, rowld ? hs.row_logdet : nullptr);
         if (rc) return rc;
         *hs.n_partials = (int32_t)n_wg;
         if (hs.n_sq) *hs.n_sq = a.sq_partials ? (int32_t)n_wg : 0;
@@ -896,6 +919,20 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
             rc = launch_shape<1, 2, true, true, true>(a, (unsigned)tiles, fused_front_lds_bytes(s, fa.d), st, &fa);
         else
             rc = launch_shape<1, 2, true>(a, (unsigned)tiles, lds + (size_t)L.mask_words * sizeof(unsigned long long), st);
+        if (rc) return rc;
+        *hs.n_partials = (int32_t)tiles;
+        if (hs.n_sq) *hs.n_sq = a.sq_partials ? (int32_t)tiles : 0;
+        if (hs.n_bn) *hs.n_bn = a.bn_part ? (int32_t)tiles : 0;
+        return GNF_OK;
+    }
+    if (NETS == 2 && rowld) {
+        if (fold && attn_front_fixed_geometry(fa.d))
+            rc = launch_shape<1, 2, false, true, true, true>(a, (unsigned)tiles, fused_front_lds_bytes(s, fa.d), st, &fa, &rla);
+        else if (fold)
+            rc = launch_shape<1, 2, false, true, false, true>(a, (unsigned)tiles, fused_front_lds_bytes(s, fa.d), st, &fa, &rla);
+        else
+            rc = MT == 2 ? launch_shape<2, 2, false, false, false, true>(a, (unsigned)tiles, lds, st, nullptr, &rla)
+                         : launch_shape<1, 2, false, false, false, true>(a, (unsigned)tiles, lds, st, nullptr, &rla);
         if (rc) return rc;
         *hs.n_partials = (int32_t)tiles;
         if (hs.n_sq) *hs.n_sq = a.sq_partials ? (int32_t)tiles : 0;

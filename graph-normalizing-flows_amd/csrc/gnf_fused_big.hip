@@ -289,8 +289,9 @@ __device__ __forceinline__ void big_chunk_thin(float* __restrict__ act, const BC
 }
 
 // SPLIT: the launch has split row tiles (big_seg_kind != 0 somewhere); the plain instance carries none of that code
-template <bool SPLIT>
-__global__ __launch_bounds__(kBigThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_half_big(const FusedArgs a) {
+// ROWLD (forward): the workgroup also leaves sum_j s[r, j] of every row it couples in row_ld (per-graph log-likelihoods)
+template <bool SPLIT, bool ROWLD = false>
+__global__ __launch_bounds__(kBigThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_half_big(const FusedArgs a, double* __restrict__ row_ld) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* act = smem;
     double* red = reinterpret_cast<double*>(act + kBigTM * kBigLS);  // [4] sum(s) | [4] sum(x_new^2)
@@ -638,6 +639,21 @@ __global__ __launch_bounds__(kBigThreads) __attribute__((amdgpu_waves_per_eu(2, 
         a.partials[wg] = tot;
         if (a.sq_partials) a.sq_partials[wg] = tot2;
     }
+    if constexpr (ROWLD) {
+        // the s rows are still in LDS (the coupling only read them): a wave per row, the s the coupling used (+ the residual
+        // row), lanes strided over the features, fixed order, fp64; a split tile's rows by the workgroup that coupled them
+#pragma unroll 1
+        for (int rl = wave; rl < rows_c; rl += kBigWaves) {
+            const int64_t gr = grow(rl);
+            double acc = 0.0;
+            for (int f = lane; f < H; f += 64) {
+                const float xr = a.residual ? a.x_cond[gr * a.ld + f] : 0.f;
+                acc += (double)(act[rl * kBigLS + f] + xr);
+            }
+            for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+            if (lane == 0) row_ld[gr] = lost ? __builtin_nan("") : acc;
+        }
+    }
 }
 
 
@@ -743,7 +759,7 @@ int big_cu_count() {
     return c;
 }
 
-int launch_half_big(FusedArgs& a, int64_t n_nodes, int cap, hipStream_t st, int* n_wg_out) {
+int launch_half_big(FusedArgs& a, int64_t n_nodes, int cap, hipStream_t st, int* n_wg_out, double* row_logdet) {
     const bool split = a.big_split_flag && a.big_split_s && a.big_epoch > 0;
     const int n_wg = big_plan(n_nodes, big_cu_count(), cap, a.big_seg_n, a.big_seg_sz, split ? a.big_seg_kind : nullptr, split ? &a.big_xg0 : nullptr);
     a.n_tiles = n_wg;
@@ -754,10 +770,19 @@ int launch_half_big(FusedArgs& a, int64_t n_nodes, int cap, hipStream_t st, int*
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 84 * 1024)));
     bool any_split = false;
     for (int k = 0; k < 6; ++k) any_split = any_split || (a.big_seg_n[k] > 0 && a.big_seg_kind[k] != 0);
-    if (any_split)
-        hipLaunchKernelGGL(k_half_big<true>, dim3((unsigned)n_wg), dim3(kBigThreads), lds, st, a);
+    if (row_logdet) {
+        GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_big<false, true>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 84 * 1024));
+                            GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_big<true, true>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 84 * 1024)));
+        if (any_split)
+            hipLaunchKernelGGL((k_half_big<true, true>), dim3((unsigned)n_wg), dim3(kBigThreads), lds, st, a, row_logdet);
+        else
+            hipLaunchKernelGGL((k_half_big<false, true>), dim3((unsigned)n_wg), dim3(kBigThreads), lds, st, a, row_logdet);
+    } else if (any_split)
+        hipLaunchKernelGGL(k_half_big<true>, dim3((unsigned)n_wg), dim3(kBigThreads), lds, st, a, (double*)nullptr);
     else
-        hipLaunchKernelGGL(k_half_big<false>, dim3((unsigned)n_wg), dim3(kBigThreads), lds, st, a);
+        hipLaunchKernelGGL(k_half_big<false>, dim3((unsigned)n_wg), dim3(kBigThreads), lds, st, a, (double*)nullptr);
     GNF_LAUNCH_CHECK("k_half_big");
     *n_wg_out = n_wg;
     return GNF_OK;

@@ -78,6 +78,13 @@ struct FusedArgs {
 };
 
 
+// per-graph log-likelihoods: what the ROWLD instances of the forward half-step kernels write beside their usual outputs
+// (a kernel argument of its own behind the others: the plain instances never read it)
+struct RowLdArgs {
+    double* row;   // [n_nodes] this half-step's sum_j s[r, j] per row, fp64
+    double* bn_c;  // attention instance with the bijector on load: its per-node log-det term c, or NULL
+};
+
 // B fragments come through a buffer descriptor: base = this (net, layer)'s packed weights (SGPRs),
 // soffset = wave-uniform byte offset of the 1 KiB fragment block, voffset = lane * 16.  No per-load
 // 64-bit VALU address arithmetic and a single constant address VGPR.

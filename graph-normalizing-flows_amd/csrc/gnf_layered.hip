@@ -273,16 +273,42 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh) {
     return tot;  // valid on thread 0
 }
 
+// ROWLD instances of the two coupling kernels (per-graph log-likelihoods): sum_j s[r, j] of the rows [ra, rb) this workgroup
+// owns, fp64, a wave per row with the lanes strided over the features (fixed order).  s is formed exactly as the coupling
+// loop forms it - bias + the slabs in slab order, + the residual row - from buffers the launch only reads.
+__device__ __forceinline__ void coupling_rows_logdet(const float* __restrict__ s, int64_t lds_, const SlabSrc& sl,
+                                                     const float* __restrict__ xres, int64_t ld, int H, int64_t ra, int64_t rb,
+                                                     double* __restrict__ row_ld) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int64_t r = ra + wave; r < rb; r += 4) {
+        double acc = 0.0;
+        for (int f = lane; f < H; f += 64) {
+            float sv;
+            if (sl.n_slab) {
+                sv = sl.bias_s[f];
+                for (int k = 0; k < sl.n_slab; ++k) sv += s[k * sl.stride + r * lds_ + f];
+            } else {
+                sv = s[r * lds_ + f];
+            }
+            if (xres) sv += xres[r * ld + f];
+            acc += (double)sv;
+        }
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if (lane == 0) row_ld[r] = acc;
+    }
+}
+
 // V4: every row is whole, aligned float4s (H, ld, every pointer): a thread takes four consecutive features of a row per step -
 // a quarter of the loads, index divisions and stores (with the last layer's slabs a scalar element is 2 x n_slab + 2 loads:
 // 9.8 us per half-step on the 2 718 x 100 wide_fc batch)
-template <bool V4>
+template <bool V4, bool ROWLD = false>
 __global__ __launch_bounds__(256) void k_coupling(const float* __restrict__ s,
                                                   const float* __restrict__ t, int64_t lds_,
                                                   float* __restrict__ x_upd, int64_t ld,
                                                   int64_t n_nodes, int H, int inverse,
                                                   double* __restrict__ partials,
-                                                  const float* __restrict__ xres, const SlabSrc sl) {
+                                                  const float* __restrict__ xres, const SlabSrc sl,
+                                                  double* __restrict__ row_ld) {
     typedef float vf __attribute__((ext_vector_type(V4 ? 4 : 1)));
     constexpr int W = V4 ? 4 : 1;
     __shared__ double sh[4];
@@ -324,16 +350,22 @@ __global__ __launch_bounds__(256) void k_coupling(const float* __restrict__ s,
     }
     const double tot = block_sum_256(local, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+    if constexpr (ROWLD) {  // the rows whose first element falls into this workgroup's share
+        const int64_t ra = (beg + Hw - 1) / Hw, rb = end >= total ? n_nodes : (end + Hw - 1) / Hw;
+        coupling_rows_logdet(s, lds_, sl, xres, ld, H, ra, rb, row_ld);
+    }
 }
 
 // The same update for a flow with batch-norm bijectors (forward): the half this launch writes is what the NEXT bijector
 // normalises, so its column sums ride along as one [H][2] fp64 partial row per workgroup (sum x, sum x^2 of the new values,
 // k_bn_stats' arithmetic: fixed order) - a pass over [N, H] of its own took 22.9 us per half-step on the data driver's batch.
 // A workgroup owns `rows` consecutive nodes; thread (rs, c) walks column c of rows rs, rs + lanes, ...  (H <= 256)
+template <bool ROWLD = false>
 __global__ __launch_bounds__(256) void k_coupling_rows(const float* __restrict__ s, const float* __restrict__ t, int64_t lds_,
                                                        float* __restrict__ x_upd, int64_t ld, int64_t n_nodes, int H, int rows,
                                                        double* __restrict__ partials, const float* __restrict__ xres,
-                                                       double* __restrict__ bn_part, const SlabSrc sl) {
+                                                       double* __restrict__ bn_part, const SlabSrc sl,
+                                                       double* __restrict__ row_ld) {
     __shared__ double sh[4];
     __shared__ double cs[2][256];
     const int tid = threadIdx.x;
@@ -390,6 +422,7 @@ __global__ __launch_bounds__(256) void k_coupling_rows(const float* __restrict__
         bn_part[((int64_t)blockIdx.x * H + tid) * 2 + 0] = a0;
         bn_part[((int64_t)blockIdx.x * H + tid) * 2 + 1] = a1;
     }
+    if constexpr (ROWLD) coupling_rows_logdet(s, lds_, sl, xres, ld, H, r0, r1, row_ld);
 }
 
 // Kernel D: per-workgroup fp64 partials of sum(z^2).
@@ -789,12 +822,18 @@ int launch_coupling(const float* sbuf, const float* tbuf, const HalfStep& hs, co
     SlabSrc sl;
     memset(&sl, 0, sizeof(sl));
     if (slabs) sl = *slabs;
+    // per-graph log-likelihoods (forward): the ROWLD instance of whichever of the two kernels the launch takes anyway
+    const bool rowld = hs.row_logdet != nullptr && hs.direction == GNF_FORWARD;
     if (hs.bn_part && hs.n_bn && hs.direction == GNF_FORWARD && H <= 256 && n > 0) {
         // (16 rows per workgroup: (n + 15) / 16 partial rows - the caller sized both partial buffers for exactly that)
         const int rows = 16;
         const int64_t blocks = (n + rows - 1) / rows;
-        hipLaunchKernelGGL(k_coupling_rows, dim3((unsigned)blocks), dim3(256), 0, st, sbuf, tbuf, (int64_t)H, hs.x_upd, hs.ld, n, H,
-                           rows, hs.partials, xres, hs.bn_part, sl);
+        if (rowld)
+            hipLaunchKernelGGL(k_coupling_rows<true>, dim3((unsigned)blocks), dim3(256), 0, st, sbuf, tbuf, (int64_t)H, hs.x_upd, hs.ld, n, H,
+                               rows, hs.partials, xres, hs.bn_part, sl, hs.row_logdet);
+        else
+            hipLaunchKernelGGL(k_coupling_rows<false>, dim3((unsigned)blocks), dim3(256), 0, st, sbuf, tbuf, (int64_t)H, hs.x_upd, hs.ld, n, H,
+                               rows, hs.partials, xres, hs.bn_part, sl, (double*)nullptr);
         GNF_LAUNCH_CHECK("k_coupling_rows");
         *hs.n_partials = (int32_t)blocks;
         *hs.n_bn = (int32_t)blocks;
@@ -808,12 +847,15 @@ int launch_coupling(const float* sbuf, const float* tbuf, const HalfStep& hs, co
                    reinterpret_cast<uintptr_t>(xres) | reinterpret_cast<uintptr_t>(sl.bias_s) | reinterpret_cast<uintptr_t>(sl.bias_t) |
                    reinterpret_cast<uintptr_t>(sl.s_out) | reinterpret_cast<uintptr_t>(sl.t_out);
     const bool v4 = (H & 3) == 0 && (hs.ld & 3) == 0 && (sl.stride & 3) == 0 && (al & 15) == 0;
-    if (v4)
-        hipLaunchKernelGGL(k_coupling<true>, dim3((unsigned)blocks), dim3(256), 0, st, sbuf, tbuf, (int64_t)H,
-                           hs.x_upd, hs.ld, n, H, hs.direction == GNF_INVERSE ? 1 : 0, hs.partials, xres, sl);
-    else
-        hipLaunchKernelGGL(k_coupling<false>, dim3((unsigned)blocks), dim3(256), 0, st, sbuf, tbuf, (int64_t)H,
-                           hs.x_upd, hs.ld, n, H, hs.direction == GNF_INVERSE ? 1 : 0, hs.partials, xres, sl);
+#define GNF_COUPLING(V4_, ROWLD_)                                                                                          \
+    hipLaunchKernelGGL((k_coupling<V4_, ROWLD_>), dim3((unsigned)blocks), dim3(256), 0, st, sbuf, tbuf, (int64_t)H, hs.x_upd, \
+                       hs.ld, n, H, hs.direction == GNF_INVERSE ? 1 : 0, hs.partials, xres, sl, ROWLD_ ? hs.row_logdet : (double*)nullptr)
+    if (rowld) {
+        if (v4) GNF_COUPLING(true, true); else GNF_COUPLING(false, true);
+    } else {
+        if (v4) GNF_COUPLING(true, false); else GNF_COUPLING(false, false);
+    }
+#undef GNF_COUPLING
     GNF_LAUNCH_CHECK("k_coupling");
     *hs.n_partials = (int32_t)blocks;
     return GNF_OK;

@@ -88,6 +88,32 @@ def log_prob_terms(grevnet, graph):
     return out
 
 
+def log_prob_per_graph(grevnet, graph):
+    """log p(G_g) for every graph of the batch from ONE forward pass (GRevNet.f_per_graph).  [B] device fp64 tensors:
+      log_det_jacobian[g], log_prob_zs[g] = -0.5 * sum_{n in g} |z_n|^2 - n_g * D/2 * ln(2 pi), log_prob_xs = their sum,
+      num_nodes[g], log_prob_xs_per_node[g] (an empty graph: 0, not NaN);
+    plus z_graph and, under "batch", the scalars log_prob_terms returns - from the same call.  With batch norm the
+    bijectors use the moments of the whole batch, so the values differ from those of single-graph calls: they are the
+    terms of THIS batch's log-likelihood, and they add up to it."""
+    z_graph, logdet = grevnet.f_per_graph(graph)
+    gs = grevnet.last_graph_sums
+    n, d = z_graph.nodes.shape
+    dev = z_graph.nodes.device
+    num = graph.n_node.to(device=dev, dtype=torch.float64)
+    log_prob_zs = -0.5 * gs[:, 1] - 0.5 * d * LN_2PI * num
+    log_prob_xs = log_prob_zs + logdet
+    sums = grevnet.last_sums
+    b_zs = -0.5 * sums[1] - 0.5 * d * LN_2PI * n
+    b_xs = b_zs + sums[0]
+    nn = float(n)
+    batch = {"log_det_jacobian": sums[0], "log_prob_zs": b_zs, "log_prob_xs": b_xs, "total_loss": -b_xs, "num_nodes": nn,
+             "loss_per_node": -b_xs / nn if n else b_xs * 0.0, "log_prob_xs_per_node": b_xs / nn if n else b_xs * 0.0,
+             "log_prob_zs_per_node": b_zs / nn if n else b_zs * 0.0,
+             "log_det_jacobian_per_node": sums[0] / nn if n else sums[0] * 0.0}
+    return {"z_graph": z_graph, "log_det_jacobian": logdet, "log_prob_zs": log_prob_zs, "log_prob_xs": log_prob_xs,
+            "num_nodes": num, "log_prob_xs_per_node": log_prob_xs / torch.clamp(num, min=1.0), "batch": batch}
+
+
 def sample(grevnet, graph, generator=None):
     """run_grevnet.py:304-311: z ~ N(0, I) of shape [sum(n_node), D]; x = grevnet(graph.replace(nodes=z),
     inverse=False).nodes; also MVN.log_prob(z) per node.  torch.randn is the sampler (SURVEY.md 2b #11)."""

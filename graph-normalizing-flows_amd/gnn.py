@@ -672,6 +672,7 @@ class GRevNet:
         self._cache_fast = None  # (device, hdim, fused, sync world, mutation epoch) the cache was last validated at
         self.fused = True        # False: hide the packed weights -> the layered (generic) kernels run
         self.last_sums = None    # device fp64 [2]: log_det_jacobian, sum(z^2) of the last f()
+        self.last_graph_sums = None   # device fp64 [B, 2]: the same two per graph, of the last f_per_graph()
 
     # ---- parameter plumbing ------------------------------------------------------------------
     def _gnns(self, kind):
@@ -875,6 +876,48 @@ class GRevNet:
         self.last_sums = sums
         self._last_z = z
         return x.replace(nodes=z), sums[0].to(torch.float32)
+
+    def f_per_graph(self, x, sums_out=None):
+        """f with each graph's share of the log-det kept: ONE batched forward pass (gnf_grevnet_per_graph_f32), the same z
+        and the same batch sums as f, bit for bit.  Returns (GraphsTuple with nodes = z, logdet [B] device fp64);
+        `last_graph_sums` holds the [B, 2] buffer (logdet_g, sum z^2 of graph g), `last_sums` what f leaves there.  With
+        batch norm the bijectors' moments are those of the whole batch - what single-graph calls cannot reproduce."""
+        lib = _abi.lib()
+        nodes = x.nodes
+        if nodes.device.type != "cuda":
+            raise _abi.GnfError("GRevNet runs on a HIP device only (no CPU path)")
+        if nodes.ndim != 2 or nodes.shape[1] % 2:
+            raise ValueError(f"nodes must be [N, D] with even D (tf.split, gnn.py:306); got {tuple(nodes.shape)}")
+        n, d = nodes.shape
+        dev = nodes.device
+        b = int(x.n_node.shape[0])
+        src = nodes.to(torch.float32)
+        if n > 0 and (src.stride(1) != 1 or src.stride(0) < d):
+            src = src.contiguous()
+        out = torch.empty((n, d), dtype=torch.float32, device=dev)
+        flow = self._flow(d // 2, dev)
+        if n == 0 and self._bn_sync_world() > 1:
+            raise ValueError("sync_batch_norm: a rank with an empty shard cannot take part in the cross-rank moments "
+                             "(every rank must make the same sequence of all-reduce calls)")
+        csr = csr_desc(x, csr_of(x), True)   # every GNN family: the per-graph reduction reads the graph boundaries
+        with torch.cuda.device(dev):
+            ws_bytes = lib.gnf_per_graph_workspace_bytes(n, b, d, C.byref(flow))
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+        sums = sums_out if sums_out is not None else torch.zeros(2, dtype=torch.float64, device=dev)
+        graph_sums = torch.zeros((b, 2), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _abi.check(lib.gnf_grevnet_per_graph_f32(C.byref(csr), C.byref(flow), _abi.ptr(src), src.stride(0) if n else d,
+                                                     _abi.ptr(out), d, d, _abi.ptr(sums), _abi.ptr(graph_sums), _abi.ptr(ws),
+                                                     ws_bytes, _abi.stream_ptr(dev)), "gnf_grevnet_per_graph_f32")
+        self.last_sums = sums
+        self.last_graph_sums = graph_sums
+        self._last_z = out
+        return x.replace(nodes=out), graph_sums[:, 0]
+
+    def log_prob_per_graph(self, x):
+        """log p(G_g) of every graph of the batch, [B] device fp64, from one forward pass (standard-normal prior)."""
+        from .flow import log_prob_per_graph
+        return log_prob_per_graph(self, x)["log_prob_xs"]
 
     def g(self, z):
         """gnn.py:343-373: latent -> data (sampling direction)."""

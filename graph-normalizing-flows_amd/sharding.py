@@ -80,6 +80,43 @@ def assemble_from_sums(sums):
     }
 
 
+def gather_per_graph(local, shard_ids, group=None):
+    """Per-graph vectors computed on shards, back in batch order.  `local` is this rank's [B_r] (or [B_r, k]) tensor - e.g.
+    an entry of flow.log_prob_per_graph on the rank's shard - whose row j belongs to graph shard_ids[rank][j] of the batch;
+    `shard_ids` is the whole assignment (shard_graph_ids: one sorted id array per rank, known to every rank).  One all-gather
+    of the vectors padded to the largest shard, then the permutation.  Returns the [B] (or [B, k]) tensor on every rank;
+    without an initialised process group (one rank) it is the permutation alone."""
+    sizes = [int(len(ids)) for ids in shard_ids]
+    world = len(sizes)
+    total = sum(sizes)
+    multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    rank = dist.get_rank(group) if multi else 0
+    if (dist.get_world_size(group) if multi else 1) != world:
+        raise ValueError(f"shard_ids has {world} shards but the group has {dist.get_world_size(group) if multi else 1} ranks")
+    if int(local.shape[0]) != sizes[rank]:
+        raise ValueError(f"rank {rank} holds {int(local.shape[0])} graphs, shard_ids says {sizes[rank]}")
+    tail = tuple(local.shape[1:])
+    if multi:
+        width = max(max(sizes), 1)
+        padded = torch.zeros((width,) + tail, dtype=local.dtype, device=local.device)
+        padded[:sizes[rank]] = local
+        parts = [torch.empty_like(padded) for _ in range(world)]
+        if padded.is_cuda and dist.get_backend(group) == "gloo":   # (debugging path, as all_reduce_shard_sums)
+            host = [p.cpu() for p in parts]
+            dist.all_gather(host, padded.cpu(), group=group)
+            parts = [h.to(local.device) for h in host]
+        else:
+            dist.all_gather(parts, padded, group=group)
+        flat = torch.cat([p[:m] for p, m in zip(parts, sizes)])
+    else:
+        flat = local
+    order = torch.as_tensor(np.concatenate([np.asarray(ids, np.int64) for ids in shard_ids]) if total else
+                            np.zeros(0, np.int64), device=local.device)
+    out = torch.empty((total,) + tail, dtype=local.dtype, device=local.device)
+    out[order] = flat
+    return out
+
+
 class RcclComm:
     """An RCCL communicator created by the library itself (gnf_rccl_comm_create, ABI v9) on the CURRENT device: what a
     non-Python host would hand to GnfFlow.bn_allreduce_ctx with bn_allreduce = gnf_rccl_allreduce_sum_f64.

@@ -308,6 +308,30 @@ int gnf_grevnet_f32(const GnfCsr* csr, const GnfFlow* flow, float* x, int64_t ld
 int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
                          int32_t D, int32_t direction, double* sums, void* ws, size_t ws_bytes, gnf_stream_t stream);
 
+/* Added within ABI v10 (new entry points only: no existing signature or struct changed, GNF_ABI_VERSION stays 10).
+ * Per-graph log-likelihood terms from ONE batched forward pass.  GRevNet.f of gnf_grevnet_from_f32(GNF_FORWARD) - same
+ * arguments, same z and the same sums[2], bit for bit - plus, for every graph g of the batch (rows node_offsets[g] ..
+ * node_offsets[g + 1]):
+ *   graph_out[2 g + 0] = log|det| share of graph g = sum over its rows, the 2T half-steps and the features of s, plus - with
+ *                        batch-norm bijectors - n_g * sum_bijectors sum_f (log gamma_f - 0.5 log(var_f + epsilon)); the moments
+ *                        stay those of the WHOLE batch (of all ranks with bn_allreduce), which single-graph calls cannot give
+ *   graph_out[2 g + 1] = sum over its rows and all D features of z^2
+ * both device fp64, written (not accumulated); log p(G_g) = -0.5 * graph_out[2g+1] - 0.5 * D * ln(2 pi) * n_g + graph_out[2g].
+ * The reference has no counterpart (its GRevNet.log_prob, gnn.py:375-377, is never called; its loss needs the batch scalar,
+ * run_grevnet.py:292-302).  Every half-step runs the per-row instance of the kernel the batch size and net widths select
+ * anyway; each row's sum_j s is stored by the one workgroup that owns the row and the per-graph sums are taken in a fixed
+ * order in fp64 - no atomics, two calls give the same bits.
+ * csr->node_offsets / csr->n_graphs are REQUIRED here for every GNN family (GNF_EINVAL without them, before any launch).
+ * Asynchronous on `stream`, no host synchronisation, capturable like gnf_grevnet_f32.  n_nodes == 0: sums and the n_graphs
+ * entries are zeroed (n_graphs == 0 as well: returns before any device work).  A graph with no nodes gets {0, 0}.
+ * GnfFlow.attn_stash / mlp_stash are ignored (not written).  ws: gnf_per_graph_workspace_bytes(n_nodes, n_graphs, D, flow)
+ * bytes - gnf_workspace_bytes plus 2T (n_nodes + 1) doubles (a host computation). */
+size_t gnf_per_graph_workspace_bytes(int64_t n_nodes, int64_t n_graphs, int32_t D, const GnfFlow* flow);
+int gnf_grevnet_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
+                              int32_t D, double* sums /* [2], as gnf_grevnet_from_f32 */,
+                              double* graph_out /* [n_graphs][2]: logdet_g, sum z^2 of graph g */,
+                              void* ws, size_t ws_bytes, gnf_stream_t stream);
+
 /* Kernel D alone: *out = sum_{n,j} z[n,j]^2 in fp64 (device).  log_prob_zs =
  * -0.5 * (*out) - 0.5 * D * ln(2*pi) * N   (tfd.MultivariateNormalDiag(0,1).log_prob summed,
  * run_grevnet.py:292-294; train_grevnet_with_data.py:348-351). ws: gnf_workspace_bytes(...) or
