@@ -149,11 +149,8 @@ WorkspacePlan plan_workspace(int64_t n_nodes, int32_t H, const GnfMlp* net, int3
     p.bn_const_offset = p.bn_offset2 + (size_t)kBnPartRowsMax * (size_t)H * 2;
     size_t pb = (p.bn_const_offset + ((size_t)(n_halfsteps > 0 ? n_halfsteps : 1) * 2 * (size_t)H + 1) / 2) * sizeof(double);
     p.partial_bytes = (pb + 255) / 256 * 256;
-    int lmax = 1;
-    if (net)
-        for (int j = 1; j < net->num_layers; ++j) lmax = lmax > net->dims[j] ? lmax : net->dims[j];
     const int in0 = net ? net->dims[0] : ((combine == GNF_COMBINE_CONCAT) ? 2 * H : H);
-    p.base_floats = (size_t)n_nodes * (size_t)(in0 + kLayeredActBufs * lmax + 2 * H);
+    p.base_floats = half_scratch(n_nodes, in0, hidden_max(net), H).attn_region;
     p.attn_pack_offset = p.base_floats + attn_scratch_floats(net ? net->attn : nullptr, n_nodes, in0);
     p.attn_pack_per_net = net ? (attn_pack_floats(net->attn, H) + 63) / 64 * 64 : 0;
     // (every net of the call: at most 2 per half-step and kind; weight sharing needs fewer)
@@ -168,8 +165,22 @@ static int run_half(const HalfStep& hs, float* scratch, hipStream_t st) {
     return launch_half_layered(hs, scratch, st);
 }
 
-static const GnfMlp* pick(const GnfFlow* f, const GnfMlp* nets, int half, int i) {
-    return f->weight_sharing ? &nets[half] : &nets[half * f->num_timesteps + i];
+// One coupling half-step on `csr`: topology, graph boundaries (graph-scope attention nets), both nets and both column
+// pointers; the caller adds where its partials go and whatever rides along.
+static HalfStep half_step(const GnfCsr* csr, const GnfGnnSpec& gnn, const GnfMlp* s_net, const GnfMlp* t_net, const float* x_cond,
+                          float* x_upd, int64_t ld, int32_t H, int32_t direction) {
+    HalfStep hs;
+    hs.rowptr = csr->rowptr, hs.col = csr->col, hs.n_nodes = csr->n_nodes, hs.n_edges = csr->n_edges;
+    hs.node_offsets = csr->node_offsets, hs.n_graphs = csr->n_graphs;
+    hs.x_cond = x_cond, hs.x_upd = x_upd, hs.ld = ld, hs.H = H;
+    hs.direction = direction, hs.gnn = gnn;
+    hs.s_net = s_net, hs.t_net = t_net;
+    return hs;
+}
+// ... of a flow on x [n, 2 H]: half 0 conditions on columns [0, H) and updates [H, 2 H), half 1 the other way round
+static HalfStep half_step(const GnfCsr* csr, const GnfFlow* flow, float* x, int64_t ld, int32_t H, int32_t direction, int half, int i) {
+    return half_step(csr, flow->gnn, flow_net(flow, flow->s_nets, half, i), flow_net(flow, flow->t_nets, half, i),
+                     x + (half == 0 ? 0 : H), x + (half == 0 ? H : 0), ld, H, direction);
 }
 
 // Argument checks shared by the whole-flow entry points (forward / inverse / backward).
@@ -382,9 +393,8 @@ int gnf_coupling_half_f32(const GnfCsr* csr, const GnfMlp* s_net, const GnfMlp* 
     }
     hipStream_t st = (hipStream_t)stream;
     int32_t nparts = 0;
-    HalfStep hs{csr->rowptr, csr->col, csr->n_nodes, x_cond, x_upd, ld, H, direction, *gnn,
-                s_net, t_net, (double*)ws, &nparts, nullptr, csr->n_edges};
-    hs.node_offsets = csr->node_offsets, hs.n_graphs = csr->n_graphs;
+    HalfStep hs = half_step(csr, *gnn, s_net, t_net, x_cond, x_upd, ld, H, direction);
+    hs.partials = (double*)ws, hs.n_partials = &nparts;
     rc = run_half(hs, (float*)((char*)ws + p.partial_bytes), st);
     if (rc) return rc;
     if (logdet_accum)
@@ -452,10 +462,7 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
     if (x_src && n > 0) {
         if (T > 0 && ld_src == ld && !(direction == GNF_FORWARD && flow->bns)) {
             const int h0_ = direction == GNF_FORWARD ? 0 : 1, i0_ = direction == GNF_FORWARD ? 0 : T - 1;
-            HalfStep probe{csr->rowptr, csr->col, n, x, x, ld, H, direction, flow->gnn,
-                           pick(flow, flow->s_nets, h0_, i0_), pick(flow, flow->t_nets, h0_, i0_), nullptr, nullptr,
-                           nullptr, csr->n_edges};
-            first_oop = fused_supports_oop(probe);
+            first_oop = fused_supports_oop(half_step(csr, flow, x, ld, H, direction, h0_, i0_));
         }
         if (!first_oop) {
             rc = launch_copy_rows(x_src, ld_src, x, ld, n, D, st);
@@ -485,7 +492,6 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
         }
     }
     auto mark_attn = [&](HalfStep& hs, int half, int i) {
-        hs.node_offsets = csr->node_offsets, hs.n_graphs = csr->n_graphs;   // (graph-scope attention nets)
         if (!attn_pack) return;
         const int q = flow->weight_sharing ? half : half * T + i;
         hs.attn_packed[0] = attn_pack + (size_t)q * p.attn_pack_per_net;
@@ -496,11 +502,9 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
     // flags are zeroed once per call, every half-step launch gets a value of its own
     int32_t split_epoch = 0;
     if (n_nets > 0 && !flow->s_nets[0].attn && n > (int64_t)32 * big_cu_count()) {
-        const int in0_ = flow->s_nets[0].dims[0];
-        int lmax_ = 1;
-        for (int j = 1; j < flow->s_nets[0].num_layers; ++j) lmax_ = lmax_ > flow->s_nets[0].dims[j] ? lmax_ : flow->s_nets[0].dims[j];
-        if (big_split_offset(n, in0_) + big_split_floats() <= (size_t)n * (size_t)(in0_ + kLayeredActBufs * lmax_ + 2 * H)) {
-            GNF_HIP_TRY(hipMemsetAsync(scratch + big_split_offset(n, in0_), 0, kBigSplitMax * sizeof(int), st));
+        const HalfScratch hsl = half_scratch(n, flow->s_nets[0].dims[0], hidden_max(&flow->s_nets[0]), H);
+        if (hsl.split_fits()) {
+            GNF_HIP_TRY(hipMemsetAsync(scratch + hsl.split_flags, 0, kBigSplitMax * sizeof(int), st));
             split_epoch = 1;
         }
     }
@@ -558,11 +562,9 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
                     double* bn_slot = nullptr;
                     if (flow->bns) bn_slot = partials + used, used += 1;
                     int32_t np_ = 0;
-                    HalfStep hs{csr->rowptr, csr->col, n, half == 0 ? half0 : half1,
-                                half == 0 ? half1 : half0, ld, H, GNF_FORWARD, flow->gnn,
-                                pick(flow, flow->s_nets, half, i), pick(flow, flow->t_nets, half, i),
-                                partials + used, &np_,
-                                stash ? stash + (size_t)(2 * i + half) * stash_slot : nullptr, csr->n_edges};
+                    HalfStep hs = half_step(csr, flow, x, ld, H, GNF_FORWARD, half, i);
+                    hs.partials = partials + used, hs.n_partials = &np_;
+                    if (stash) hs.attn_region = stash + (size_t)(2 * i + half) * stash_slot;
                     mark_first(hs, half);
                     mark_attn(hs, half, i);
                     if (split_epoch) hs.split_epoch = split_epoch++;
@@ -576,7 +578,7 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
                         for (int i2 = 0; i2 < T && bn_on_load; ++i2)
                             for (int h2 = 0; h2 < 2 && bn_on_load; ++h2) {
                                 HalfStep probe = hs;
-                                probe.s_net = pick(flow, flow->s_nets, h2, i2), probe.t_net = pick(flow, flow->t_nets, h2, i2);
+                                probe.s_net = flow_net(flow, flow->s_nets, h2, i2), probe.t_net = flow_net(flow, flow->t_nets, h2, i2);
                                 mark_attn(probe, h2, i2);
                                 bn_on_load = fused_bn_on_load_ok(probe);
                             }
@@ -625,10 +627,8 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
             for (int i = T - 1; i >= 0; --i) {  // gnn.py:347-372
                 for (int half = 1; half >= 0; --half) {
                     int32_t np_ = 0;
-                    HalfStep hs{csr->rowptr, csr->col, n, half == 0 ? half0 : half1,
-                                half == 0 ? half1 : half0, ld, H, GNF_INVERSE, flow->gnn,
-                                pick(flow, flow->s_nets, half, i), pick(flow, flow->t_nets, half, i),
-                                partials + used, &np_, nullptr, csr->n_edges};
+                    HalfStep hs = half_step(csr, flow, x, ld, H, GNF_INVERSE, half, i);
+                    hs.partials = partials + used, hs.n_partials = &np_;
                     mark_first(hs, half);
                     mark_attn(hs, half, i);
                     if (split_epoch) hs.split_epoch = split_epoch++;

@@ -598,13 +598,6 @@ __global__ __launch_bounds__(512) void k_attn_fwd_rows(const AttnArgs a, int win
     }
 }
 
-size_t attn_scratch_floats(const GnfAttn* at, int64_t n_nodes, int32_t in0) {
-    if (!at) return 0;
-    const size_t P = (size_t)attn_qkv_width(at);
-    // [2][n][P] q|k|v, [2][n][in0] h0, [2][n][heads*v] attended values, [2][n][3*heads] softmax statistics
-    return 2 * (size_t)n_nodes * (P + (size_t)in0 + (size_t)at->num_heads * at->v_dim + 3 * (size_t)at->num_heads);
-}
-
 size_t attn_stash_slot_floats(const GnfFlow* flow, int64_t n_nodes) {
     const GnfMlp* net = flow && flow->s_nets ? &flow->s_nets[0] : nullptr;
     if (!net || !net->attn || n_nodes <= 0) return 0;
@@ -627,11 +620,12 @@ int launch_attn_front(const int32_t* rowptr, const int32_t* col, int64_t n, cons
             return GNF_ESHAPE;
         }
     AttnArgs a;
-    const size_t P = 2 * (size_t)a0->num_heads * a0->kq_dim + a0->v_dim;
+    const size_t P = (size_t)attn_qkv_width(a0);
+    const AttnRegion R = attn_region(a0, n, in0);   // (one net: its q | k | v and attended values at the region's [0] places)
     // sparse batches (mean in-degree under ~24: the config-2 batch has 12): ONE launch, projections on the matrix
     // cores per tile (gnf_attn_front.hip); dense batches (complete graphs) keep the per-node projection below
     if (packed && packed[0] && n_edges > 0 && n_edges < 24 * n && attn_front_fused_ok(a0, H)) {
-        float* qkv_ptr[2] = {scratch, scratch + (size_t)(nets > 1 ? 1 : 0) * n * P};
+        float* qkv_ptr[2] = {scratch + R.qkv[0], scratch + R.qkv[nets > 1 ? 1 : 0]};
         return launch_attn_front_fused(rowptr, col, n, x, ldx, H, at, nets, in0, packed, need_qkv ? qkv_ptr : nullptr,
                                        h0_out, st, agg_out, mz_out);
     }
@@ -641,7 +635,7 @@ int launch_attn_front(const int32_t* rowptr, const int32_t* col, int64_t n, cons
         a.Wk[q] = t->Wk;
         a.Wv[q] = t->Wv;
         a.Wo[q] = t->Wo;
-        a.qkv[q] = scratch + (size_t)q * n * P;
+        a.qkv[q] = scratch + R.qkv[q];
         a.h0[q] = h0_out[q < nets ? q : 0];
         a.agg_out[q] = agg_out ? agg_out[q < nets ? q : 0] : nullptr;
         a.mz_out[q] = mz_out ? mz_out[q < nets ? q : 0] : nullptr;
@@ -739,8 +733,7 @@ int launch_attn_front(const int32_t* rowptr, const int32_t* col, int64_t n, cons
                 }
             }
             const int NV = a.nh * a.v;
-            float* agg_def = scratch + 2 * (size_t)n * (P + (size_t)in0);   // attn_scratch_floats' layout
-            float* aggs[2] = {a.agg_out[0] ? a.agg_out[0] : agg_def, a.agg_out[1] ? a.agg_out[1] : agg_def + (size_t)(nets > 1 ? 1 : 0) * n * NV};
+            float* aggs[2] = {a.agg_out[0] ? a.agg_out[0] : scratch + R.agg[0], a.agg_out[1] ? a.agg_out[1] : scratch + R.agg[nets > 1 ? 1 : 0]};
             const float* qk[2] = {a.qkv[0], a.qkv[1]};
             float* mzs[2] = {a.mz_out[0], a.mz_out[1]};
             int rc = launch_attn_core(a0, nets, rowptr, col, n, x, ldx, H, in0, qk, aggs, mzs, a.h0, st);

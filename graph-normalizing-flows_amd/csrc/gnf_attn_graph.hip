@@ -153,19 +153,18 @@ int launch_attn_graph_front(const GnfAttn* const* at, int nets, int64_t n, const
         return GNF_EINVAL;
     }
     const int nh = a0->num_heads, kq = a0->kq_dim, vd = a0->v_dim, NV = nh * vd;
-    const size_t P = (size_t)attn_qkv_width(a0);
-    float* qkv[2] = {scratch, scratch + (size_t)(nets > 1 ? 1 : 0) * n * P};
+    const AttnRegion R = attn_region(a0, n, in0);
+    float* qkv[2] = {scratch + R.qkv[0], scratch + R.qkv[nets > 1 ? 1 : 0]};
     float* h0[2] = {h0_out[0], h0_out[nets > 1 ? 1 : 0]};
     // q | k | v (per-head values: Wv is [H, heads v]) and h0[:, :H) = x
     int rc = launch_attn_proj_mfma(at, nets, n, x, ldx, H, qkv, st, h0, in0, NV);
     if (rc) return rc;
     GraphAttnFwdArgs a;
     const bool project = a0->Wo != nullptr;
-    float* agg_def = scratch + 2 * (size_t)n * (P + (size_t)in0);   // attn_scratch_floats' layout
     for (int q = 0; q < 2; ++q) {
         const int s = q < nets ? q : 0;
         a.qkv[q] = qkv[s];
-        a.agg[q] = !project ? h0[s] + H : (agg_out ? agg_out[s] : agg_def + (size_t)s * n * NV);
+        a.agg[q] = !project ? h0[s] + H : (agg_out ? agg_out[s] : scratch + R.agg[s]);
         a.mz[q] = mz_out ? mz_out[s] : nullptr;
     }
     a.agg_ld = project ? NV : in0;

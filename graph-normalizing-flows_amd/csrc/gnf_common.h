@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "gnf.h"
+#include "gnf_layout.h"
 #include "gnf_options.h"
 
 namespace gnf {
@@ -32,22 +33,22 @@ void set_error(const char* fmt, ...);
 // Everything one coupling half-step needs, resolved to raw pointers (host struct, passed by value
 // to the launchers).
 struct HalfStep {
-    const int32_t* rowptr;
-    const int32_t* col;
-    int64_t n_nodes;
-    const float* x_cond;  // first column of the conditioning half
-    float* x_upd;         // first column of the half being updated
-    int64_t ld;
-    int32_t H;
-    int32_t direction;
-    GnfGnnSpec gnn;
-    const GnfMlp* s_net;  // host
-    const GnfMlp* t_net;  // host
-    double* partials;     // device: one fp64 partial sum(s) per workgroup of the epilogue kernel
-    int32_t* n_partials;  // host out: how many partials this launch writes
-    float* attn_region;   // NULL: the attention front-end works in the scratch; else q | k | v and h0 of both nets go
-                          // here (a slot of GnfFlow.attn_stash) and stay for the backward pass
-    int64_t n_edges;      // 0: unknown (only used to pick between kernel generations by mean degree)
+    const int32_t* rowptr = nullptr;
+    const int32_t* col = nullptr;
+    int64_t n_nodes = 0;
+    const float* x_cond = nullptr;  // first column of the conditioning half
+    float* x_upd = nullptr;         // first column of the half being updated
+    int64_t ld = 0;
+    int32_t H = 0;
+    int32_t direction = GNF_FORWARD;
+    GnfGnnSpec gnn = {};
+    const GnfMlp* s_net = nullptr;  // host
+    const GnfMlp* t_net = nullptr;  // host
+    double* partials = nullptr;     // device: one fp64 partial sum(s) per workgroup of the epilogue kernel
+    int32_t* n_partials = nullptr;  // host out: how many partials this launch writes
+    float* attn_region = nullptr;   // NULL: the attention front-end works in the scratch; else q | k | v and h0 of both nets go
+                                    // here (a slot of GnfFlow.attn_stash: AttnRegion) and stay for the backward pass
+    int64_t n_edges = 0;            // 0: unknown (only used to pick between kernel generations by mean degree)
     // out-of-place first half-step of a flow (the caller's functional x -> z without a separate copy pass): when
     // x_src != NULL the conditioning half is read from x_src + cond_off, the old value of the updated half from
     // x_src + upd_off (same leading dimension ld), and the launch also copies its rows of the conditioning half into
@@ -62,7 +63,7 @@ struct HalfStep {
     // graph-scope attention nets (GnfAttn.scope == GNF_ATTN_GRAPH): GnfCsr.node_offsets / n_graphs of the batch
     const int32_t* node_offsets = nullptr;
     int64_t n_graphs = 0;
-    // large-batch kernel, split row tiles (gnf_fused_big.hip): > 0 = the caller zeroed big_split_flags(scratch, ...) at the
+    // large-batch kernel, split row tiles (gnf_fused_big.hip): > 0 = the caller zeroed HalfScratch.split_flags at the
     // start of its call and hands every half-step launch a value of its own (1, 2, ...); 0 = no split tiles
     int32_t split_epoch = 0;
     // training forward: this half-step's slot of GnfFlow.mlp_stash (mlp_stash_layout), or NULL
@@ -103,13 +104,7 @@ int launch_bn_affine(float* x, int64_t ld, int64_t n, int32_t H, const float* sc
 // partial rows (sum x, sum x^2 per feature, fp64) of x[:, :H] - the first bijector's moments; returns the row count
 int launch_bn_stats(const float* x, int64_t ld, int64_t n, int32_t H, double* part, hipStream_t st, int* rows_out);
 
-// MLP-row stash (GnfFlow.mlp_stash, ABI v8): the rows of a half-step the backward walk would otherwise recompute
-struct MlpStashLayout {
-    size_t h0, act, act_each, st, st_each, mask, slot;  // float offsets inside a slot / floats per slot
-    int ld_act;                                   // row pitch of the hidden activations (widest hidden layer)
-    int mld, mask_words;                          // act' ballot words: 16-column tiles per mask row, 64-bit words per 16-node tile
-};
-MlpStashLayout mlp_stash_layout(const GnfMlp* net, int64_t n, int32_t H);
+// MLP-row stash (GnfFlow.mlp_stash, ABI v8; MlpStashLayout): when a flow's half-steps fill it
 bool fused_stash_shape(const GnfMlp* s, const GnfMlp* t, int64_t n);   // forward side (gnf_fused.hip)
 // both sides: message-passing nets on the fused forward kernel's (1,2) shape AND the merged backward launch
 bool mlp_stash_supported(const GnfFlow* flow, int64_t n, int32_t H);   // gnf_train.hip
@@ -117,8 +112,7 @@ bool mlp_stash_supported(const GnfFlow* flow, int64_t n, int32_t H);   // gnf_tr
 // layer outputs and s, t go straight into the slot, the backward skips its recompute of both MLPs
 bool layered_stash_mode(const GnfFlow* flow, int64_t n, int32_t H);
 bool fused_supports_oop(const HalfStep& hs);
-// floats of one half-step's slot in GnfFlow.attn_stash ( = attn_scratch_floats: [2][n][P] q|k|v, [2][n][in0] h0,
-// [2][n][heads*v] attended values, [2][n][3*heads] softmax statistics)
+// floats of one half-step's slot in GnfFlow.attn_stash (AttnRegion.total; 0: this flow keeps none)
 size_t attn_stash_slot_floats(const GnfFlow* flow, int64_t n_nodes);
 
 // ---- layout of the caller-provided workspace --------------------------------------------------
@@ -132,9 +126,6 @@ inline int64_t coupling_blocks_max(int64_t n_nodes) { return (n_nodes + 15) / 16
 // per half-step: the coupling partials + one slot for the batch-norm log-det term
 inline int64_t partials_per_halfstep(int64_t n_nodes) { return coupling_blocks_max(n_nodes) + 1; }
 
-// layered path: ping-pong activation buffers per net x two nets side by side (grouped GEMM launches)
-static constexpr int kLayeredActBufs = 4;
-
 struct WorkspacePlan {
     int64_t partial_stride;  // doubles per half-step
     int64_t n_halfsteps;
@@ -146,7 +137,7 @@ struct WorkspacePlan {
     size_t attn_pack_per_net;
     size_t attn_tile_offset; // floats: [tiles][2] ints, the attention front-end's per-tile sender windows (behind the packed weights)
     size_t scratch_floats;   // layered path activations (+ attention front-end region at its end)
-    size_t base_floats;      // offset of the attention region inside the scratch
+    size_t base_floats;      // offset of the attention region inside the scratch (HalfScratch.attn_region)
     size_t total_bytes;
 };
 WorkspacePlan plan_workspace(int64_t n_nodes, int32_t H, const GnfMlp* net, int32_t combine,
@@ -162,11 +153,6 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st);
 struct FusedArgs;
 bool big_supported(const GnfMlp* s, int32_t H);
 int big_cu_count();  // multiProcessorCount of the current device (cached per device)
-// split row tiles of the large-batch kernel: [kBigSplitMax flags | kBigSplitMax x 16 x 128 floats of s rows] behind the layer-0
-// rows at the head of the half-step scratch (message-passing nets; room = the layered path's activation buffers)
-static constexpr int kBigSplitMax = 128;
-inline size_t big_split_offset(int64_t n_nodes, int in0) { return ((size_t)n_nodes * (size_t)in0 + 63) / 64 * 64; }
-inline size_t big_split_floats() { return (size_t)kBigSplitMax + (size_t)kBigSplitMax * 16 * 128; }
 int big_plan(int64_t n_nodes, int cus, int cap, int32_t* seg_n, int32_t* seg_sz, int32_t* seg_kind = nullptr, int32_t* xg0 = nullptr);  // -> workgroups; runs of (count, row tiles)
 int launch_half_big(FusedArgs& a, int64_t n_nodes, int cap, hipStream_t st, int* n_wg_out, double* row_logdet = nullptr);
 // s, t as the last layer's partial products (launch_linear_big_fused): n_slab dense [N, H] slabs `stride` floats apart
@@ -307,14 +293,10 @@ inline bool attn_geometry_ok(int heads, int kq, int v, int H) {
 }
 int validate_attn(const GnfAttn* at, const GnfMlp* mlp, int32_t H, const char* what);
 // graph-scope attention (GnfAttn.scope == GNF_ATTN_GRAPH; include/gnf.h): its own limit (no row-width clause: its kernels
-// hold any H) and its own q | k | v row, 2 heads kq + heads v (the edge scope's is 2 heads kq + v)
-inline bool attn_is_graph(const GnfAttn* at) { return at && at->scope == GNF_ATTN_GRAPH; }
+// hold any H)
 inline bool attn_graph_geometry_ok(int heads, int kq, int v) {
     return heads >= 1 && heads <= kAttnMaxHeads && kq >= 1 && v >= 1 && (int64_t)heads * kq <= kAttnMaxWidth &&
            (int64_t)heads * v <= kAttnMaxWidth;
-}
-inline int64_t attn_qkv_width(const GnfAttn* at) {
-    return 2 * (int64_t)at->num_heads * at->kq_dim + (attn_is_graph(at) ? (int64_t)at->num_heads : 1) * at->v_dim;
 }
 // graph-scope front-end (gnf_attn_graph.hip): q | k | v of net q at scratch + q n P, h0[q] = [x || new]; agg_out / mz_out as
 // launch_attn_front's (a block without Wo leaves its attended values in h0[q][:, H:) whatever agg_out says)
@@ -328,15 +310,15 @@ int launch_attn_graph_backward(const GnfAttn* const* at, int64_t n, int32_t H, i
                                const float* const* agg, int64_t agg_ld, float* const* stats, float* const* dqkv,
                                const float* const* dh0, float* g_cond, int64_t ldg, const float* xc_src, int64_t xc_ld,
                                float* xc_dst, hipStream_t st);
-size_t attn_scratch_floats(const GnfAttn* at, int64_t n_nodes, int32_t in0);
+inline size_t attn_scratch_floats(const GnfAttn* at, int64_t n_nodes, int32_t in0) { return attn_region(at, n_nodes, in0).total; }
 // need_qkv: the caller reads the per-node q | k | v block of `scratch` afterwards (backward pass, attention stash)
 int launch_attn_front(const int32_t* rowptr, const int32_t* col, int64_t n, const float* x, int64_t ldx,
                       int32_t H, const GnfAttn* const* at, int nets, int32_t in0, float* scratch,
                       float* const* h0_out, hipStream_t st, int64_t n_edges = 0, bool need_qkv = true,
                       const float* const* packed = nullptr, float* const* agg_out = nullptr, float* const* mz_out = nullptr);
-// Scratch contract: q | k | v of net q at scratch + q n P.  With agg_out == NULL the kernels that need the attended values
-// in memory (gnf_attn_core.hip) put them at scratch + 2 n (P + in0) - attn_scratch_floats' layout, which every caller that
-// passes NULL provides (plan_workspace); a caller that passes only the q | k | v block (the backward recompute) passes agg_out.
+// Scratch contract: `scratch` is an AttnRegion, of which q | k | v is always used.  With agg_out == NULL the kernels that need
+// the attended values in memory (gnf_attn_core.hip) use its agg block, which every caller that passes NULL provides
+// (plan_workspace); a caller that passes only the q | k | v block (the backward recompute) passes agg_out.
 // agg_out / mz_out (training): per net [N, heads*v] attended values and [N, 3*heads] softmax statistics (running max at [h],
 // denominator at [heads + h]; the third block is scratch of the backward pass), kept for launch_attn_backward
 // matrix-core attention core for wide heads (gnf_attn_core.hip): qkv[q] -> agg[q] ([N, heads v], normalised), mz[q]

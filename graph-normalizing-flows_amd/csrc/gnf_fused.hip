@@ -658,8 +658,7 @@ bool fused_bn_on_load_ok(const HalfStep& hs) {
     if (!hs.s_net->attn || hs.H > 128 || !fused_supported(hs)) return false;
     int MT, NETS;
     choose_shape(hs, &MT, &NETS);
-    FrontArgs fa;
-    memset(&fa, 0, sizeof(fa));
+    FrontArgs fa{};
     return MT == 1 && NETS == 2 && !choose_big(hs) && front_fold_ok(hs, &fa);
 }
 
@@ -696,21 +695,16 @@ static bool front_fold_ok(const HalfStep& hs, FrontArgs* fa) {
         const size_t act_bytes = (size_t)2 * 2 * 16 * (max_padded_width(s) + 4) * sizeof(float);
         if (!attn_front_fixed_geometry(d) || act_bytes + (size_t)SL.mask_words * 8 > (size_t)front_lds(d).total * sizeof(float)) return false;
     }
+    // training forward (r != NULL): q | k | v, h0, the attended values and the softmax statistics stay in the half-step's slot
+    // of GnfFlow.attn_stash
+    const AttnRegion R = attn_region(a0, hs.n_nodes, in0);
+    float* const r = hs.attn_region;
     for (int q = 0; q < 2; ++q) {
         fa->packed[q] = hs.attn_packed[q];
-        fa->qkv[q] = nullptr;
-        fa->h0[q] = nullptr;
-        fa->agg_out[q] = nullptr;
-        fa->mz_out[q] = nullptr;
-    }
-    if (hs.attn_region) {  // training forward: q | k | v, h0, the attended values and the softmax statistics stay in the
-                           // half-step's slot of GnfFlow.attn_stash (attn_scratch_floats' layout, as launch_attn_pair)
-        const size_t n = (size_t)hs.n_nodes, P = 2 * (size_t)a0->num_heads * a0->kq_dim + a0->v_dim, NV = (size_t)a0->num_heads * a0->v_dim;
-        float* r = hs.attn_region;
-        fa->qkv[0] = r, fa->qkv[1] = r + n * P;
-        fa->h0[0] = r + 2 * n * P, fa->h0[1] = fa->h0[0] + n * in0;
-        fa->agg_out[0] = fa->h0[1] + n * in0, fa->agg_out[1] = fa->agg_out[0] + n * NV;
-        fa->mz_out[0] = fa->agg_out[1] + n * NV, fa->mz_out[1] = fa->mz_out[0] + n * 3 * a0->num_heads;
+        fa->qkv[q] = r ? r + R.qkv[q] : nullptr;
+        fa->h0[q] = r ? r + R.h0[q] : nullptr;
+        fa->agg_out[q] = r ? r + R.agg[q] : nullptr;
+        fa->mz_out[q] = r ? r + R.stats[q] : nullptr;
     }
     fa->rowptr = hs.rowptr, fa->col = hs.col, fa->x = hs.x_cond, fa->ldx = hs.ld;
     fa->tiles = hs.attn_tiles;
@@ -726,19 +720,18 @@ static bool front_fold_ok(const HalfStep& hs, FrontArgs* fa) {
 MlpStashLayout mlp_stash_layout(const GnfMlp* net, int64_t n, int32_t H) {
     auto al = [](size_t v) { return (v + 63) / 64 * 64; };
     MlpStashLayout L;
-    const int K = net->num_layers;
-    int lmax = 1;
-    for (int j = 1; j < K; ++j) lmax = lmax > net->dims[j] ? lmax : net->dims[j];
+    const int K = net->num_layers, lmax = hidden_max(net);
     L.ld_act = lmax;
+    L.hidden = K > 1 ? K - 1 : 0;
     size_t off = 0;
     L.h0 = off, off += al((size_t)n * net->dims[0]);
     L.act_each = al((size_t)n * lmax);
-    L.act = off, off += 2 * (size_t)(K > 1 ? K - 1 : 0) * L.act_each;
+    L.act = off, off += 2 * (size_t)L.hidden * L.act_each;
     L.st_each = al((size_t)n * H);
     L.st = off, off += 2 * L.st_each;
     L.mld = 1;
     for (int j = 1; j < K; ++j) L.mld = L.mld > pad16(net->dims[j]) / 16 ? L.mld : pad16(net->dims[j]) / 16;
-    L.mask_words = 2 * (K > 1 ? K - 1 : 0) * 4 * L.mld;
+    L.mask_words = 2 * L.hidden * 4 * L.mld;
     L.mask = off, off += al((size_t)((n + 15) / 16) * L.mask_words * 2);
     L.slot = off;
     return L;
@@ -754,21 +747,28 @@ bool fused_stash_shape(const GnfMlp* s, const GnfMlp* t, int64_t n) {
     return (n + 15) / 16 <= big_cu_count() && fused_lds_bytes(s, 1, 2) <= (size_t)kLdsLimit;
 }
 
+// the both-nets instance for this launch: plain, the attention front-end folded in (any geometry / the fixed one), or
+// two row tiles per workgroup - each as it is, or (ROWLD) leaving the per-row log-dets as well
+template <bool ROWLD>
+static int launch_nets2(const FusedArgs& a, int MT, bool fold, const FrontArgs& fa, const RowLdArgs* rla, unsigned tiles, size_t lds,
+                        size_t front_lds, hipStream_t st) {
+    if (fold && attn_front_fixed_geometry(fa.d)) return launch_shape<1, 2, false, true, true, ROWLD>(a, tiles, front_lds, st, &fa, rla);
+    if (fold) return launch_shape<1, 2, false, true, false, ROWLD>(a, tiles, front_lds, st, &fa, rla);
+    return MT == 2 ? launch_shape<2, 2, false, false, false, ROWLD>(a, tiles, lds, st, nullptr, rla)
+                   : launch_shape<1, 2, false, false, false, ROWLD>(a, tiles, lds, st, nullptr, rla);
+}
+
 int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
     const GnfMlp *s = hs.s_net, *t = hs.t_net;
     *hs.n_partials = 0;
     if (hs.n_nodes == 0) return GNF_OK;
     int MT, NETS;
     choose_shape(hs, &MT, &NETS);
-    FusedArgs a;
+    FusedArgs a{};
     a.rowptr = hs.rowptr;
     a.col = hs.col;
     a.x_cond = hs.x_cond;
     a.x_upd = hs.x_upd;
-    memset(a.big_seg_n, 0, sizeof(a.big_seg_n));
-    memset(a.big_seg_sz, 0, sizeof(a.big_seg_sz));
-    memset(a.big_seg_kind, 0, sizeof(a.big_seg_kind));
-    a.big_xg0 = 0, a.big_epoch = 0, a.big_epoch_set = 0, a.big_split_s = nullptr, a.big_split_flag = nullptr;
     a.x_upd_src = hs.x_upd_src ? hs.x_upd_src : hs.x_upd;
     a.cond_copy = hs.cond_copy;
     a.partials = hs.partials;
@@ -777,20 +777,7 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
     // NETS = 1 scratch: s [N,H] | t [N,H] at the head of the float scratch
     a.st_out[0] = scratch;
     a.st_out[1] = scratch + hs.n_nodes * hs.H;
-    a.h0[0] = a.h0[1] = nullptr;
-    a.residual = 0;
-    a.stash_h0 = nullptr;
-    memset(a.stash_act, 0, sizeof(a.stash_act));
-    a.stash_st[0] = a.stash_st[1] = nullptr;
-    memset(a.stash_w, 0, sizeof(a.stash_w));
-    a.stash_ld = 0;
-    a.stash_mask = nullptr;
-    a.stash_mld = 0;
-    a.bnu_const = nullptr;
-    a.bnu_inv[0] = a.bnu_inv[1] = a.bnu_inv[2] = a.bnu_inv[3] = nullptr;
-    a.bnu_inv_eps = 0.f;
-    FrontArgs fa;
-    memset(&fa, 0, sizeof(fa));
+    FrontArgs fa{};
     const bool fold = s->attn && MT == 1 && NETS == 2 && !choose_big(hs) && front_fold_ok(hs, &fa);
     // per-graph log-likelihoods: the same shape choice, the ROWLD instance of it
     const bool rowld = hs.row_logdet != nullptr;
@@ -857,6 +844,14 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
     a.eps = hs.gnn.epsilon;
     a.alpha = hs.gnn.alpha;
 
+    // what the launch leaves for the caller: partials (one per workgroup), and whether sum(x^2) / the next bijector's column
+    // sums rode along
+    auto report = [&](int64_t wgs) {
+        *hs.n_partials = (int32_t)wgs;
+        if (hs.n_sq) *hs.n_sq = a.sq_partials ? (int32_t)wgs : 0;
+        if (hs.n_bn) *hs.n_bn = a.bn_part ? (int32_t)wgs : 0;
+        return GNF_OK;
+    };
     int rc;
     if (const int big = choose_big(hs)) {
         // bn_part stays unwritten (*n_bn = 0: the bijector in front of the next half-step runs its own moment pass)
@@ -875,13 +870,10 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
             if (rc) return rc;
             a.h0[0] = a.h0[1] = scratch;
             // split row tiles: flags and s rows behind the layer-0 rows (the caller zeroed the flags: split_epoch > 0)
-            int lmax = 1;
-            for (int j = 1; j < s->num_layers; ++j) lmax = lmax > s->dims[j] ? lmax : s->dims[j];
-            const size_t off = big_split_offset(hs.n_nodes, a.in0);
-            const size_t room = (size_t)hs.n_nodes * (size_t)(a.in0 + kLayeredActBufs * lmax + 2 * hs.H);
-            if (hs.split_epoch > 0 && big_cu_count() / 2 <= kBigSplitMax && off + big_split_floats() <= room) {
-                a.big_split_flag = reinterpret_cast<int*>(scratch + off);
-                a.big_split_s = scratch + off + kBigSplitMax;
+            const HalfScratch hsl = half_scratch(hs.n_nodes, a.in0, hidden_max(s), hs.H);
+            if (hs.split_epoch > 0 && big_cu_count() / 2 <= kBigSplitMax && hsl.split_fits()) {
+                a.big_split_flag = reinterpret_cast<int*>(scratch + hsl.split_flags);
+                a.big_split_s = scratch + hsl.split_s;
                 a.big_epoch = hs.split_epoch;
                 // force_shape = 49: the s-net workgroups of split tiles publish a value the t-net workgroups do not wait for -
                 // every split tile's partner is "lost" (the only way to execute that branch: in a healthy launch the flag is
@@ -891,11 +883,7 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
         }
         int n_wg = 0;
         rc = launch_half_big(a, hs.n_nodes, big, st, &n_wg, rowld ? hs.row_logdet : nullptr);
-        if (rc) return rc;
-        *hs.n_partials = (int32_t)n_wg;
-        if (hs.n_sq) *hs.n_sq = a.sq_partials ? (int32_t)n_wg : 0;
-        if (hs.n_bn) *hs.n_bn = 0;
-        return GNF_OK;
+        return rc ? rc : report(n_wg);
     }
     const int64_t tiles = (hs.n_nodes + 16 * MT - 1) / (16 * MT);
     a.n_tiles = (int32_t)tiles;
@@ -904,53 +892,26 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
         set_error("internal: MLP-row stash on a launch shape other than (1,2) (mlp_stash_supported is false there)");
         return GNF_EINVAL;
     }
-    if (hs.mlp_stash) {
-        const MlpStashLayout L = mlp_stash_layout(s, hs.n_nodes, hs.H);
-        a.stash_h0 = hs.mlp_stash + L.h0;
-        for (int q = 0; q < 2; ++q) {
-            for (int j = 1; j < s->num_layers; ++j) a.stash_act[q][j] = hs.mlp_stash + L.act + ((size_t)q * (s->num_layers - 1) + (j - 1)) * L.act_each;
-            a.stash_st[q] = hs.mlp_stash + L.st + (size_t)q * L.st_each;
-        }
-        for (int j = 0; j < s->num_layers; ++j) a.stash_w[j] = s->dims[j + 1];
-        a.stash_ld = L.ld_act;
-        a.stash_mask = reinterpret_cast<unsigned long long*>(hs.mlp_stash + L.mask);
-        a.stash_mld = L.mld;
-        if (fold)
-            rc = launch_shape<1, 2, true, true, true>(a, (unsigned)tiles, fused_front_lds_bytes(s, fa.d), st, &fa);
-        else
-            rc = launch_shape<1, 2, true>(a, (unsigned)tiles, lds + (size_t)L.mask_words * sizeof(unsigned long long), st);
-        if (rc) return rc;
-        *hs.n_partials = (int32_t)tiles;
-        if (hs.n_sq) *hs.n_sq = a.sq_partials ? (int32_t)tiles : 0;
-        if (hs.n_bn) *hs.n_bn = a.bn_part ? (int32_t)tiles : 0;
-        return GNF_OK;
-    }
-    if (NETS == 2 && rowld) {
-        if (fold && attn_front_fixed_geometry(fa.d))
-            rc = launch_shape<1, 2, false, true, true, true>(a, (unsigned)tiles, fused_front_lds_bytes(s, fa.d), st, &fa, &rla);
-        else if (fold)
-            rc = launch_shape<1, 2, false, true, false, true>(a, (unsigned)tiles, fused_front_lds_bytes(s, fa.d), st, &fa, &rla);
-        else
-            rc = MT == 2 ? launch_shape<2, 2, false, false, false, true>(a, (unsigned)tiles, lds, st, nullptr, &rla)
-                         : launch_shape<1, 2, false, false, false, true>(a, (unsigned)tiles, lds, st, nullptr, &rla);
-        if (rc) return rc;
-        *hs.n_partials = (int32_t)tiles;
-        if (hs.n_sq) *hs.n_sq = a.sq_partials ? (int32_t)tiles : 0;
-        if (hs.n_bn) *hs.n_bn = a.bn_part ? (int32_t)tiles : 0;
-        return GNF_OK;
-    }
     if (NETS == 2) {
-        if (fold && attn_front_fixed_geometry(fa.d))
-            rc = launch_shape<1, 2, false, true, true>(a, (unsigned)tiles, fused_front_lds_bytes(s, fa.d), st, &fa);
-        else if (fold)
-            rc = launch_shape<1, 2, false, true>(a, (unsigned)tiles, fused_front_lds_bytes(s, fa.d), st, &fa);
-        else
-            rc = MT == 2 ? launch_shape<2, 2>(a, (unsigned)tiles, lds, st) : launch_shape<1, 2>(a, (unsigned)tiles, lds, st);
-        if (rc) return rc;
-        *hs.n_partials = (int32_t)tiles;
-        if (hs.n_sq) *hs.n_sq = a.sq_partials ? (int32_t)tiles : 0;
-        if (hs.n_bn) *hs.n_bn = a.bn_part ? (int32_t)tiles : 0;
-        return GNF_OK;
+        const size_t front_lds = fold ? fused_front_lds_bytes(s, fa.d) : 0;
+        if (hs.mlp_stash) {
+            const MlpStashLayout L = mlp_stash_layout(s, hs.n_nodes, hs.H);
+            a.stash_h0 = hs.mlp_stash + L.h0;
+            for (int q = 0; q < 2; ++q) {
+                for (int j = 1; j < s->num_layers; ++j) a.stash_act[q][j] = hs.mlp_stash + L.act_of(q, j);
+                a.stash_st[q] = hs.mlp_stash + L.st_of(q);
+            }
+            for (int j = 0; j < s->num_layers; ++j) a.stash_w[j] = s->dims[j + 1];
+            a.stash_ld = L.ld_act;
+            a.stash_mask = reinterpret_cast<unsigned long long*>(hs.mlp_stash + L.mask);
+            a.stash_mld = L.mld;
+            rc = fold ? launch_shape<1, 2, true, true, true>(a, (unsigned)tiles, front_lds, st, &fa)
+                      : launch_shape<1, 2, true>(a, (unsigned)tiles, lds + (size_t)L.mask_words * sizeof(unsigned long long), st);
+        } else {
+            rc = rowld ? launch_nets2<true>(a, MT, fold, fa, &rla, (unsigned)tiles, lds, front_lds, st)
+                       : launch_nets2<false>(a, MT, fold, fa, nullptr, (unsigned)tiles, lds, front_lds, st);
+        }
+        return rc ? rc : report(tiles);
     }
     if (hs.x_upd_src || hs.cond_copy) {
         set_error("internal: out-of-place half-step on the one-net-per-workgroup shape (fused_supports_oop is false there)");

@@ -208,6 +208,7 @@ __device__ __forceinline__ void mlp_chunk_thin(const float* __restrict__ in_lds,
     }
 }
 
+// (entered with full exec: the MFMAs, and EPI_EX's v_writelane / v_readlane hand-over of the mask words, need all 64 lanes)
 template <int MT, int NV, int EPI = EPI_PLAIN>
 __device__ __forceinline__ void mlp_chunk(const float* __restrict__ in_lds, int LS, const WChunk& c,
                                           const WChunk& nx, int ts, const float* __restrict__ bias_lds,
@@ -314,6 +315,7 @@ __device__ __forceinline__ void mlp_chunk(const float* __restrict__ in_lds, int 
     [[maybe_unused]] int mlo = 0, mhi = 0;
     [[maybe_unused]] int my_word = 0;
     if constexpr (EPI == EPI_EX) {
+        static_assert(MT * NV * 4 <= 64, "EPI_EX: one mask word per lane of the wave");
         const int e = lane < MT * NV * 4 ? lane : 0;
         const int em = e / (4 * NV), eb = (e >> 2) % NV, er = e & 3;
         my_word = (4 * em + er) * ea.mld + nt0 + ts * eb;

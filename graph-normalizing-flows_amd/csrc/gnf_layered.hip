@@ -657,24 +657,19 @@ int launch_layer_norm(const LnArgs& a, int nets, hipStream_t st) {
     return GNF_OK;
 }
 
-static int lmax_of(const GnfMlp* m) {
-    int lmax = 1;
-    for (int j = 1; j < m->num_layers; ++j) lmax = lmax > m->dims[j] ? lmax : m->dims[j];
-    return lmax;
-}
-
-// One GNN module call: scratch = h0 [N, in0] | bufA [N, Lmax] | bufB [N, Lmax] | (s, t unused) | attention region
+// One GNN module call: the half-step scratch (HalfScratch) with one net's buffers in use
 int launch_gnn_layered(const int32_t* rowptr, const int32_t* col, int64_t n, const float* x,
                        int64_t ldx, int32_t H, const GnfGnnSpec& g, const GnfMlp* mlp, float* out,
                        int64_t ldo, float* scratch, hipStream_t st, const int32_t* node_offsets, int64_t n_graphs) {
     const int in0 = mlp->dims[0];
-    const int lmax = lmax_of(mlp);
-    float* h0 = scratch;
-    float* bufA = h0 + n * in0;
-    float* bufB = bufA + n * lmax;
+    const int lmax = hidden_max(mlp);
+    const HalfScratch L = half_scratch(n, in0, lmax, H);
+    float* h0 = scratch + L.h0;
+    float* bufA = scratch + L.bufA[0];
+    float* bufB = scratch + L.bufB[0];
     int rc;
     if (mlp->attn) {
-        float* attn_scratch = scratch + (size_t)n * (size_t)(in0 + kLayeredActBufs * lmax + 2 * H);
+        float* attn_scratch = scratch + L.attn_region;
         const GnfAttn* at[1] = {mlp->attn};
         float* h0s[1] = {h0};
         rc = attn_is_graph(mlp->attn)
@@ -719,21 +714,19 @@ int launch_half_layer_norm(const HalfStep& hs, float* sbuf, float* tbuf, const f
     return launch_layer_norm(a, 2, st);
 }
 
-// scratch layout (floats): h0 [N,in0] | bufA,bufB (s) | bufA,bufB (t) | s [N,H] | t [N,H] | attention region: qkv x2, h0_s, h0_t
 int launch_half_layered(const HalfStep& hs, float* scratch, hipStream_t st) {
     const int64_t n = hs.n_nodes;
     *hs.n_partials = 0;
     if (n == 0) return GNF_OK;
     const int H = hs.H;
     const int in0 = hs.s_net->dims[0];
-    int lmax = lmax_of(hs.s_net);
-    const int lt = lmax_of(hs.t_net);
-    lmax = lmax > lt ? lmax : lt;
-    float* h0 = scratch;
-    float* bufA[2] = {h0 + n * in0, h0 + n * in0 + 2 * n * lmax};   // per net: A | B
-    float* bufB[2] = {bufA[0] + n * lmax, bufA[1] + n * lmax};
-    float* sbuf = bufA[0] + n * lmax * kLayeredActBufs;
-    float* tbuf = sbuf + n * H;
+    const int lmax = hidden_max(hs.s_net, hs.t_net);
+    const HalfScratch S = half_scratch(n, in0, lmax, H);
+    float* h0 = scratch + S.h0;
+    float* bufA[2] = {scratch + S.bufA[0], scratch + S.bufA[1]};
+    float* bufB[2] = {scratch + S.bufB[0], scratch + S.bufB[1]};
+    float* sbuf = scratch + S.s;
+    float* tbuf = scratch + S.t;
     // training forward with the MLP-row stash in its layered mode (layered_stash_mode, gnf_train.hip): the layer-0 rows of a
     // message-passing net, every hidden activation and s, t are written straight into the half-step's slot
     float* keep[2 * GNF_MAX_LAYERS];
@@ -741,11 +734,10 @@ int launch_half_layered(const HalfStep& hs, float* scratch, hipStream_t st) {
     if (stash) {
         const MlpStashLayout L = mlp_stash_layout(hs.s_net, n, H);
         if (!hs.s_net->attn) h0 = hs.mlp_stash + L.h0;
-        for (int q = 0; q < 2; ++q)
-            for (int j = 0; j + 1 < hs.s_net->num_layers; ++j)
-                keep[q * GNF_MAX_LAYERS + j] = hs.mlp_stash + L.act + ((size_t)q * (hs.s_net->num_layers - 1) + j) * L.act_each;
-        sbuf = hs.mlp_stash + L.st;
-        tbuf = sbuf + L.st_each;
+        for (int q = 0; q < 2; ++q)   // (run_mlps keeps the OUTPUT of hidden layer j - 1 = the input of layer j)
+            for (int j = 1; j < hs.s_net->num_layers; ++j) keep[q * GNF_MAX_LAYERS + j - 1] = hs.mlp_stash + L.act_of(q, j);
+        sbuf = hs.mlp_stash + L.st_of(0);
+        tbuf = hs.mlp_stash + L.st_of(1);
     }
     const float* h0s = h0;
     const float* h0t = h0;
@@ -789,28 +781,18 @@ int launch_half_layered(const HalfStep& hs, float* scratch, hipStream_t st) {
 int launch_attn_pair(const HalfStep& hs, float* scratch, float** h0_pair, hipStream_t st) {
     const int64_t n = hs.n_nodes;
     const int in0 = hs.s_net->dims[0];
-    int lmax = lmax_of(hs.s_net);
-    const int lt = lmax_of(hs.t_net);
-    lmax = lmax > lt ? lmax : lt;
-    float* region = hs.attn_region ? hs.attn_region
-                                   : scratch + (size_t)n * (size_t)(in0 + kLayeredActBufs * lmax + 2 * hs.H);
-    const GnfAttn* a0 = hs.s_net->attn;
+    float* region = hs.attn_region
+                        ? hs.attn_region
+                        : scratch + half_scratch(n, in0, hidden_max(hs.s_net, hs.t_net), hs.H).attn_region;
     const GnfAttn* at[2] = {hs.s_net->attn, hs.t_net->attn};
-    if (attn_is_graph(a0)) {   // (no stash slot: attn_region is NULL for this scope)
-        const size_t Pg = (size_t)attn_qkv_width(a0);
-        h0_pair[0] = region + 2 * (size_t)n * Pg;
-        h0_pair[1] = h0_pair[0] + (size_t)n * in0;
+    const AttnRegion R = attn_region(at[0], n, in0);
+    h0_pair[0] = region + R.h0[0];
+    h0_pair[1] = region + R.h0[1];
+    if (attn_is_graph(at[0]))   // (no stash slot: attn_region is NULL for this scope)
         return launch_attn_graph_front(at, 2, n, hs.x_cond, hs.ld, hs.H, in0, hs.node_offsets, hs.n_graphs, region, h0_pair, st);
-    }
-    const size_t P = 2 * (size_t)a0->num_heads * a0->kq_dim + a0->v_dim;
-    h0_pair[0] = region + 2 * (size_t)n * P;
-    h0_pair[1] = h0_pair[0] + (size_t)n * in0;
-    // a stash slot also keeps the attended values and the softmax statistics (attn_scratch_floats' layout)
-    const size_t NV = (size_t)a0->num_heads * a0->v_dim;
-    float* agg0 = h0_pair[1] + (size_t)n * in0;
-    float* mz0 = agg0 + 2 * (size_t)n * NV;
-    float* agg_out[2] = {agg0, agg0 + (size_t)n * NV};
-    float* mz_out[2] = {mz0, mz0 + (size_t)n * 3 * a0->num_heads};
+    // a stash slot also keeps the attended values and the softmax statistics
+    float* agg_out[2] = {region + R.agg[0], region + R.agg[1]};
+    float* mz_out[2] = {region + R.stats[0], region + R.stats[1]};
     const bool keep = hs.attn_region != nullptr;
     return launch_attn_front(hs.rowptr, hs.col, n, hs.x_cond, hs.ld, hs.H, at, 2, in0, region, h0_pair, st, hs.n_edges,
                              /*need_qkv=*/keep, hs.attn_packed, keep ? agg_out : nullptr, keep ? mz_out : nullptr);

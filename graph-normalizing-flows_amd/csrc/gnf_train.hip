@@ -1054,10 +1054,9 @@ static BwdPlan plan_backward(int64_t n, int32_t D, const GnfMlp* net, int n_sets
     p.H = D / 2;
     p.K = net->num_layers;
     p.in0 = net->dims[0];
-    int lmax = 1;
+    const int lmax = hidden_max(net);
     int64_t wsum = 0, osum = 0;
     for (int j = 0; j < p.K; ++j) {
-        if (j >= 1) lmax = lmax > net->dims[j] ? lmax : net->dims[j];
         wsum += (int64_t)net->dims[j] * net->dims[j + 1];
         osum += net->dims[j + 1];
     }
@@ -1114,7 +1113,7 @@ static BwdPlan plan_backward(int64_t n, int32_t D, const GnfMlp* net, int n_sets
     off += (size_t)(p.slab_sets - 1) * p.slab_stride;
     p.qkv = off, off += 2 * al64((size_t)n * p.P);
     p.dagg = off, off += 2 * al64((size_t)n * p.NV);
-    p.stats = off, off += 2 * al64((size_t)n * 3 * p.nh);
+    p.stats = off, off += 2 * al64((size_t)n * attn_stats_width(p.nh));
     if (net->attn) {  // (s-nets first, then t-nets: n_nets_each of either)
         p.wot_each = al64((size_t)((p.C + 15) & ~15) * (size_t)((p.NV + 15) & ~15));
         p.wot = off, off += 2 * (size_t)n_nets_each * p.wot_each;
@@ -1189,10 +1188,6 @@ __global__ __launch_bounds__(256) void k_pack_wot(const PackWot b) {
     }
 }
 
-static const GnfMlp* pick_net(const GnfFlow* f, const GnfMlp* nets, int half, int i) {
-    return f->weight_sharing ? &nets[half] : &nets[half * f->num_timesteps + i];
-}
-
 // Buffers of one half-step, resolved for one operand set.
 struct BwdOperands {
     float* hin[2 * GNF_MAX_LAYERS];   // [net * K + j]: input of layer j
@@ -1231,7 +1226,7 @@ static BwdOperands bwd_operands(const BwdPlan& p, float* ws, int set, bool attn)
         o.agg[q] = wss + p.agg + q * al64((size_t)n * p.NV);
         o.qkv[q] = ws + p.qkv + (size_t)q * n * p.P;   // launch_attn_front's layout: net q at scratch + q * n * P
         o.dagg[q] = ws + p.dagg + q * al64((size_t)n * p.NV);
-        o.stats[q] = ws + p.stats + q * al64((size_t)n * 3 * p.nh);
+        o.stats[q] = ws + p.stats + q * al64((size_t)n * attn_stats_width(p.nh));
         for (int j = 0; j < K; ++j) {
             const int e = q * K + j;
             o.hin[e] = j == 0 ? o.h0[q] : wss + p.acts + ((size_t)q * (K - 1) + (j - 1)) * act_sz;
@@ -1300,14 +1295,12 @@ static DwPolicy dw_policy(const GnfMlp* net, int64_t bwd_tiles, size_t bwd_lds) 
         // hundreds of full 128 x 128 tiles over the whole node axis - the wide kernel with ONE chunk per tile (the slab IS
         // the gradient: no reduce pass) where three workgroups per CU hold them all, against the grouped kernel's 128 x 64
         // tiles + slabs + reduce: wide_fc_train 34.2 -> 29.8 ms per step (measured with dw_wide_units = 640 .. 4096)
-        int lmax = 1;
-        for (int j = 1; j < net->num_layers; ++j) lmax = lmax > net->dims[j] ? lmax : net->dims[j];
         // ONE workgroup per CU, each taking its share of the hidden layers' 2 x 256 full tiles by stride (one chunk per tile:
         // the slab is the gradient) with the thin first / last layers' tiles cut into pieces that ride behind through slabs of
         // their own.  The count hardly matters (measured 128 .. 512 workgroups: 29.56 .. 29.90 ms per wide_fc_train step,
         // best at one per CU): the step is bound by the matrix cores under these kernels' efficiencies, and one workgroup per
         // CU leaves the other LDS slot of every CU to the main stream's kernels
-        if (lmax >= 512) pol.max_units = big_cu_count(), pol.budget_us = 1e30, pol.big_tiles_only = true;
+        if (hidden_max(net) >= 512) pol.max_units = big_cu_count(), pol.budget_us = 1e30, pol.big_tiles_only = true;
     }
     if (env_u > 0) pol.max_units = (int)env_u, pol.budget_us = 1e30;
     return pol;
@@ -2099,6 +2092,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
     }
     const int H = D / 2;
     const size_t stash_slot = attn_stash_slot_floats(flow, n);
+    const AttnRegion R = attn_region(flow->s_nets[0].attn, n, p.in0);   // (a slot's layout, as the plan: net 0's)
     if (flow->attn_stash && stash_slot > 0 && flow->attn_stash_bytes < (size_t)2 * T * stash_slot * sizeof(float)) {
         set_error("gnf_grevnet_backward_f32: attn_stash %zu < %zu bytes", flow->attn_stash_bytes,
                   (size_t)2 * T * stash_slot * sizeof(float));
@@ -2282,8 +2276,8 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
     const float* fold_dh[2] = {nullptr, nullptr};
     for (int i = T - 1; i >= 0; --i)
         for (int half = 1; half >= 0; --half) {
-            const GnfMlp* nets[2] = {pick_net(flow, flow->s_nets, half, i), pick_net(flow, flow->t_nets, half, i)};
-            const GnfMlp* grads[2] = {pick_net(grad, grad->s_nets, half, i), pick_net(grad, grad->t_nets, half, i)};
+            const GnfMlp* nets[2] = {flow_net(flow, flow->s_nets, half, i), flow_net(flow, flow->t_nets, half, i)};
+            const GnfMlp* grads[2] = {flow_net(grad, grad->s_nets, half, i), flow_net(grad, grad->t_nets, half, i)};
             const bool acc = flow->weight_sharing && used[half];
             used[half] = true;
             const int co = half == 0 ? 0 : H, uo = half == 0 ? H : 0;
@@ -2298,12 +2292,12 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
             if (stashed) {
                 float* slot = flow->attn_stash + (size_t)(2 * i + half) * stash_slot;
                 for (int q = 0; q < 2; ++q) {
-                    o.qkv[q] = slot + (size_t)q * n * p.P;
-                    o.h0[q] = slot + 2 * (size_t)n * p.P + (size_t)q * n * p.in0;
+                    o.qkv[q] = slot + R.qkv[q];
+                    o.h0[q] = slot + R.h0[q];
                     o.hin[q * p.K] = o.h0[q];
                     // attended values (A operand of dWo) and softmax statistics of the forward pass
-                    o.agg[q] = slot + 2 * (size_t)n * (p.P + p.in0) + (size_t)q * n * p.NV;
-                    o.stats[q] = slot + 2 * (size_t)n * (p.P + p.in0 + p.NV) + (size_t)q * n * 3 * p.nh;
+                    o.agg[q] = slot + R.agg[q];
+                    o.stats[q] = slot + R.stats[q];
                 }
             }
             float* x_cond = z + co;
@@ -2342,7 +2336,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
                             o.h0[q] = slot + msl.h0;
                             o.hin[q * p.K] = o.h0[q];
                         }
-                        for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act + ((size_t)q * (p.K - 1) + (j - 1)) * msl.act_each;
+                        for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act_of(q, j);
                     }
                 }
                 const float* h0c[2] = {o.h0[0], o.h0[1]};
@@ -2377,7 +2371,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
                 }
                 if (mstashed) {
                     const float* slot = flow->mlp_stash + (size_t)(2 * i + half) * msl.slot;
-                    for (int q = 0; q < 2; ++q) ba.st_in[q] = slot + msl.st + (size_t)q * msl.st_each;
+                    for (int q = 0; q < 2; ++q) ba.st_in[q] = slot + msl.st_of(q);
                     ba.mask_in = reinterpret_cast<const unsigned long long*>(slot + msl.mask);
                 }
                 const int prev = (step + 1) & 1, cur = step & 1;   // pend[prev]: half-step k-1, pend[cur]: k-2
@@ -2441,7 +2435,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
             if (fused && mstashed) {  // (attention nets, or the auxiliary-stream scheme by option: the stash without the merged launch)
                 float* slot = flow->mlp_stash + (size_t)(2 * i + half) * msl.slot;
                 for (int q = 0; q < 2; ++q)
-                    for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act + ((size_t)q * (p.K - 1) + (j - 1)) * msl.act_each;
+                    for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act_of(q, j);
                 if (!attn) o.h0[0] = o.h0[1] = o.hin[0] = o.hin[p.K] = slot + msl.h0;
                 const float* h0c[2] = {o.h0[0], o.h0[1]};
                 BwdArgs ba;
@@ -2451,7 +2445,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
                 rc = build_bwd_args(csr->rowptr, csr->col, n, flow->gnn, nets[0], nets[1], x_cond, z + uo, ld, g + uo, D, H,
                                     o.h0[0], attn ? h0c : nullptr, o.hin, p.lmax, o.dPs, p.lmax, o.gst, o.dh0, &ba, &mt, &tiles, &lds);
                 if (rc) return rc;
-                for (int q = 0; q < 2; ++q) ba.st_in[q] = slot + msl.st + (size_t)q * msl.st_each;
+                for (int q = 0; q < 2; ++q) ba.st_in[q] = slot + msl.st_of(q);
                 ba.mask_in = reinterpret_cast<const unsigned long long*>(slot + msl.mask);
                 if (attn && wot_packed) {  // (as on the merged walk)
                     const int ni = flow->weight_sharing ? half : half * T + i;
@@ -2470,8 +2464,8 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
                     float* slot = flow->mlp_stash + (size_t)(2 * i + half) * msl.slot;
                     for (int q = 0; q < 2; ++q) {
                         if (!attn) o.h0[q] = slot + msl.h0, o.hin[q * p.K] = o.h0[q];
-                        for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act + ((size_t)q * (p.K - 1) + (j - 1)) * msl.act_each;
-                        o.stb[q] = slot + msl.st + (size_t)q * msl.st_each;
+                        for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act_of(q, j);
+                        o.stb[q] = slot + msl.st_of(q);
                     }
                 }
                 rc = mlp_backward_generic(p, o, flow->gnn, nets, grads, acc, x_cond, z + uo, ld, g + uo, D, wsf, st, rows);
