@@ -3,7 +3,8 @@
 MI355X kernels: node-embedding chunks on disk -> batches of complete graphs (transform_example) -> GRevNet with that
 driver's default GNN (dm_attn: one head, kq = v = 64, C = 64, kq_dim_division; :40-46, 303-310) around its wide relu
 MLPs (latent 2048 x 3 layers, D = 200, 10 coupling layers, batch norm) -> Adam (beta2 0.999, constant lr); then the
-sampling pipeline z ~ N(0, I) -> grevnet(., inverse=False) -> pred_adj(scaled_hacky_sigmoid_l2) -> threshold 0.5.
+sampling pipeline z ~ N(0, I) -> grevnet(., inverse=False) -> pred_adj(scaled_hacky_sigmoid_l2) -> threshold 0.5
+(flow.generate_graphs: the generated graphs come back as a GraphsTuple with its CSR).
 
 There is no trained encoder here (run_gnn.py is out of scope), so --make_chunks writes embedding chunks whose
 embeddings are synthetic (two well-separated clusters per graph, so that the decoder finds structure); point
@@ -29,7 +30,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gnf_amd import datasets as D, gnn                                # noqa: E402
-from gnf_amd.flow import pred_adj, sample                             # noqa: E402
+from gnf_amd.flow import generate_graphs                             # noqa: E402
 from gnf_amd.train import GRevNetTrainer                              # noqa: E402
 
 
@@ -133,12 +134,11 @@ def main():
     # ---- sampling pipeline (train_grevnet_with_data.py:397-416, 526-540) ---------------------------------------
     n_node = np.asarray(random.sample(list(data.n_node) * F.sample_size, F.sample_size), np.int32)
     shell = D.transform_example(np.zeros((int(n_node.sum()), F.node_embedding_dim), np.float32), n_node, dev)
-    out = sample(grevnet, shell)
-    blocks = pred_adj(out["grevnet_top"])
-    for i, b in enumerate(blocks):
-        adj = (b > 0.5)
-        print(f"sampled graph {i}: {int(n_node[i])} nodes, {int(adj.sum().item()) // 2} edges, "
-              f"mean sample log-prob {float(out['sample_log_prob'][sum(n_node[:i]):sum(n_node[:i + 1])].mean()):.2f}")
+    out = generate_graphs(grevnet, shell)      # sample -> flow in reverse -> edge lists + CSR, all on the device
+    rows = torch.stack([out["graph"].n_node.to(dev, torch.float64), out["graph"].n_edge.to(torch.float64),
+                        out["sample_log_prob_per_graph"]]).cpu().numpy()          # the one device-to-host copy of the tail
+    for i, (nodes, edges, mean_lp) in enumerate(rows.T):
+        print(f"sampled graph {i}: {int(nodes)} nodes, {int(edges) // 2} edges, mean sample log-prob {mean_lp:.2f}")
     if tmp is not None:
         tmp.cleanup()
 

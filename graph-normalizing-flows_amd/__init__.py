@@ -3,8 +3,9 @@ log-det hot path of jliu/graph-normalizing-flows behind the reference's own gnn.
 
 Import as `gnf_amd` (the directory name has a hyphen; gnf_amd.py at the repo root is the loader):
     from gnf_amd.gnn import GRevNet, avg_then_mlp_gnn, make_mlp_model, leaky_relu
+    from gnf_amd.flow import log_prob_per_graph, sample, decode_graphs, generate_graphs
 """
 from . import _abi
-from .graphs import GraphsTuple, data_dicts_to_graphs_tuple, build_csr_host, csr_of
+from .graphs import GraphsTuple, data_dicts_to_graphs_tuple, build_csr_host, csr_of, seed_csr_cache
 
-__all__ = ["GraphsTuple", "data_dicts_to_graphs_tuple", "build_csr_host", "csr_of", "_abi"]
+__all__ = ["GraphsTuple", "data_dicts_to_graphs_tuple", "build_csr_host", "csr_of", "seed_csr_cache", "_abi"]

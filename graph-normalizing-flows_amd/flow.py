@@ -167,3 +167,95 @@ def pred_adj(gnn_output, distance_fn=scaled_hacky_sigmoid_l2, max_nodes_per_grap
         blocks.append(out[o:o + n * n].view(n, n))
         o += n * n
     return blocks
+
+
+def decode_graphs(gnn_output, threshold=0.5, self_loops=False, edge_capacity=None, n_node_host=None,
+                  distance_fn=scaled_hacky_sigmoid_l2, max_nodes_per_graph=None):
+    """The graphs the sampling path generates (generate_graphs.py:68-78, train_grevnet_with_data.py:532-540: `pred_adj >
+    0.5`, one graph per block), as device edge lists: edge (sender = j, receiver = i) of graph g exists iff
+    pred_adj(gnn_output)[g][i, j] > threshold - the same fp32 arithmetic, bit for bit, without the dense blocks
+    (gnf_adj_edges_count_f32 / gnf_adj_edges_fill).  The diagonal is no edge unless self_loops=True; then every node has its
+    self loop whatever the threshold (the convention of the flow's datasets).  Returns a dict:
+      "graph"        GraphsTuple: the input's nodes and n_node, int32 senders / receivers (batch-wide node ids, receivers
+                     ascending, senders ascending within a receiver) and n_edge, zero edges / globals as
+                     data_dicts_to_graphs_tuple makes them
+      "csr"          graphs.Csr over (rowptr, senders): the receiver-sorted CSR of that edge list and, the edge set being
+                     exactly symmetric, its by-sender transpose as well
+      "total_edges"  0-d device int64
+    Without edge_capacity the call reads total_edges once (an 8-byte copy, its only synchronisation when n_node_host or
+    max_nodes_per_graph says how large the graphs are; otherwise n_node is read from the device first, as pred_adj does),
+    allocates exactly that many edges and seeds csr_of's cache for both orientations: a GRevNet call or a trainer step on
+    result["graph"] launches no gnf_build_csr.
+    With edge_capacity (and n_node_host, a host sequence of the graphs' sizes, or max_nodes_per_graph) nothing is copied to
+    the host and nothing synchronises, so the call can be captured into a hipGraph.  The edge tensors (and "graph".edges)
+    then have edge_capacity entries of which only the first min(total_edges, edge_capacity) are valid - the rest is
+    unspecified - and rowptr / n_edge / "csr" describe the untruncated edge list: check total_edges <= edge_capacity before
+    using them.  The CSR cache is not seeded in this mode."""
+    if distance_fn is not scaled_hacky_sigmoid_l2:
+        raise NotImplementedError("decode_graphs supports distance_fn=scaled_hacky_sigmoid_l2 (loss.py:45-53)")
+    from .graphs import Csr, GraphsTuple, seed_csr_cache
+    lib = _abi.lib()
+    z = gnn_output.nodes
+    if z.device.type != "cuda":
+        raise _abi.GnfError("decode_graphs runs on a HIP device only (no CPU path)")
+    dev = z.device
+    z = z.to(torch.float32)
+    if z.stride(1) != 1:
+        z = z.contiguous()
+    n, d = int(z.shape[0]), int(z.shape[1])
+    ld = z.stride(0) if n > 1 else max(int(z.stride(0)), d)   # (torch reports any stride, 0 included, for a dimension of 0 or 1 rows)
+    b = int(gnn_output.n_node.shape[0])
+    if n_node_host is not None:
+        sizes = [int(v) for v in n_node_host]
+        if len(sizes) != b or sum(sizes) != n:
+            raise ValueError(f"n_node_host describes {len(sizes)} graphs / {sum(sizes)} nodes, the batch has {b} / {n}")
+    elif max_nodes_per_graph is None:
+        sizes = gnn_output.n_node.cpu().tolist()
+    else:
+        sizes = None
+    largest = (max(sizes) if sizes else 0) if sizes is not None else None
+    cap = int(max_nodes_per_graph) if max_nodes_per_graph is not None else largest
+    if largest is not None and cap < largest:   # the bitmap holds `cap` columns per row: a smaller bound would drop edges
+        raise ValueError(f"max_nodes_per_graph={cap} is below the largest graph of the batch ({largest} nodes)")
+    nn = gnn_output.n_node.to(device=dev, dtype=torch.int32).contiguous()
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    n_edge = torch.empty(b, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    ws_bytes = lib.gnf_adj_edges_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_adj_edges_count_f32(_abi.ptr(z), ld, d, _abi.ptr(nn), b, n, cap, float(threshold),
+                                               int(bool(self_loops)), _abi.ptr(rowptr), _abi.ptr(n_edge), _abi.ptr(total),
+                                               _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_edges_count_f32")
+        exact = edge_capacity is None
+        e = int(total.item()) if exact else int(edge_capacity)
+        senders = torch.empty(e, dtype=torch.int32, device=dev)
+        receivers = torch.empty(e, dtype=torch.int32, device=dev)
+        _abi.check(lib.gnf_adj_edges_fill(b, n, cap, _abi.ptr(rowptr), e, _abi.ptr(senders), _abi.ptr(receivers),
+                                          _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_edges_fill")
+    graph = GraphsTuple(nodes=gnn_output.nodes, edges=torch.zeros(e, dtype=torch.float32, device=dev), receivers=receivers,
+                        senders=senders, globals=torch.zeros(b, dtype=torch.float32, device=dev), n_node=gnn_output.n_node,
+                        n_edge=n_edge)
+    csr = Csr(rowptr, senders, n, e)
+    if exact:
+        seed_csr_cache(graph, csr, by_sender=False)
+        seed_csr_cache(graph, csr, by_sender=True)
+    return {"graph": graph, "csr": csr, "total_edges": total[0]}
+
+
+def generate_graphs(grevnet, shell_graph, generator=None, threshold=0.5, self_loops=False):
+    """generate_graphs.py:57-84 / train_grevnet_with_data.py:526-540 in one call: sample z ~ N(0, I) on shell_graph's
+    topology, run the flow in reverse, decode the embeddings to graphs (decode_graphs, exact-size mode).  Returns what
+    decode_graphs returns, what sample returns, and "sample_log_prob_per_graph": the mean of sample_log_prob over each
+    graph's nodes (generate_graphs.py:76; device fp64 [B], 0 for a graph without nodes)."""
+    out = sample(grevnet, shell_graph, generator=generator)
+    top = out["grevnet_top"]
+    res = decode_graphs(top, threshold=threshold, self_loops=self_loops)
+    dev = top.nodes.device
+    nn = shell_graph.n_node.to(device=dev, dtype=torch.int64)
+    b = int(nn.shape[0])
+    gid = torch.repeat_interleave(torch.arange(b, device=dev), nn, output_size=int(top.nodes.shape[0]))
+    sums = torch.zeros(b, dtype=torch.float64, device=dev).index_add_(0, gid, out["sample_log_prob"])
+    res.update(out)
+    res["sample_log_prob_per_graph"] = sums / torch.clamp(nn, min=1).to(torch.float64)
+    return res

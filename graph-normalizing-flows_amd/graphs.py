@@ -176,6 +176,19 @@ def csr_of(graph, by_sender=False):
     return csr
 
 
+def seed_csr_cache(graph, csr, by_sender=False):
+    """Store a CSR that already exists (flow.decode_graphs produces the edge list sorted, together with its rowptr) under the
+    key csr_of(graph, by_sender) looks up, so that no gnf_build_csr runs for this graph.  The caller vouches that `csr`
+    IS what build_csr_device(graph, by_sender) would return.  Returns csr."""
+    key = (graph.senders.data_ptr(), graph.receivers.data_ptr(), int(graph.senders.shape[0]),
+           int(graph.nodes.shape[0]), str(graph.senders.device), bool(by_sender))
+    _CSR_CACHE[key] = (csr, graph.senders, graph.receivers)
+    _CSR_CACHE.move_to_end(key)
+    while len(_CSR_CACHE) > _CSR_CACHE_MAX:
+        _CSR_CACHE.popitem(last=False)
+    return csr
+
+
 def clear_csr_cache():
     _CSR_CACHE.clear()
 

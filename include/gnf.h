@@ -354,6 +354,39 @@ int gnf_pred_adj_f32(const float* z, int64_t ld, int32_t D, const int32_t* n_nod
                      int32_t max_nodes_per_graph, float* out_blocks, int64_t* block_off, void* ws,
                      size_t ws_bytes, gnf_stream_t stream);
 
+/* Added within ABI v10 (new entry points only, GNF_ABI_VERSION stays 10).  Sampled embeddings -> graphs, on the device:
+ * what the reference does on the host after pred_adj - `pred_adj > 0.5`, one adjacency block and one graph per batch entry
+ * (generate_graphs.py:68-78, train_grevnet_with_data.py:532-540) - without the dense float blocks.
+ * Edge rule: for row i and column j of graph g, edge (sender = j, receiver = i) exists iff P[i,j] > threshold (strictly, in
+ * fp32), P[i,j] being the very fp32 expression of gnf_pred_adj_f32 (loss.py:45-53,154-159), so the edge set is bit-equal to
+ * thresholding its blocks.  The diagonal is never an edge, unless self_loops != 0: then (i,i) always is, whatever the
+ * threshold (one self loop per node, the convention of the flow's datasets, graph_data.py:33-50).
+ * The result is deterministic (no atomics): receivers ascend, senders ascend within a receiver.  Hence (rowptr, senders) is
+ * the receiver-sorted CSR gnf_build_csr would make of the edge list, and - P being symmetric bit for bit - also its by-sender
+ * transpose.  Ids are batch-wide node ids (node_offset[g] + local id), as in a GraphsTuple.
+ * Two calls on one stream, so that the caller can size the edge arrays in between (or not: see edge_capacity):
+ *   gnf_adj_edges_count_f32  writes rowptr[n_nodes + 1] (int32), n_edge[n_graphs] (int32), *total (int64) - all device -
+ *                            and leaves the edge bitmap in ws.  n_nodes = sum(n_node); max_nodes_per_graph: any upper bound
+ *                            on n_node (sizes launch and bitmap; nothing is read from the host).  A bound below the largest
+ *                            graph, or counts that do not add up to n_nodes, lose edges but never touch memory outside the
+ *                            arrays.  n_graphs == 0 or n_nodes == 0: GNF_OK, rowptr[0] = 0 and *total = 0 written.
+ *   gnf_adj_edges_fill       expands that bitmap (same n_graphs / n_nodes / max_nodes_per_graph / ws, same stream) into
+ *                            senders / receivers [edge_capacity] (int32).  Only edge ids < edge_capacity are written: a buffer
+ *                            smaller than *total holds the first edge_capacity edges and is never overrun.
+ * GNF_ESHAPE: D < 1, ld < D, a negative size, max_nodes_per_graph == 0 with nodes, or n_nodes * max_nodes_per_graph >
+ * INT32_MAX (the edge ids are int32); GNF_EINVAL: null pointers; GNF_EWORKSPACE: ws_bytes below
+ * gnf_adj_edges_workspace_bytes (a host computation: node offsets, bitmap [n_nodes][ceil(max/64)] of 64-bit words, row
+ * counts; the scan needs no memory of its own) - all before any launch.  Asynchronous, no host synchronisation, capturable. */
+size_t gnf_adj_edges_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph);
+/* replaces generate_graphs.py:68-78 / train_grevnet_with_data.py:532-540 (threshold) on loss.py:45-53,154-159 (P) */
+int gnf_adj_edges_count_f32(const float* z, int64_t ld, int32_t D, const int32_t* n_node, int64_t n_graphs, int64_t n_nodes,
+                            int32_t max_nodes_per_graph, float threshold, int32_t self_loops, int32_t* rowptr,
+                            int32_t* n_edge, int64_t* total, void* ws, size_t ws_bytes, gnf_stream_t stream);
+/* replaces the per-block graph construction of generate_graphs.py:68-78 / train_grevnet_with_data.py:532-540 */
+int gnf_adj_edges_fill(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph, const int32_t* rowptr,
+                       int64_t edge_capacity, int32_t* senders, int32_t* receivers, const void* ws, size_t ws_bytes,
+                       gnf_stream_t stream);
+
 /* ---- training step ---------------------------------------------------------------
  * Replaces optimizer.compute_gradients(total_loss) (run_grevnet.py:361-362) for
  *   total_loss = -(sum_n log N(z_n; 0, I) + log_det_jacobian)           (run_grevnet.py:291-295)
