@@ -15,6 +15,7 @@ GNF_COMBINE_EPS, GNF_COMBINE_CONCAT = 0, 1
 GNF_ACT_RELU, GNF_ACT_LEAKY_RELU = 0, 1
 GNF_FORWARD, GNF_INVERSE = 0, 1
 GNF_ATTN_EDGES, GNF_ATTN_GRAPH = 0, 1   # GnfAttn.scope (ABI v10)
+GNF_MMD_GAUSSIAN_EMD, GNF_MMD_GAUSSIAN_TV = 0, 1   # gnf_hist_mmd_f64 kernel
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNF_LIB_PATH: developer override (a library built from another checkout, for A/B runs); still a HIP build
@@ -110,6 +111,13 @@ _SIGNATURES = {
                                           C.c_void_p]),
     "gnf_adj_edges_fill": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    # added within ABI v10: degree / clustering statistics of a batch of graphs and the MMD of two histogram sets
+    "gnf_graph_stats_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_graph_stats": (C.c_int, [C.POINTER(GnfCsr), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_hist_mmd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gnf_hist_mmd_f64": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                   C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gnf_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.POINTER(GnfFlow)]),
     "gnf_grevnet_backward_f32": (C.c_int, [C.POINTER(GnfCsr), C.POINTER(GnfCsr), C.POINTER(GnfFlow),
                                            C.POINTER(GnfFlow), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,

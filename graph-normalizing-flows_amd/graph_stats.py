@@ -1,0 +1,125 @@
+"""Scoring generated graphs on the device: the step after flow.generate_graphs.
+
+GraphRNN-style evaluation compares generated graphs to held-out ones by the MMD of their degree and clustering-coefficient
+histograms.  The reference stops at pickling the graphs (generate_graphs.py:68-84); here the edge lists never leave the
+device: graph_stats (gnf_graph_stats) turns a batch into per-node degrees / triangle counts and per-graph histograms,
+hist_mmd (gnf_hist_mmd_f64) reduces two histogram sets to one MMD^2, evaluate_generated does both for two batches.
+Every graph is read as undirected and simple (self loops ignored, duplicates once, one direction is enough).  HIP only:
+CPU tensors raise GnfError.
+"""
+import ctypes as C
+
+import torch
+
+from . import _abi
+
+_KERNELS = {"gaussian_emd": _abi.GNF_MMD_GAUSSIAN_EMD, "gaussian_tv": _abi.GNF_MMD_GAUSSIAN_TV}
+MAX_NODES_PER_GRAPH = 65536   # a node's triangle count must fit int32
+STATS_KEYS = ("degree", "triangles", "clustering", "degree_hist", "clustering_hist", "n_edges", "n_triangles")
+
+
+def graph_stats(graph, max_nodes_per_graph=None, n_node_host=None, clustering_bins=100):
+    """Degree and clustering statistics of every graph of a GraphsTuple, as a dict of device tensors:
+      "degree", "triangles"   int32 [N]: neighbours of each node, triangles through it
+      "clustering"            float64 [N]: 2 T / (d (d - 1)), 0 for d < 2
+      "degree_hist"           int32 [B, max_nodes_per_graph]: nodes of graph g with degree d
+      "clustering_hist"       int32 [B, clustering_bins]: bin 0 for d < 2, else min(bins - 1, (2 T bins) // (d (d - 1))) in
+                              exact integers (c = 1 lands in the last bin)
+      "n_edges", "n_triangles" int64 [B]
+    The CSR comes from graphs.csr_of: on the result of decode_graphs / generate_graphs no gnf_build_csr runs.
+    With max_nodes_per_graph (any upper bound on n_node) or n_node_host (the sizes as a host sequence) nothing is copied to
+    the host and nothing synchronises, so the call can be captured; otherwise n_node is read once, as pred_adj does."""
+    from .graphs import csr_desc, csr_of
+    lib = _abi.lib()
+    dev = graph.senders.device
+    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
+        raise _abi.GnfError("graph_stats runs on a HIP device only (no CPU path)")
+    n = int(graph.nodes.shape[0])
+    b = int(graph.n_node.shape[0])
+    bins = int(clustering_bins)
+    if n_node_host is not None:
+        sizes = [int(v) for v in n_node_host]
+        if len(sizes) != b or sum(sizes) != n:
+            raise ValueError(f"n_node_host describes {len(sizes)} graphs / {sum(sizes)} nodes, the batch has {b} / {n}")
+    elif max_nodes_per_graph is None:
+        sizes = graph.n_node.cpu().tolist()
+    else:
+        sizes = None
+    largest = (max(sizes) if sizes else 0) if sizes is not None else None
+    cap = int(max_nodes_per_graph) if max_nodes_per_graph is not None else largest
+    if largest is not None and cap < largest:   # the bitmap holds `cap` columns per row: a smaller bound would drop edges
+        raise ValueError(f"max_nodes_per_graph={cap} is below the largest graph of the batch ({largest} nodes)")
+    if cap > MAX_NODES_PER_GRAPH:
+        raise ValueError(f"max_nodes_per_graph={cap} exceeds {MAX_NODES_PER_GRAPH}")
+    if bins < 1:
+        raise ValueError(f"clustering_bins={bins}")
+    csr = csr_of(graph)
+    desc = csr_desc(graph, csr, node_offsets=True)
+    out = {"degree": torch.empty(n, dtype=torch.int32, device=dev),
+           "triangles": torch.empty(n, dtype=torch.int32, device=dev),
+           "degree_hist": torch.empty((b, cap), dtype=torch.int32, device=dev),
+           "clustering_hist": torch.empty((b, bins), dtype=torch.int32, device=dev),
+           "n_edges": torch.empty(b, dtype=torch.int64, device=dev),
+           "n_triangles": torch.empty(b, dtype=torch.int64, device=dev)}
+    ws_bytes = lib.gnf_graph_stats_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_graph_stats(C.byref(desc), cap, bins, _abi.ptr(out["degree"]), _abi.ptr(out["triangles"]),
+                                       _abi.ptr(out["degree_hist"]), _abi.ptr(out["clustering_hist"]),
+                                       _abi.ptr(out["n_edges"]), _abi.ptr(out["n_triangles"]), _abi.ptr(ws), ws_bytes,
+                                       _abi.stream_ptr(dev)), "gnf_graph_stats")
+    d = out["degree"].to(torch.float64)
+    pairs = d * (d - 1.0)
+    out["clustering"] = torch.where(pairs > 0, 2.0 * out["triangles"].to(torch.float64) / pairs.clamp(min=1.0),
+                                    torch.zeros_like(pairs))
+    return out
+
+
+def _hist_mmd_sums(hists_a, hists_b, kernel, sigma, distance_scaling):
+    if kernel not in _KERNELS:
+        raise ValueError(f"kernel={kernel!r}: one of {sorted(_KERNELS)}")
+    lib = _abi.lib()
+    for h in (hists_a, hists_b):
+        if not isinstance(h, torch.Tensor) or h.device.type != "cuda":
+            raise _abi.GnfError("hist_mmd runs on a HIP device only (no CPU path)")
+        if h.dim() != 2:
+            raise ValueError(f"hist_mmd takes [rows, bins] histograms, got shape {tuple(h.shape)}")
+    dev = hists_a.device
+    ha = hists_a.to(torch.int32).contiguous()
+    hb = hists_b.to(device=dev, dtype=torch.int32).contiguous()
+    a, la = int(ha.shape[0]), int(ha.shape[1])
+    b, lb = int(hb.shape[0]), int(hb.shape[1])
+    out5 = torch.empty(5, dtype=torch.float64, device=dev)
+    ws_bytes = lib.gnf_hist_mmd_workspace_bytes(a, b)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_hist_mmd_f64(_abi.ptr(ha), a, la, la, _abi.ptr(hb), b, lb, lb, _KERNELS[kernel], float(sigma),
+                                        float(distance_scaling), _abi.ptr(out5), _abi.ptr(ws), ws_bytes,
+                                        _abi.stream_ptr(dev)), "gnf_hist_mmd_f64")
+    return out5
+
+
+def hist_mmd(hists_a, hists_b, kernel="gaussian_emd", sigma=1.0, distance_scaling=1.0):
+    """MMD^2 of two sets of histograms (int32 [a, La] and [b, Lb] on the device; the narrower set reads as zero-padded), as a
+    0-d float64 device tensor: sum_AA / cnt_a^2 + sum_BB / cnt_b^2 - 2 sum_AB / (cnt_a cnt_b) with the Gaussian kernel
+    exp(-W^2 / (2 sigma^2)) over W = the 1-D earth mover's distance of the normalised rows divided by distance_scaling
+    ("gaussian_emd") or their total variation ("gaussian_tv") - the biased V-statistic, diagonals in, as in GraphRNN's
+    evaluation.  All-zero rows (graphs without nodes) are left out.  Raises ValueError when a set has no other row: reading
+    the two counts is the call's only copy to the host."""
+    out5 = _hist_mmd_sums(hists_a, hists_b, kernel, sigma, distance_scaling)
+    cnt_a, cnt_b = out5[3:5].tolist()
+    if cnt_a < 1 or cnt_b < 1:
+        raise ValueError(f"hist_mmd: {int(cnt_a)} / {int(cnt_b)} non-empty histograms in the two sets; both need one")
+    return out5[0] / (out5[3] * out5[3]) + out5[1] / (out5[4] * out5[4]) - 2.0 * out5[2] / (out5[3] * out5[4])
+
+
+def evaluate_generated(generated, reference):
+    """Degree and clustering MMD^2 of a generated batch against a reference batch: two GraphsTuples, or two results of
+    graph_stats (clustering_hist with 100 bins).  Degree: EMD kernel, sigma 1, distance_scaling 1.  Clustering: 100 bins,
+    EMD kernel, sigma 0.1, distance_scaling 100.  Returns {"degree_mmd", "clustering_mmd"}, 0-d float64 device tensors."""
+    stats = [s if isinstance(s, dict) else graph_stats(s, clustering_bins=100) for s in (generated, reference)]
+    for s in stats:
+        if int(s["clustering_hist"].shape[1]) != 100:
+            raise ValueError(f"evaluate_generated needs 100 clustering bins, got {int(s['clustering_hist'].shape[1])}")
+    return {"degree_mmd": hist_mmd(stats[0]["degree_hist"], stats[1]["degree_hist"], "gaussian_emd", 1.0, 1.0),
+            "clustering_mmd": hist_mmd(stats[0]["clustering_hist"], stats[1]["clustering_hist"], "gaussian_emd", 0.1, 100.0)}

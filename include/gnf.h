@@ -387,6 +387,53 @@ int gnf_adj_edges_fill(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_
                        int64_t edge_capacity, int32_t* senders, int32_t* receivers, const void* ws, size_t ws_bytes,
                        gnf_stream_t stream);
 
+/* Added within ABI v10 (new entry points only: no existing signature or struct changed, GNF_ABI_VERSION stays 10).
+ * Scoring generated graphs on the device: degree / triangle counts, per-graph degree and clustering-coefficient histograms
+ * and the MMD of two histogram sets - the evaluation that follows generation in GraphRNN-style work.  The reference has no
+ * counterpart: it pickles the generated graphs (generate_graphs.py:68-84) and leaves scoring to outside code.
+ * Graph model: every graph is read as UNDIRECTED and SIMPLE - self loops are ignored (the flow's datasets carry one per
+ * node), duplicate edges count once, an edge given in one direction only counts in both, sender order inside a CSR row
+ * does not matter.  csr is the receiver-sorted CSR of the batch (gnf_build_csr, or the one gnf_adj_edges_* produce);
+ * csr->node_offsets / csr->n_graphs are REQUIRED (GNF_EINVAL without them).
+ *   degree[i], triangles[i]   int32 [n_nodes]: neighbours of node i, triangles through node i
+ *   degree_hist[g][d]         int32 [n_graphs][max_nodes_per_graph]: nodes of graph g with degree d (d <= n_g - 1)
+ *   clustering_hist[g][bin]   int32 [n_graphs][clustering_bins]: nodes of graph g by local clustering coefficient
+ *                             c = 2 T / (d (d - 1)); NORMATIVE, exact 64-bit integer arithmetic: bin = 0 for d < 2, else
+ *                             min(bins - 1, (2 T bins) / (d (d - 1))) - floor(c bins) on the exact rational, c = 1 in the last
+ *                             bin.  Where numpy.histogram's float rounding of a bin edge disagrees, this definition wins.
+ *   n_edges[g], n_triangles[g] int64 [n_graphs]: sum deg / 2 and sum tri / 3 of graph g
+ * All outputs are written (the call zeroes what it accumulates into); integer atomics only, so the result is deterministic.
+ * max_nodes_per_graph: any upper bound on n_node, at most 65536 (a node's triangle count must fit int32).  A graph larger
+ * than the bound is the caller's error, as for gnf_adj_edges_*: its surplus rows and edges are dropped, nothing outside the
+ * arrays is touched.  ws: gnf_graph_stats_workspace_bytes (a host computation: one 64-bit word per (node, 64 graph-local
+ * columns) and one int32 per node).
+ * GNF_ESHAPE: clustering_bins < 1, max_nodes_per_graph < 0 or > 65536 (or 0 with nodes); GNF_EINVAL: null pointers, missing
+ * node_offsets; GNF_EWORKSPACE: short workspace - all before any launch.  n_graphs == 0: GNF_OK, nothing written.
+ * Asynchronous on `stream`, no host synchronisation, capturable. */
+size_t gnf_graph_stats_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph);
+int gnf_graph_stats(const GnfCsr* csr, int32_t max_nodes_per_graph, int32_t clustering_bins,
+                    int32_t* degree, int32_t* triangles,          /* [n_nodes] */
+                    int32_t* degree_hist, int32_t* clustering_hist, /* [n_graphs][max_nodes] / [n_graphs][bins] */
+                    int64_t* n_edges, int64_t* n_triangles,        /* [n_graphs] */
+                    void* ws, size_t ws_bytes, gnf_stream_t stream);
+/* MMD block sums of two sets of int32 histograms A [a][La] (row stride lda) and B [b][Lb] (row stride ldb); the narrower set
+ * reads as zero-padded to L = max(La, Lb).  Every row is normalised to a pmf in fp64; rows with sum <= 0 (a graph without
+ * nodes) are excluded.  For rows x, y:
+ *   GNF_MMD_GAUSSIAN_EMD  W = (1 / distance_scaling) sum_{k=0}^{L-2} |sum_{i<=k} (x_i - y_i)|  (1-D earth mover's distance)
+ *   GNF_MMD_GAUSSIAN_TV   W = 1/2 sum_i |x_i - y_i|                                               (distance_scaling unused)
+ *   k(x, y) = exp(-W^2 / (2 sigma^2))
+ * out5 (device fp64, written) = { sum_{x,y in A} k, sum_{x,y in B} k, sum_{x in A, y in B} k, cnt_a, cnt_b } over the rows
+ * that were kept, diagonals included: MMD^2 = out[0] / cnt_a^2 + out[1] / cnt_b^2 - 2 out[2] / (cnt_a cnt_b), the biased
+ * V-statistic.  No floating-point atomics: per-workgroup partials in ws, one fixed-order final sum - two calls give the same
+ * bits.  ws: gnf_hist_mmd_workspace_bytes(a, b) (host computation).  GNF_ESHAPE: negative sizes, La > lda, Lb > ldb;
+ * GNF_EINVAL: bad kernel, sigma <= 0, distance_scaling <= 0, null pointers; GNF_EWORKSPACE.  a + b == 0: five zeros. */
+enum GnfMmdKernel { GNF_MMD_GAUSSIAN_EMD = 0, GNF_MMD_GAUSSIAN_TV = 1 };
+size_t gnf_hist_mmd_workspace_bytes(int64_t a, int64_t b);
+int gnf_hist_mmd_f64(const int32_t* ha, int64_t a, int64_t lda, int32_t La,
+                     const int32_t* hb, int64_t b, int64_t ldb, int32_t Lb,
+                     int32_t kernel, double sigma, double distance_scaling,
+                     double* out5, void* ws, size_t ws_bytes, gnf_stream_t stream);
+
 /* ---- training step ---------------------------------------------------------------
  * Replaces optimizer.compute_gradients(total_loss) (run_grevnet.py:361-362) for
  *   total_loss = -(sum_n log N(z_n; 0, I) + log_det_jacobian)           (run_grevnet.py:291-295)
