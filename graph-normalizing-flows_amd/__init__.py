@@ -4,11 +4,11 @@ log-det hot path of jliu/graph-normalizing-flows behind the reference's own gnn.
 Import as `gnf_amd` (the directory name has a hyphen; gnf_amd.py at the repo root is the loader):
     from gnf_amd.gnn import GRevNet, avg_then_mlp_gnn, make_mlp_model, leaky_relu
     from gnf_amd.flow import log_prob_per_graph, sample, decode_graphs, generate_graphs
-    from gnf_amd.graph_stats import graph_stats, hist_mmd, evaluate_generated
+    from gnf_amd.graph_stats import graph_stats, hist_mmd, evaluate_generated, graph_orbits, orbit_mmd
 """
 from . import _abi
 from .graphs import GraphsTuple, data_dicts_to_graphs_tuple, build_csr_host, csr_of, seed_csr_cache
-from .graph_stats import graph_stats, hist_mmd, evaluate_generated
+from .graph_stats import graph_stats, hist_mmd, evaluate_generated, graph_orbits, orbit_mmd
 
 __all__ = ["GraphsTuple", "data_dicts_to_graphs_tuple", "build_csr_host", "csr_of", "seed_csr_cache", "_abi",
-           "graph_stats", "hist_mmd", "evaluate_generated"]
+           "graph_stats", "hist_mmd", "evaluate_generated", "graph_orbits", "orbit_mmd"]

@@ -137,7 +137,20 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/gnf_graph_orbits.h (included by gnf.h, added within ABI v10): 4-node orbit counts of a batch of graphs and the MMD
+# of two sets of mean orbit vectors.  A table of its own, as the header is a file of its own: EXPORTED_SYMBOLS mirrors the
+# prototypes written in gnf.h itself, ORBIT_SYMBOLS those of gnf_graph_orbits.h; lib() binds both.
+_ORBIT_SIGNATURES = {
+    "gnf_graph_orbits_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_graph_orbits": (C.c_int, [C.POINTER(GnfCsr), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "gnf_vec_mmd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gnf_vec_mmd_i64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                  C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+ORBIT_SYMBOLS = tuple(_ORBIT_SIGNATURES)
 
 _lib = None
 
@@ -151,7 +164,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -28,49 +28,11 @@
 // and k = exp(-W^2 / (2 sigma^2)), added to the AA / BB / AB block sum (diagonal pairs once, off-diagonal pairs inside a block
 // twice, cross pairs once).  No floating-point atomics: workgroup p owns row p's pairs and leaves one fp64 partial triple in the
 // workspace, a single workgroup adds the partials up in a fixed order - two calls give the same bits.
-#include "gnf_common.h"
+#include "gnf_graph_bitmap.h"
 
 namespace gnf {
 
 static constexpr int kStatsMaxNodes = 65536;   // tri_i <= C(n - 1, 2) must fit int32
-static constexpr int kStatsGridMax = 1 << 16;  // workgroups of the grid-stride kernels
-
-// caller-owned workspace of gnf_graph_stats (host only): bitmap uint64 [N][W] | graph id of every node int32 [N]
-struct StatsWs {
-    size_t bitmap, gid, total;
-    int64_t W;
-};
-static StatsWs stats_ws(int64_t n_nodes, int32_t max_nodes) {
-    StatsWs L;
-    L.W = ((int64_t)max_nodes + 63) / 64;
-    L.bitmap = 0;
-    L.gid = (size_t)n_nodes * (size_t)L.W * sizeof(uint64_t);
-    L.total = (L.gid + (size_t)n_nodes * sizeof(int32_t) + 7) / 8 * 8;
-    return L;
-}
-
-// graph of node i: the last g with node_offsets[g] <= i (empty graphs share their offset with the next one), -1 when i lies
-// past node_offsets[n_graphs].  n0 / ng: its first row and size, cut to the node buffer and to the bitmap's columns - offsets
-// that do not describe the batch give wrong numbers, never an access outside the arrays.
-__device__ __forceinline__ int stats_graph_of(const int32_t* __restrict__ off, int64_t n_graphs, int64_t i) {
-    int64_t lo = 0, hi = n_graphs + 1;   // first index with off[idx] > i
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)off[mid] <= i) lo = mid + 1; else hi = mid;
-    }
-    const int64_t g = lo - 1;
-    return (g >= 0 && g < n_graphs) ? (int)g : -1;
-}
-__device__ __forceinline__ void stats_graph_range(const int32_t* __restrict__ off, int g, int64_t n_nodes, int max_nodes,
-                                                  int64_t& n0, int& ng) {
-    n0 = off[g];
-    int64_t n1 = off[g + 1];
-    if (n0 < 0) n0 = 0;
-    if (n1 > n_nodes) n1 = n_nodes;
-    int64_t c = n1 - n0;
-    if (c > max_nodes) c = max_nodes;
-    ng = c > 0 ? (int)c : 0;
-}
 
 // one wave per CSR row i: lanes take its entries 64 at a time.  An entry whose endpoints are not both inside the graph's
 // [n0, n0 + ng) window is dropped (never an access outside the bitmap).
@@ -98,11 +60,6 @@ __global__ __launch_bounds__(256) void k_stats_bitmap(const int32_t* __restrict_
             atomicOr(&bitmap[(n0 + lj) * W + (li >> 6)], 1ull << (li & 63));
         }
     }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return __shfl(v, 0, 64);
 }
 
 // one wave = one workgroup per node.  LDS: row_i [W] words | queue [128] graph-local neighbour ids.
@@ -205,11 +162,6 @@ __device__ __forceinline__ const int32_t* mmd_row(const MmdSets& s, int64_t r, i
     return s.hb + (r - s.a) * s.ldb;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return __shfl(v, 0, 64);
-}
-
 __global__ __launch_bounds__(256) void k_mmd_rowsums(MmdSets s, double* __restrict__ inv) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t n = s.a + s.b;
@@ -288,11 +240,6 @@ __global__ __launch_bounds__(256) void k_mmd_final(int64_t a, int64_t b, const d
         __syncthreads();
     }
     if (threadIdx.x < 5) out5[threadIdx.x] = sh[threadIdx.x][0];
-}
-
-static unsigned stats_grid(int64_t items) {
-    if (items < 1) items = 1;
-    return (unsigned)(items > kStatsGridMax ? kStatsGridMax : items);
 }
 
 }  // namespace gnf

@@ -4,6 +4,9 @@ GraphRNN-style evaluation compares generated graphs to held-out ones by the MMD 
 histograms.  The reference stops at pickling the graphs (generate_graphs.py:68-84); here the edge lists never leave the
 device: graph_stats (gnf_graph_stats) turns a batch into per-node degrees / triangle counts and per-graph histograms,
 hist_mmd (gnf_hist_mmd_f64) reduces two histogram sets to one MMD^2, evaluate_generated does both for two batches.
+The third statistic of that evaluation, orbit counts: graph_orbits (gnf_graph_orbits) counts the 15 node orbits of the
+graphlets on 2, 3 and 4 nodes, orbit_mmd (gnf_vec_mmd_i64) is the MMD^2 of two sets of per-graph mean orbit vectors under a
+Gaussian kernel; evaluate_generated(..., orbits=True) adds it.
 Every graph is read as undirected and simple (self loops ignored, duplicates once, one direction is enough).  HIP only:
 CPU tensors raise GnfError.
 """
@@ -16,6 +19,30 @@ from . import _abi
 _KERNELS = {"gaussian_emd": _abi.GNF_MMD_GAUSSIAN_EMD, "gaussian_tv": _abi.GNF_MMD_GAUSSIAN_TV}
 MAX_NODES_PER_GRAPH = 65536   # a node's triangle count must fit int32
 STATS_KEYS = ("degree", "triangles", "clustering", "degree_hist", "clustering_hist", "n_edges", "n_triangles")
+ORBIT_MAX_NODES_PER_GRAPH = 8192   # gnf_graph_orbits: the cost per node grows with n_g + d_i d_mean
+N_ORBITS = 15
+ORBIT_KEYS = ("orbits", "orbit_sums", "orbit_mean", "n_node")
+
+
+def _node_bound(graph, max_nodes_per_graph, n_node_host, limit):
+    """Columns of the adjacency bitmap: max_nodes_per_graph, else the largest graph (n_node_host, else n_node read once)."""
+    n = int(graph.nodes.shape[0])
+    b = int(graph.n_node.shape[0])
+    if n_node_host is not None:
+        sizes = [int(v) for v in n_node_host]
+        if len(sizes) != b or sum(sizes) != n:
+            raise ValueError(f"n_node_host describes {len(sizes)} graphs / {sum(sizes)} nodes, the batch has {b} / {n}")
+    elif max_nodes_per_graph is None:
+        sizes = graph.n_node.cpu().tolist()
+    else:
+        sizes = None
+    largest = (max(sizes) if sizes else 0) if sizes is not None else None
+    cap = int(max_nodes_per_graph) if max_nodes_per_graph is not None else largest
+    if largest is not None and cap < largest:   # the bitmap holds `cap` columns per row: a smaller bound would drop edges
+        raise ValueError(f"max_nodes_per_graph={cap} is below the largest graph of the batch ({largest} nodes)")
+    if cap > limit:
+        raise ValueError(f"max_nodes_per_graph={cap} exceeds {limit}")
+    return cap
 
 
 def graph_stats(graph, max_nodes_per_graph=None, n_node_host=None, clustering_bins=100):
@@ -37,20 +64,7 @@ def graph_stats(graph, max_nodes_per_graph=None, n_node_host=None, clustering_bi
     n = int(graph.nodes.shape[0])
     b = int(graph.n_node.shape[0])
     bins = int(clustering_bins)
-    if n_node_host is not None:
-        sizes = [int(v) for v in n_node_host]
-        if len(sizes) != b or sum(sizes) != n:
-            raise ValueError(f"n_node_host describes {len(sizes)} graphs / {sum(sizes)} nodes, the batch has {b} / {n}")
-    elif max_nodes_per_graph is None:
-        sizes = graph.n_node.cpu().tolist()
-    else:
-        sizes = None
-    largest = (max(sizes) if sizes else 0) if sizes is not None else None
-    cap = int(max_nodes_per_graph) if max_nodes_per_graph is not None else largest
-    if largest is not None and cap < largest:   # the bitmap holds `cap` columns per row: a smaller bound would drop edges
-        raise ValueError(f"max_nodes_per_graph={cap} is below the largest graph of the batch ({largest} nodes)")
-    if cap > MAX_NODES_PER_GRAPH:
-        raise ValueError(f"max_nodes_per_graph={cap} exceeds {MAX_NODES_PER_GRAPH}")
+    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
     if bins < 1:
         raise ValueError(f"clustering_bins={bins}")
     csr = csr_of(graph)
@@ -113,13 +127,99 @@ def hist_mmd(hists_a, hists_b, kernel="gaussian_emd", sigma=1.0, distance_scalin
     return out5[0] / (out5[3] * out5[3]) + out5[1] / (out5[4] * out5[4]) - 2.0 * out5[2] / (out5[3] * out5[4])
 
 
-def evaluate_generated(generated, reference):
+def graph_orbits(graph, max_nodes_per_graph=None, n_node_host=None):
+    """Orbit counts of every graph of a GraphsTuple, as a dict of device tensors:
+      "orbits"      int64 [N, 15]: induced connected subgraphs on 2, 3 and 4 nodes through each node, by the node's orbit
+                    (Przulj's numbering, as ORCA: 0 edge, 1-2 path, 3 triangle, 4-5 4-path, 6-7 star, 8 4-cycle, 9-11 tailed
+                    triangle, 12-13 chorded 4-cycle, 14 complete graph); column 0 is the degree, column 3 the triangles
+      "orbit_sums"  int64 [B, 15]: the columns summed over each graph
+      "orbit_mean"  float64 [B, 15]: orbit_sums / n_node, the graph's orbit vector; 0 for a graph without nodes
+      "n_node"      int32 [B]: the batch's sizes (what orbit_mmd divides by)
+    The CSR comes from graphs.csr_of: on the result of decode_graphs / generate_graphs no gnf_build_csr runs.  As for
+    graph_stats, with max_nodes_per_graph (any upper bound on n_node, at most 8192) or n_node_host nothing is copied to the
+    host and nothing synchronises, so the call can be captured; otherwise n_node is read once."""
+    from .graphs import csr_desc, csr_of
+    lib = _abi.lib()
+    dev = graph.senders.device
+    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
+        raise _abi.GnfError("graph_orbits runs on a HIP device only (no CPU path)")
+    n = int(graph.nodes.shape[0])
+    b = int(graph.n_node.shape[0])
+    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, ORBIT_MAX_NODES_PER_GRAPH)
+    csr = csr_of(graph)
+    desc = csr_desc(graph, csr, node_offsets=True)
+    out = {"orbits": torch.empty((n, N_ORBITS), dtype=torch.int64, device=dev),
+           "orbit_sums": torch.empty((b, N_ORBITS), dtype=torch.int64, device=dev)}
+    ws_bytes = lib.gnf_graph_orbits_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_graph_orbits(C.byref(desc), cap, _abi.ptr(out["orbits"]), N_ORBITS, _abi.ptr(out["orbit_sums"]),
+                                        _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_graph_orbits")
+    out["n_node"] = graph.n_node.to(torch.int32)
+    out["orbit_mean"] = out["orbit_sums"].to(torch.float64) / out["n_node"].clamp(min=1).to(torch.float64).unsqueeze(1)
+    return out
+
+
+def _orbit_set(x, dev=None):
+    """(orbit_sums int64 [rows, L] contiguous, n_node int32 [rows]) of a graph_orbits result or an (orbit_sums, n_node) pair"""
+    sums, cnt = (x["orbit_sums"], x["n_node"]) if isinstance(x, dict) else x
+    for v in (sums, cnt):
+        if not isinstance(v, torch.Tensor) or v.device.type != "cuda":
+            raise _abi.GnfError("orbit_mmd runs on a HIP device only (no CPU path)")
+    if sums.dim() != 2 or cnt.dim() != 1 or int(cnt.shape[0]) != int(sums.shape[0]):
+        raise ValueError(f"orbit_mmd takes [rows, L] sums with [rows] sizes, got {tuple(sums.shape)} and {tuple(cnt.shape)}")
+    dev = sums.device if dev is None else dev
+    return sums.to(device=dev, dtype=torch.int64).contiguous(), cnt.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _orbit_mmd_sums(orbits_a, orbits_b, sigma):
+    lib = _abi.lib()
+    xa, ca = _orbit_set(orbits_a)
+    dev = xa.device
+    xb, cb = _orbit_set(orbits_b, dev)
+    a, b, width = int(xa.shape[0]), int(xb.shape[0]), int(xa.shape[1])
+    if int(xb.shape[1]) != width:
+        raise ValueError(f"orbit_mmd: vectors of {width} and {int(xb.shape[1])} entries")
+    out5 = torch.empty(5, dtype=torch.float64, device=dev)
+    ws_bytes = lib.gnf_vec_mmd_workspace_bytes(a, b)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_vec_mmd_i64(_abi.ptr(xa), _abi.ptr(ca), a, width, _abi.ptr(xb), _abi.ptr(cb), b, width, width,
+                                       float(sigma), _abi.ptr(out5), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                   "gnf_vec_mmd_i64")
+    return out5
+
+
+def orbit_mmd(orbits_a, orbits_b, sigma=30.0):
+    """MMD^2 of the orbit vectors (orbit_sums / n_node, not normalised further) of two sets of graphs - two results of
+    graph_orbits, or two (orbit_sums int64 [rows, L], n_node int32 [rows]) pairs on the device - under the Gaussian kernel
+    exp(-|x - y|^2 / (2 sigma^2)), sigma = 30 as in GraphRNN's orbit evaluation: the same biased V-statistic as hist_mmd, as
+    a 0-d float64 device tensor.  Graphs without nodes are left out.  Two identical sets give exactly 0.  Raises ValueError
+    when a set has no other graph: reading the two counts is the call's only copy to the host."""
+    out5 = _orbit_mmd_sums(orbits_a, orbits_b, sigma)
+    cnt_a, cnt_b = out5[3:5].tolist()
+    if cnt_a < 1 or cnt_b < 1:
+        raise ValueError(f"orbit_mmd: {int(cnt_a)} / {int(cnt_b)} non-empty graphs in the two sets; both need one")
+    return out5[0] / (out5[3] * out5[3]) + out5[1] / (out5[4] * out5[4]) - 2.0 * out5[2] / (out5[3] * out5[4])
+
+
+def evaluate_generated(generated, reference, orbits=False):
     """Degree and clustering MMD^2 of a generated batch against a reference batch: two GraphsTuples, or two results of
     graph_stats (clustering_hist with 100 bins).  Degree: EMD kernel, sigma 1, distance_scaling 1.  Clustering: 100 bins,
-    EMD kernel, sigma 0.1, distance_scaling 100.  Returns {"degree_mmd", "clustering_mmd"}, 0-d float64 device tensors."""
-    stats = [s if isinstance(s, dict) else graph_stats(s, clustering_bins=100) for s in (generated, reference)]
+    EMD kernel, sigma 0.1, distance_scaling 100.  Returns {"degree_mmd", "clustering_mmd"}, 0-d float64 device tensors.
+    orbits=True adds "orbit_mmd" (orbit_mmd, sigma 30); dicts passed instead of GraphsTuples must then also hold the
+    result of graph_orbits ({**graph_stats(g), **graph_orbits(g)})."""
+    inputs = (generated, reference)
+    stats = [s if isinstance(s, dict) else graph_stats(s, clustering_bins=100) for s in inputs]
     for s in stats:
         if int(s["clustering_hist"].shape[1]) != 100:
             raise ValueError(f"evaluate_generated needs 100 clustering bins, got {int(s['clustering_hist'].shape[1])}")
-    return {"degree_mmd": hist_mmd(stats[0]["degree_hist"], stats[1]["degree_hist"], "gaussian_emd", 1.0, 1.0),
-            "clustering_mmd": hist_mmd(stats[0]["clustering_hist"], stats[1]["clustering_hist"], "gaussian_emd", 0.1, 100.0)}
+    out = {"degree_mmd": hist_mmd(stats[0]["degree_hist"], stats[1]["degree_hist"], "gaussian_emd", 1.0, 1.0),
+           "clustering_mmd": hist_mmd(stats[0]["clustering_hist"], stats[1]["clustering_hist"], "gaussian_emd", 0.1, 100.0)}
+    if orbits:
+        for s in inputs:
+            if isinstance(s, dict) and not ("orbit_sums" in s and "n_node" in s):
+                raise ValueError("evaluate_generated(orbits=True) on a dict needs the result of graph_orbits in it")
+        sets = [s if isinstance(s, dict) else graph_orbits(s) for s in inputs]
+        out["orbit_mmd"] = orbit_mmd(sets[0], sets[1], 30.0)
+    return out

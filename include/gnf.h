@@ -504,6 +504,10 @@ size_t gnf_clip_workspace_bytes(int32_t n_tensors);
 int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, float clip_norm, void* ws, size_t ws_bytes,
                          gnf_stream_t stream);
 
+/* Added within ABI v10: orbit counts of a batch of graphs and the MMD of mean orbit vectors (gnf_graph_orbits.h) - part of
+ * this interface, kept in a header of its own. */
+#include "gnf_graph_orbits.h"
+
 #ifdef __cplusplus
 }
 #endif
