@@ -70,6 +70,11 @@ class GnfFlow(C.Structure):
                 ("mlp_stash", C.c_void_p), ("mlp_stash_bytes", C.c_size_t)]
 
 
+class GnfAdjLossSpec(C.Structure):   # include/gnf_adj_loss.h
+    _fields_ = [("temp", C.c_float), ("shift", C.c_float), ("scale_by_sqrt_dim", C.c_int32), ("soft_labels", C.c_int32),
+                ("label_epsilon", C.c_float), ("abs_tol", C.c_float)]
+
+
 _SIGNATURES = {
     "gnf_abi_version": (C.c_int, []),
     "gnf_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
@@ -149,8 +154,18 @@ _ORBIT_SIGNATURES = {
                                   C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/gnf_adj_loss.h (included by gnf.h, added within ABI v10): the adjacency reconstruction loss of embeddings against a
+# true batch, its edge-error counts and its gradient.  A table of its own for the same reason.
+_ADJ_LOSS_SIGNATURES = {
+    "gnf_adj_loss_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_adj_loss_f32": (C.c_int, [C.POINTER(GnfCsr), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(GnfAdjLossSpec),
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 ORBIT_SYMBOLS = tuple(_ORBIT_SIGNATURES)
+ADJ_LOSS_SYMBOLS = tuple(_ADJ_LOSS_SIGNATURES)
 
 _lib = None
 
@@ -164,7 +179,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

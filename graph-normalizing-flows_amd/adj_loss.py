@@ -1,0 +1,139 @@
+"""How well do embeddings reconstruct the graph they belong to: loss.py's binary_loss, its edge-error counts and the gradient
+of the loss with respect to the embeddings, on the device (gnf_adj_loss_f32, include/gnf_adj_loss.h).
+
+The reference builds a dense [N, N] true adjacency, a dense distance_fn(nodes) and their element-wise cross-entropy
+(loss.py:162-188), counts wrong entries on those matrices (loss.py:88-116) and lets tf.gradients differentiate through
+them.  Here the embeddings meet the true graph's receiver-sorted CSR pair by pair inside each graph; the arithmetic of a pair
+is flow.pred_adj's, so the verdict on an edge agrees with `pred_adj > 0.5` and flow.decode_graphs bit for bit.
+HIP only: CPU tensors raise GnfError.
+
+Unpinned upstream facts this relies on: tf.keras.backend.binary_crossentropy of TF 1.x clips the probability to
+[1e-7, 1 - 1e-7] (Keras' epsilon, K.epsilon() = 1e-7), converts it to a logit and applies sigmoid cross-entropy with logits;
+tf.clip_by_value passes no gradient where it clips.
+"""
+import ctypes as C
+
+import torch
+
+from . import _abi
+from .flow import scaled_hacky_sigmoid_l2
+from .graph_stats import _node_bound
+
+MAX_NODES_PER_GRAPH = 65536
+RESULT_KEYS = ("sum_loss", "mean_loss", "loss_per_graph", "false_positive_pairs", "false_negative_pairs")
+
+
+def hacky_sigmoid_l2(*_a, **_k):
+    """Token for the distance function of loss.py:36-42, sigmoid(10 * (1 - ||z_i - z_j||^2)); the arithmetic runs inside
+    gnf_adj_loss_f32."""
+    raise NotImplementedError("token only: pass it as distance_fn to binary_loss")
+
+
+class sigmoid_l2:
+    """Token for loss.py:56-62 with its two parameters bound, sigmoid(temp * (shift - ||z_i - z_j||^2 / sqrt(D))):
+    binary_loss(..., distance_fn=sigmoid_l2(3.0, 2.0))."""
+
+    def __init__(self, temp, shift):
+        self.temp, self.shift = float(temp), float(shift)
+
+    def __repr__(self):
+        return f"sigmoid_l2(temp={self.temp}, shift={self.shift})"
+
+
+def _distance_params(distance_fn):
+    """(temp, shift, scale_by_sqrt_dim) of a distance-function token"""
+    if distance_fn is scaled_hacky_sigmoid_l2:
+        return 10.0, 1.0, 1
+    if distance_fn is hacky_sigmoid_l2:
+        return 10.0, 1.0, 0
+    if isinstance(distance_fn, sigmoid_l2):
+        return distance_fn.temp, distance_fn.shift, 1
+    raise NotImplementedError("binary_loss supports distance_fn = scaled_hacky_sigmoid_l2 (loss.py:45-53), hacky_sigmoid_l2 "
+                              "(loss.py:36-42) or sigmoid_l2(temp, shift) (loss.py:56-62)")
+
+
+def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_soft_labels=False, epsilon=0.1, grad=None,
+                abs_tol=0.5, max_nodes_per_graph=None, n_node_host=None):
+    """loss.py:162-188 with the counts of loss.py:88-116 and, on request, dL/dnodes: gnn_output.nodes are the embeddings,
+    graph_phs gives the true topology and n_node.  Returns a dict of device tensors:
+      "sum_loss", "mean_loss"     0-d float64: the masked cross-entropy summed over the ordered pairs (i, j), i != j, inside each
+                                  graph, and that sum / (N^2 - N) with N the batch's node total (0 for N < 2)
+      "loss_per_graph"            float64 [B]: the terms of sum_loss by graph
+      "false_positive_pairs", "false_negative_pairs"  int64 [B]: ordered pairs with p - a > abs_tol / a - p > abs_tol against the
+                                  hard label a (the helpers below halve them as loss.py does)
+      "grad_nodes"                float32 [N, D], with grad="sum" (d sum_loss / d nodes) or grad="mean" (d mean_loss / d nodes)
+    The dense true_adj, pred_adj and ce_loss the reference also returns are NOT produced.  Per pair: p = sigmoid(u),
+    ce = softplus(u_c) - t u_c with u_c = u clipped to +-log((1 - 1e-7) / 1e-7) - Keras' binary_crossentropy - and no gradient
+    where the clip is active: a true edge whose endpoints lie far apart gets none, as in the reference.  t is the hard label,
+    or with use_soft_labels 1 - epsilon / epsilon.  Duplicate edges count once (the reference counts their multiplicity; the
+    datasets hold none); self loops and edges into another graph are ignored.
+    The CSR comes from graphs.csr_of(graph_phs): on the result of decode_graphs no gnf_build_csr runs.  With
+    max_nodes_per_graph (any upper bound on n_node, at most 65536) or n_node_host (the sizes as a host sequence) nothing is
+    copied to the host and nothing synchronises, so the call can be captured; otherwise n_node is read once."""
+    from .graphs import csr_desc, csr_of
+    temp, shift, by_sqrt = _distance_params(distance_fn)
+    if grad not in (None, "sum", "mean"):
+        raise ValueError(f"grad={grad!r}: None, 'sum' or 'mean'")
+    if not 0.0 <= float(epsilon) <= 0.5:
+        raise ValueError(f"epsilon={epsilon}: a soft label lies in [0, 0.5]")
+    if not float(abs_tol) >= 0.0:
+        raise ValueError(f"abs_tol={abs_tol}")
+    z = gnn_output.nodes
+    n = int(z.shape[0])
+    if int(graph_phs.nodes.shape[0]) != n:
+        raise ValueError(f"gnn_output has {n} nodes, graph_phs {int(graph_phs.nodes.shape[0])}")
+    lib = _abi.lib()
+    dev = z.device
+    if dev.type != "cuda" or graph_phs.senders.device.type != "cuda" or graph_phs.n_node.device.type != "cuda":
+        raise _abi.GnfError("binary_loss runs on a HIP device only (no CPU path)")
+    b = int(graph_phs.n_node.shape[0])
+    cap = _node_bound(graph_phs, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
+    z = z.to(torch.float32)
+    if z.dim() != 2 or z.shape[1] < 1:
+        raise ValueError(f"binary_loss takes [N, D] embeddings with D >= 1, got shape {tuple(z.shape)}")
+    if z.stride(1) != 1:
+        z = z.contiguous()
+    d = int(z.shape[1])
+    ld = z.stride(0) if n > 1 else max(int(z.stride(0)), d)   # (torch reports any stride for a dimension of 0 or 1 rows)
+    csr = csr_of(graph_phs)
+    desc = csr_desc(graph_phs, csr, node_offsets=True)
+    spec = _abi.GnfAdjLossSpec(temp, shift, by_sqrt, int(bool(use_soft_labels)), float(epsilon), float(abs_tol))
+    sums2 = torch.empty(2, dtype=torch.float64, device=dev)
+    out = {"loss_per_graph": torch.empty(b, dtype=torch.float64, device=dev),
+           "false_positive_pairs": torch.empty(b, dtype=torch.int64, device=dev),
+           "false_negative_pairs": torch.empty(b, dtype=torch.int64, device=dev)}
+    g = torch.empty((n, d), dtype=torch.float32, device=dev) if grad else None
+    pairs = float(n) * float(n) - float(n)
+    grad_scale = 1.0 if grad != "mean" else (1.0 / pairs if n >= 2 else 0.0)
+    ws_bytes = lib.gnf_adj_loss_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_adj_loss_f32(C.byref(desc), _abi.ptr(z), ld, d, cap, C.byref(spec), _abi.ptr(out["loss_per_graph"]),
+                                        _abi.ptr(sums2), _abi.ptr(out["false_positive_pairs"]),
+                                        _abi.ptr(out["false_negative_pairs"]), _abi.ptr(g), d, grad_scale, _abi.ptr(ws),
+                                        ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_loss_f32")
+    out["sum_loss"], out["mean_loss"] = sums2[0], sums2[1]
+    if grad:
+        out["grad_nodes"] = g
+    return out
+
+
+# ---- loss.py:88-116 over the result dict: the reference's figures are the ordered-pair counts halved -------------------------
+def incorrect_edges_per_graph(result):
+    """loss.py:88-95: wrong entries of each graph's block, halved, int32 [B]"""
+    return ((result["false_positive_pairs"] + result["false_negative_pairs"]) // 2).to(torch.int32)
+
+
+def false_positive_edges(result):
+    """loss.py:104-106: 0-d float64"""
+    return result["false_positive_pairs"].sum().to(torch.float64) / 2.0
+
+
+def false_negative_edges(result):
+    """loss.py:109-111: 0-d float64"""
+    return result["false_negative_pairs"].sum().to(torch.float64) / 2.0
+
+
+def total_incorrect_edges(result):
+    """loss.py:114-116: 0-d float64"""
+    return (result["false_positive_pairs"].sum() + result["false_negative_pairs"].sum()).to(torch.float64) / 2.0

@@ -1,0 +1,377 @@
+// Adjacency reconstruction loss of embeddings against a true batch (include/gnf_adj_loss.h): binary_loss
+// (loss.py:162-188 of the reference), the edge-error counts (loss.py:88-116) and dL/dnodes, without the dense [N, N] true_adj /
+// pred_adj / ce_loss matrices the reference builds and differentiates through.
+//
+// True graph.  Two DIRECTED bitmaps in the layout of gnf_graph_stats.hip (one 64-bit word per (node, 64 graph-local columns)),
+// zeroed on the stream, then filled from the receiver-sorted CSR by one wave per row with 64-bit integer atomicOr: for an
+// entry (receiver i, sender j), i != j, both inside the graph's window,
+//   in [i]  bit (j - n0): a_ji - "senders into row i"        out[j]  bit (i - n0): a_ji - "receivers out of row j"
+// so a lane that works on the pair (i, j) finds a_ij in row i of `out` and a_ji in row i of `in`: both words of its own row.
+//
+// Pairs.  One workgroup per (graph, 16-row tile) walks the graph's columns in chunks of CJ (64, or 32 when that is what LDS
+// holds).  Pass A: a lane owns one column of the chunk and CJ / 16 rows of the tile; d2 is k_pred_adj's fmaf chain, u, p
+// are written as k_pred_adj writes them (same bits), then the two counts, the cross-entropy term (its three terms added in
+// fp64) and c_ij, which goes to LDS.  Pass B: lanes over (row, feature) add c_ij (z_i - z_j) over the chunk's columns into
+// the row's gradient, which the workgroup owns (written after the first chunk, plain read-modify-write after the others; no
+// atomics).  A column with c_ij = 0 - a clipped pair, the diagonal - is skipped, not multiplied: it adds exactly nothing, as in
+// the reference, even where an embedding is not finite.  Rows that no graph covers are zeroed by the bitmap kernel.
+// z_i (the tile) and z_j (the chunk) sit in LDS while 64 KB hold them; wider rows keep the tile only, then nothing
+// (same arithmetic in the same order, operands read from global memory).
+// Row sums (fp64 loss, int32 counts) leave through a fixed shuffle tree and go to the workspace; one wave per graph adds
+// its rows up, one wave the graphs: no floating-point atomics anywhere, two calls give the same bits.
+#include "gnf_graph_bitmap.h"
+
+namespace gnf {
+
+static constexpr int kAdjLossMaxNodes = 65536;   // a row's pair count fits int32; the grid's y extent stays below 65536
+static constexpr int kAdjTile = 16;
+static constexpr size_t kAdjLdsMax = 64 * 1024;
+// U = log((1 - 1e-7) / 1e-7): Keras' epsilon clip of the probability, seen from the logit
+static constexpr float kAdjClipU = 16.118095550958316f;
+
+// caller-owned workspace (host only): in uint64 [N][W] | out uint64 [N][W] | row loss double [N] | row fp int32 [N] | row fn int32 [N]
+struct AdjLossWs {
+    size_t in, out, row_loss, row_fp, row_fn, total;
+    int64_t W;
+};
+inline AdjLossWs adj_loss_ws(int64_t n_nodes, int32_t max_nodes) {
+    AdjLossWs L;
+    L.W = ((int64_t)max_nodes + 63) / 64;
+    const size_t bm = (size_t)n_nodes * (size_t)L.W * sizeof(uint64_t);
+    L.in = 0;
+    L.out = bm;
+    L.row_loss = 2 * bm;
+    L.row_fp = L.row_loss + (size_t)n_nodes * sizeof(double);
+    L.row_fn = L.row_fp + (size_t)n_nodes * sizeof(int32_t);
+    L.total = (L.row_fn + (size_t)n_nodes * sizeof(int32_t) + 7) / 8 * 8;
+    return L;
+}
+
+// one wave per CSR row i (receiver i): lanes take its entries 64 at a time.  An entry whose endpoints are not both inside the
+// graph's [n0, n0 + ng) window is dropped (never an access outside the bitmaps).  grad != NULL: rows outside every graph's
+// window get grad[i, 0:D) = 0 here (the pair kernel writes all the others).
+__global__ __launch_bounds__(256) void k_adj_loss_bitmap(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                         int64_t n_nodes, int64_t n_edges, const int32_t* __restrict__ off,
+                                                         int64_t n_graphs, int max_nodes, int64_t W,
+                                                         unsigned long long* __restrict__ in_bits,
+                                                         unsigned long long* __restrict__ out_bits,
+                                                         float* __restrict__ grad, int64_t ldg, int D) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_nodes; i += (int64_t)gridDim.x * 4) {
+        const int g = stats_graph_of(off, n_graphs, i);
+        int64_t n0 = 0;
+        int ng = 0;
+        if (g >= 0) stats_graph_range(off, g, n_nodes, max_nodes, n0, ng);
+        const int64_t li = i - n0;
+        if (g < 0 || li < 0 || li >= ng) {   // a row no tile of the pair kernel covers: its gradient is zero
+            if (grad)
+                for (int f = lane; f < D; f += 64) grad[i * ldg + f] = 0.f;
+            continue;
+        }
+        int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
+        if (e0 < 0) e0 = 0;
+        if (e1 > n_edges) e1 = n_edges;
+        for (int64_t e = e0 + lane; e < e1; e += 64) {
+            const int64_t lj = (int64_t)col[e] - n0;
+            if (lj < 0 || lj >= ng || lj == li) continue;
+            atomicOr(&in_bits[i * W + (lj >> 6)], 1ull << (lj & 63));
+            atomicOr(&out_bits[(n0 + lj) * W + (li >> 6)], 1ull << (li & 63));
+        }
+    }
+}
+
+struct AdjLossParams {
+    float temp, shift, scale;   // u = temp * (shift - d2 * scale)
+    float t1, t0;               // label of a true edge / of a non-edge
+    float abs_tol;
+    float coef;                 // -2 temp scale
+    float grad_scale;
+};
+
+// LDS: cs [kAdjTile][CJ] | zi [kAdjTile][D] (ZI_LDS) | zj [CJ][Dp], Dp = D | 1 (ZJ_LDS: an odd row stride, lanes = columns)
+template <int CJ, bool ZI_LDS, bool ZJ_LDS>
+__global__ __launch_bounds__(256) void k_adj_loss_pairs(const float* __restrict__ z, int64_t ld, int D,
+                                                        const int32_t* __restrict__ off, int64_t n_graphs, int64_t n_nodes,
+                                                        int max_nodes, int64_t W,
+                                                        const unsigned long long* __restrict__ in_bits,
+                                                        const unsigned long long* __restrict__ out_bits, AdjLossParams P,
+                                                        double* __restrict__ row_loss, int32_t* __restrict__ row_fp,
+                                                        int32_t* __restrict__ row_fn, float* __restrict__ grad, int64_t ldg) {
+    constexpr int RPT = CJ / kAdjTile;   // rows of the tile per lane
+    constexpr int RSTEP = 256 / CJ;      // ... RSTEP apart
+    extern __shared__ float adj_lds[];
+    float* cs = adj_lds;
+    float* zi = cs + kAdjTile * CJ;
+    float* zj = zi + (ZI_LDS ? kAdjTile * D : 0);
+    const int Dp = D | 1;
+    const int i0 = blockIdx.y * kAdjTile;
+    for (int64_t g = blockIdx.x; g < n_graphs; g += gridDim.x) {   // (everything up to the lane's own pairs is uniform)
+        int64_t n0;
+        int ng;
+        stats_graph_range(off, (int)g, n_nodes, max_nodes, n0, ng);
+        if (i0 >= ng) continue;
+        const int rows = ng - i0 < kAdjTile ? ng - i0 : kAdjTile;
+        const int t = threadIdx.x;
+        const int c = t & (CJ - 1), r0 = t / CJ;
+        __syncthreads();   // the previous graph's readers of zi are done
+        if constexpr (ZI_LDS) {
+            for (int idx = t; idx < rows * D; idx += 256) {
+                const int rl = idx / D, f = idx - rl * D;
+                zi[idx] = z[(n0 + i0 + rl) * ld + f];
+            }
+        }
+        double ls[RPT];
+        int fpc[RPT], fnc[RPT];
+        const float* zr[RPT];
+#pragma unroll
+        for (int k = 0; k < RPT; ++k) {
+            ls[k] = 0.0;
+            fpc[k] = fnc[k] = 0;
+            int r = r0 + k * RSTEP;
+            if (r >= rows) r = rows - 1;   // a row past the tile's end reads the last one; its results are dropped
+            zr[k] = ZI_LDS ? zi + r * D : z + (n0 + i0 + r) * ld;
+        }
+        for (int j0 = 0; j0 < ng; j0 += CJ) {
+            const int cn = ng - j0 < CJ ? ng - j0 : CJ;
+            __syncthreads();   // the previous chunk's pass B is done with cs and zj
+            if constexpr (ZJ_LDS) {
+                for (int idx = t; idx < cn * D; idx += 256) {
+                    const int cl = idx / D, f = idx - cl * D;
+                    zj[cl * Dp + f] = z[(n0 + j0 + cl) * ld + f];
+                }
+                __syncthreads();
+            }
+            // ---- pass A: lane = (column c, rows r0 + k RSTEP)
+            float cij[RPT];
+#pragma unroll
+            for (int k = 0; k < RPT; ++k) cij[k] = 0.f;
+            if (c < cn) {
+                const int j = j0 + c;
+                const float* zc = ZJ_LDS ? zj + c * Dp : z + (n0 + j) * ld;
+                float d2[RPT];
+#pragma unroll
+                for (int k = 0; k < RPT; ++k) d2[k] = 0.f;
+                for (int f = 0; f < D; ++f) {
+                    const float zjf = zc[f];
+#pragma unroll
+                    for (int k = 0; k < RPT; ++k) {
+                        const float df = zr[k][f] - zjf;
+                        d2[k] = fmaf(df, df, d2[k]);
+                    }
+                }
+                const int64_t w = j >> 6;
+                const int bit = j & 63;
+#pragma unroll
+                for (int k = 0; k < RPT; ++k) {
+                    const int r = r0 + k * RSTEP;
+                    const int i = i0 + r;
+                    if (r >= rows || i == j) continue;
+                    const float u = P.temp * (P.shift - d2[k] * P.scale);
+                    const float p = 1.f / (1.f + expf(-u));
+                    const int64_t word = (n0 + i) * W + w;
+                    const bool aij = (out_bits[word] >> bit) & 1ull, aji = (in_bits[word] >> bit) & 1ull;
+                    const float af = aij ? 1.f : 0.f;
+                    if (p - af > P.abs_tol) ++fpc[k];
+                    if (af - p > P.abs_tol) ++fnc[k];
+                    const float tij = aij ? P.t1 : P.t0, tji = aji ? P.t1 : P.t0;
+                    const float uc = fminf(fmaxf(u, -kAdjClipU), kAdjClipU);
+                    ls[k] += ((double)fmaxf(uc, 0.f) + (double)log1pf(expf(-fabsf(uc)))) - (double)tij * (double)uc;
+                    if (fabsf(u) < kAdjClipU) cij[k] = P.coef * ((p - tij) + (p - tji));
+                }
+            }
+            if (grad) {   // (uniform)
+#pragma unroll
+                for (int k = 0; k < RPT; ++k) cs[(r0 + k * RSTEP) * CJ + c] = cij[k];
+                __syncthreads();
+                // ---- pass B: lane = (row, feature); the difference form, column by column in ascending order
+                const bool last = j0 + CJ >= ng;
+                for (int idx = t; idx < rows * D; idx += 256) {
+                    const int rl = idx / D, f = idx - rl * D;
+                    const float zif = ZI_LDS ? zi[idx] : z[(n0 + i0 + rl) * ld + f];
+                    float* gp = grad + (n0 + i0 + rl) * ldg + f;
+                    float acc = j0 == 0 ? 0.f : *gp;
+                    const float* crow = cs + rl * CJ;
+                    for (int cl = 0; cl < cn; ++cl) {
+                        const float cv = crow[cl];
+                        if (cv == 0.f) continue;   // clipped pair / diagonal: exactly nothing
+                        const float zjf = ZJ_LDS ? zj[cl * Dp + f] : z[(n0 + j0 + cl) * ld + f];
+                        acc = fmaf(cv, zif - zjf, acc);
+                    }
+                    *gp = last ? acc * P.grad_scale : acc;
+                }
+            }
+        }
+        // ---- row sums: the CJ lanes of a row, a fixed tree
+#pragma unroll
+        for (int k = 0; k < RPT; ++k) {
+            double l = ls[k];
+            int a = fpc[k], b = fnc[k];
+            for (int o = CJ / 2; o > 0; o >>= 1) {
+                l += __shfl_down(l, o, CJ);
+                a += __shfl_down(a, o, CJ);
+                b += __shfl_down(b, o, CJ);
+            }
+            const int r = r0 + k * RSTEP;
+            if (c == 0 && r < rows) {
+                row_loss[n0 + i0 + r] = l;
+                row_fp[n0 + i0 + r] = a;
+                row_fn[n0 + i0 + r] = b;
+            }
+        }
+    }
+}
+
+// one wave per graph: lane l adds rows l, l + 64, ... in that order, then the wave's fixed tree
+__global__ __launch_bounds__(256) void k_adj_loss_graphs(const int32_t* __restrict__ off, int64_t n_graphs, int64_t n_nodes,
+                                                         int max_nodes, const double* __restrict__ row_loss,
+                                                         const int32_t* __restrict__ row_fp, const int32_t* __restrict__ row_fn,
+                                                         double* __restrict__ loss_per_graph, int64_t* __restrict__ fp_pairs,
+                                                         int64_t* __restrict__ fn_pairs) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < n_graphs; g += (int64_t)gridDim.x * 4) {
+        int64_t n0;
+        int ng;
+        stats_graph_range(off, (int)g, n_nodes, max_nodes, n0, ng);
+        double l = 0.0;
+        unsigned long long a = 0, b = 0;
+        for (int r = lane; r < ng; r += 64) {
+            l += row_loss[n0 + r];
+            a += (unsigned long long)row_fp[n0 + r];
+            b += (unsigned long long)row_fn[n0 + r];
+        }
+        l = wave_sum_f64(l);
+        a = wave_sum_u64(a);
+        b = wave_sum_u64(b);
+        if (lane == 0) {
+            loss_per_graph[g] = l;
+            fp_pairs[g] = (int64_t)a;
+            fn_pairs[g] = (int64_t)b;
+        }
+    }
+}
+
+// one wave: sums2 = { sum_g loss_per_graph[g], that / (N^2 - N) }
+__global__ __launch_bounds__(64) void k_adj_loss_total(int64_t n_graphs, int64_t n_nodes,
+                                                       const double* __restrict__ loss_per_graph, double* __restrict__ sums2) {
+    double l = 0.0;
+    for (int64_t g = threadIdx.x; g < n_graphs; g += 64) l += loss_per_graph[g];
+    l = wave_sum_f64(l);
+    if (threadIdx.x == 0) {
+        sums2[0] = l;
+        sums2[1] = n_nodes < 2 ? 0.0 : l / ((double)n_nodes * (double)n_nodes - (double)n_nodes);
+    }
+}
+
+}  // namespace gnf
+
+using namespace gnf;
+
+extern "C" {
+
+size_t gnf_adj_loss_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph) {
+    if (n_graphs < 0 || n_nodes < 0 || max_nodes_per_graph < 0) return 0;
+    return adj_loss_ws(n_nodes, max_nodes_per_graph).total;
+}
+
+int gnf_adj_loss_f32(const GnfCsr* csr, const float* z, int64_t ld, int32_t D, int32_t max_nodes_per_graph,
+                     const GnfAdjLossSpec* spec, double* loss_per_graph, double* sums2, int64_t* fp_pairs, int64_t* fn_pairs,
+                     float* grad, int64_t ld_grad, float grad_scale, void* ws, size_t ws_bytes, gnf_stream_t stream) {
+    const char* what = "gnf_adj_loss_f32";
+    if (!csr || !spec) {
+        set_error("%s: null %s", what, csr ? "spec" : "csr");
+        return GNF_EINVAL;
+    }
+    if (D < 1 || ld < D || (grad && ld_grad < D)) {
+        set_error("%s: D=%d ld=%lld ld_grad=%lld", what, D, (long long)ld, (long long)ld_grad);
+        return GNF_ESHAPE;
+    }
+    if (max_nodes_per_graph < 0 || max_nodes_per_graph > kAdjLossMaxNodes) {
+        set_error("%s: max_nodes_per_graph=%d (0 <= max_nodes_per_graph <= %d)", what, max_nodes_per_graph, kAdjLossMaxNodes);
+        return GNF_ESHAPE;
+    }
+    if (csr->n_nodes < 0 || csr->n_edges < 0 || csr->n_graphs < 0 || csr->n_graphs > 0x7fffffff) {
+        set_error("%s: n_nodes=%lld n_edges=%lld n_graphs=%lld", what, (long long)csr->n_nodes, (long long)csr->n_edges,
+                  (long long)csr->n_graphs);
+        return GNF_ESHAPE;
+    }
+    if (!(spec->label_epsilon >= 0.f && spec->label_epsilon <= 0.5f) || !(spec->abs_tol >= 0.f)) {
+        set_error("%s: label_epsilon=%g (in [0, 0.5]) abs_tol=%g (>= 0)", what, (double)spec->label_epsilon,
+                  (double)spec->abs_tol);
+        return GNF_ESHAPE;
+    }
+    const int64_t n = csr->n_nodes, b = csr->n_graphs;
+    if (n > 0 && (!csr->node_offsets || b < 1)) {
+        set_error("%s: csr->node_offsets / csr->n_graphs are required", what);
+        return GNF_EINVAL;
+    }
+    if (b > 0 && !csr->node_offsets) {
+        set_error("%s: csr->node_offsets is null with n_graphs=%lld", what, (long long)b);
+        return GNF_EINVAL;
+    }
+    if (!sums2 || (n > 0 && (!csr->rowptr || !z || !ws)) || (csr->n_edges > 0 && !csr->col) ||
+        (b > 0 && (!loss_per_graph || !fp_pairs || !fn_pairs))) {
+        set_error("%s: null pointer argument", what);
+        return GNF_EINVAL;
+    }
+    if (n > 0 && max_nodes_per_graph == 0) {
+        set_error("%s: max_nodes_per_graph=0 with %lld nodes", what, (long long)n);
+        return GNF_ESHAPE;
+    }
+    const AdjLossWs L = adj_loss_ws(n, max_nodes_per_graph);
+    if (ws_bytes < L.total) {
+        set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, L.total);
+        return GNF_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0 || b == 0) {   // nothing to score: zeros
+        GNF_HIP_TRY(hipMemsetAsync(sums2, 0, 2 * sizeof(double), st));
+        if (b > 0) {
+            GNF_HIP_TRY(hipMemsetAsync(loss_per_graph, 0, (size_t)b * sizeof(double), st));
+            GNF_HIP_TRY(hipMemsetAsync(fp_pairs, 0, (size_t)b * sizeof(int64_t), st));
+            GNF_HIP_TRY(hipMemsetAsync(fn_pairs, 0, (size_t)b * sizeof(int64_t), st));
+        }
+        return GNF_OK;
+    }
+    unsigned long long* in_bits = (unsigned long long*)((char*)ws + L.in);
+    unsigned long long* out_bits = (unsigned long long*)((char*)ws + L.out);
+    double* row_loss = (double*)((char*)ws + L.row_loss);
+    int32_t* row_fp = (int32_t*)((char*)ws + L.row_fp);
+    int32_t* row_fn = (int32_t*)((char*)ws + L.row_fn);
+    GNF_HIP_TRY(hipMemsetAsync(ws, 0, L.total, st));   // bitmaps, and the sums of rows no tile covers
+    hipLaunchKernelGGL(k_adj_loss_bitmap, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->rowptr, csr->col, n,
+                       csr->n_edges, csr->node_offsets, b, max_nodes_per_graph, L.W, in_bits, out_bits, grad, ld_grad, D);
+    GNF_LAUNCH_CHECK("k_adj_loss_bitmap");
+    AdjLossParams P;
+    P.temp = spec->temp;
+    P.shift = spec->shift;
+    P.scale = spec->scale_by_sqrt_dim ? 1.f / sqrtf((float)D) : 1.f;
+    P.t1 = spec->soft_labels ? 1.f - spec->label_epsilon : 1.f;
+    P.t0 = spec->soft_labels ? spec->label_epsilon : 0.f;
+    P.abs_tol = spec->abs_tol;
+    P.coef = -2.f * spec->temp * P.scale;
+    P.grad_scale = grad_scale;
+    const dim3 grid(stats_grid(b), (unsigned)((max_nodes_per_graph + kAdjTile - 1) / kAdjTile));
+    const size_t tile = (size_t)kAdjTile * D * sizeof(float), dp = (size_t)(D | 1) * sizeof(float);
+    const size_t cs64 = (size_t)kAdjTile * 64 * sizeof(float), cs32 = (size_t)kAdjTile * 32 * sizeof(float);
+#define GNF_ADJ_LAUNCH(CJ, ZI, ZJ, LDS)                                                                                   \
+    hipLaunchKernelGGL((k_adj_loss_pairs<CJ, ZI, ZJ>), grid, dim3(256), LDS, st, z, ld, D, csr->node_offsets, b, n,       \
+                       max_nodes_per_graph, L.W, in_bits, out_bits, P, row_loss, row_fp, row_fn, grad, ld_grad)
+    if (cs64 + tile + 64 * dp <= kAdjLdsMax)
+        GNF_ADJ_LAUNCH(64, true, true, cs64 + tile + 64 * dp);
+    else if (cs32 + tile + 32 * dp <= kAdjLdsMax)
+        GNF_ADJ_LAUNCH(32, true, true, cs32 + tile + 32 * dp);
+    else if (cs64 + tile <= kAdjLdsMax)
+        GNF_ADJ_LAUNCH(64, true, false, cs64 + tile);
+    else
+        GNF_ADJ_LAUNCH(64, false, false, cs64);
+#undef GNF_ADJ_LAUNCH
+    GNF_LAUNCH_CHECK("k_adj_loss_pairs");
+    hipLaunchKernelGGL(k_adj_loss_graphs, dim3(stats_grid((b + 3) / 4)), dim3(256), 0, st, csr->node_offsets, b, n,
+                       max_nodes_per_graph, row_loss, row_fp, row_fn, loss_per_graph, fp_pairs, fn_pairs);
+    GNF_LAUNCH_CHECK("k_adj_loss_graphs");
+    hipLaunchKernelGGL(k_adj_loss_total, dim3(1), dim3(64), 0, st, b, n, loss_per_graph, sums2);
+    GNF_LAUNCH_CHECK("k_adj_loss_total");
+    return GNF_OK;
+}
+
+}  // extern "C"

@@ -507,6 +507,9 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 /* Added within ABI v10: orbit counts of a batch of graphs and the MMD of mean orbit vectors (gnf_graph_orbits.h) - part of
  * this interface, kept in a header of its own. */
 #include "gnf_graph_orbits.h"
+/* Added within ABI v10: the adjacency reconstruction loss of embeddings against a true batch, its edge-error counts and its
+ * gradient (gnf_adj_loss.h) - likewise part of this interface, in a header of its own. */
+#include "gnf_adj_loss.h"
 
 #ifdef __cplusplus
 }
