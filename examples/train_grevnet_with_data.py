@@ -6,9 +6,13 @@ MLPs (latent 2048 x 3 layers, D = 200, 10 coupling layers, batch norm) -> Adam (
 sampling pipeline z ~ N(0, I) -> grevnet(., inverse=False) -> pred_adj(scaled_hacky_sigmoid_l2) -> threshold 0.5
 (flow.generate_graphs: the generated graphs come back as a GraphsTuple with its CSR).
 
-There is no trained encoder here (run_gnn.py is out of scope), so --make_chunks writes embedding chunks whose
+Training the encoder (run_gnn.py) is out of scope, so by default --make_chunks writes embedding chunks whose
 embeddings are synthetic (two well-separated clusters per graph, so that the decoder finds structure); point
---train_data_dir at real chunks written by generate_grevnet_training_data.py to use those instead.
+--train_data_dir at real chunks written by generate_grevnet_training_data.py to use those instead.  With
+--encoder_params FILE (an .npz written by gnf_amd.encoder.save_encoder: an encoder's hyper-parameters and
+TimestepGNN.get_params()) --make_chunks runs that encoder's forward pass over --dataset instead
+(encoder.write_embedding_chunks, the loop of generate_grevnet_training_data.py) and the flow trains on its outputs;
+--node_embedding_dim is then the encoder's node width.
 
     python examples/train_grevnet_with_data.py --make_chunks --num_train_iters 200 --clip_gradient_by_norm
 
@@ -49,6 +53,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train_data_dir", default=None)
     ap.add_argument("--make_chunks", action="store_true")
+    ap.add_argument("--encoder_params", default=None)             # with --make_chunks: chunks from this encoder's forward pass
+    ap.add_argument("--dataset", default="graph_rnn_community_small")
     ap.add_argument("--node_embedding_dim", type=int, default=200)
     ap.add_argument("--latent_dim", type=int, default=2048)
     ap.add_argument("--num_layers", type=int, default=3)
@@ -90,7 +96,16 @@ def main():
             raise SystemExit("give --train_data_dir or --make_chunks")
         tmp = tempfile.TemporaryDirectory()
         F.train_data_dir = tmp.name
-        make_chunks(F.train_data_dir, 3, 10 * F.train_batch_size, F.node_embedding_dim, rng)
+        if F.encoder_params is None:
+            make_chunks(F.train_data_dir, 3, 10 * F.train_batch_size, F.node_embedding_dim, rng)
+        else:
+            from gnf_amd import encoder as E
+            enc, enc_hp = E.load_encoder(F.encoder_params)
+            F.node_embedding_dim = int(enc_hp["node_dim"])
+            paths = E.write_embedding_chunks(enc, D.GraphDataset(F.dataset, F.node_embedding_dim, seed=F.random_seed),
+                                             F.train_data_dir, 30 * F.train_batch_size, F.train_batch_size, device=dev,
+                                             chunk_bytes=10 * F.train_batch_size * 16 * F.node_embedding_dim * 4)
+            print(f"{len(paths)} embedding chunks from the encoder in {F.encoder_params} over {F.dataset}")
     # sort_files: the reference consumes the chunks in os.listdir order, which differs from one temporary directory
     # to the next (and with it the whole loss curve); sorted here so that a run of this demo is reproducible
     data = D.GrevnetDatasetFixed(F.train_data_dir, F.train_batch_size, F.train_epochs, sort_files=True)

@@ -6,14 +6,18 @@ Import as `gnf_amd` (the directory name has a hyphen; gnf_amd.py at the repo roo
     from gnf_amd.flow import log_prob_per_graph, sample, decode_graphs, generate_graphs
     from gnf_amd.graph_stats import graph_stats, hist_mmd, evaluate_generated, graph_orbits, orbit_mmd
     from gnf_amd.adj_loss import binary_loss, hacky_sigmoid_l2, sigmoid_l2, incorrect_edges_per_graph
+    from gnf_amd.gnn import TimestepGNN
+    from gnf_amd.encoder import evaluate, write_embedding_chunks
 """
 from . import _abi
 from .graphs import GraphsTuple, data_dicts_to_graphs_tuple, build_csr_host, csr_of, seed_csr_cache
 from .graph_stats import graph_stats, hist_mmd, evaluate_generated, graph_orbits, orbit_mmd
 from .adj_loss import (binary_loss, hacky_sigmoid_l2, sigmoid_l2, incorrect_edges_per_graph, false_positive_edges,
                        false_negative_edges, total_incorrect_edges)
+from .gnn import TimestepGNN
+from .encoder import evaluate, write_embedding_chunks
 
 __all__ = ["GraphsTuple", "data_dicts_to_graphs_tuple", "build_csr_host", "csr_of", "seed_csr_cache", "_abi",
            "graph_stats", "hist_mmd", "evaluate_generated", "graph_orbits", "orbit_mmd",
            "binary_loss", "hacky_sigmoid_l2", "sigmoid_l2", "incorrect_edges_per_graph", "false_positive_edges",
-           "false_negative_edges", "total_incorrect_edges"]
+           "false_negative_edges", "total_incorrect_edges", "TimestepGNN", "evaluate", "write_embedding_chunks"]

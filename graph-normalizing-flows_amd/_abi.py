@@ -75,6 +75,21 @@ class GnfAdjLossSpec(C.Structure):   # include/gnf_adj_loss.h
                 ("label_epsilon", C.c_float), ("abs_tol", C.c_float)]
 
 
+class GnfSntBatchNorm(C.Structure):   # include/gnf_timestep_gnn.h: snt.BatchNorm(scale=True) of one encoder timestep
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("moving_mean", C.c_void_p), ("moving_variance", C.c_void_p),
+                ("batch_mean", C.c_void_p), ("batch_variance", C.c_void_p)]
+
+
+class GnfRowNorm(C.Structure):        # include/gnf_timestep_gnn.h: snt.LayerNorm() of one encoder timestep
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p)]
+
+
+class GnfTimestepGnn(C.Structure):    # include/gnf_timestep_gnn.h
+    _fields_ = [("num_timesteps", C.c_int32), ("weight_sharing", C.c_int32), ("nets", C.POINTER(GnfMlp)), ("gnn", GnfGnnSpec),
+                ("bns", C.POINTER(GnfSntBatchNorm)), ("lns", C.POINTER(GnfRowNorm)), ("residual", C.c_int32),
+                ("is_training", C.c_int32), ("test_local_stats", C.c_int32), ("bn_eps", C.c_float), ("bn_decay", C.c_float)]
+
+
 _SIGNATURES = {
     "gnf_abi_version": (C.c_int, []),
     "gnf_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
@@ -163,9 +178,18 @@ _ADJ_LOSS_SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/gnf_timestep_gnn.h (included by gnf.h, added within ABI v10): the encoder's forward pass, TimestepGNN with its batch /
+# layer norms.  A table of its own for the same reason.
+_ENCODER_SIGNATURES = {
+    "gnf_timestep_gnn_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.POINTER(GnfTimestepGnn)]),
+    "gnf_timestep_gnn_f32": (C.c_int, [C.POINTER(GnfCsr), C.POINTER(GnfTimestepGnn), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                       C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 ORBIT_SYMBOLS = tuple(_ORBIT_SIGNATURES)
 ADJ_LOSS_SYMBOLS = tuple(_ADJ_LOSS_SIGNATURES)
+ENCODER_SYMBOLS = tuple(_ENCODER_SIGNATURES)
 
 _lib = None
 
@@ -179,7 +203,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

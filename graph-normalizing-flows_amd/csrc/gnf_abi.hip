@@ -52,7 +52,7 @@ int validate_mlp(const GnfMlp* m, const char* what) {
     return GNF_OK;
 }
 
-static int validate_spec(const GnfGnnSpec* g) {
+int validate_spec(const GnfGnnSpec* g) {
     if (!g) {
         set_error("null GnfGnnSpec");
         return GNF_EINVAL;
@@ -72,7 +72,7 @@ static int validate_spec(const GnfGnnSpec* g) {
     return GNF_OK;
 }
 
-static int validate_csr(const GnfCsr* c) {
+int validate_csr(const GnfCsr* c) {
     if (!c) {
         set_error("null GnfCsr");
         return GNF_EINVAL;
@@ -90,7 +90,7 @@ static int validate_csr(const GnfCsr* c) {
 }
 
 // a graph-scope attention net reads the batch's graph boundaries (GnfCsr.node_offsets, ABI v10)
-static int validate_node_offsets(const GnfCsr* c, const GnfMlp* net, const char* what) {
+int validate_node_offsets(const GnfCsr* c, const GnfMlp* net, const char* what) {
     if (!net || !attn_is_graph(net->attn) || c->n_nodes == 0) return GNF_OK;
     if (!c->node_offsets || c->n_graphs < 1 || c->n_graphs >= INT32_MAX) {
         set_error("%s: graph-scope attention needs GnfCsr.node_offsets (device int32 [n_graphs + 1]) and n_graphs >= 1; got node_offsets=%p n_graphs=%lld", what, (const void*)c->node_offsets, (long long)c->n_graphs);

@@ -278,6 +278,10 @@ int launch_bn_backward(const GnfFlow* flow, const GnfBatchNorm* bn, const GnfBat
                        float* gy, int64_t ldg, int64_t n, int32_t H, double* part, hipStream_t st, int pre_parts = 0);
 
 int validate_mlp(const GnfMlp* m, const char* what);
+// shared with the entry points of the other translation units (gnf_timestep_gnn.hip)
+int validate_spec(const GnfGnnSpec* g);
+int validate_csr(const GnfCsr* c);
+int validate_node_offsets(const GnfCsr* c, const GnfMlp* net, const char* what);
 int validate_flow_call(const GnfCsr* csr, const GnfFlow* flow, int64_t ld, int32_t D, const char* what);
 // attention front-end (gnf_attn.hip).  THE limit of the block's geometry (include/gnf.h, GnfAttn): heads <= 64,
 // heads * kq <= 256, heads * v <= 256, and pad16(2 heads kq + v) + pad16(H) + H <= 1272 (the backward pass's dL/dx_cond

@@ -8,14 +8,16 @@ from . import gnn
 
 
 def make_gnn_fn(hp):
-    """hp: D, latent, K, activation ("relu" | "leaky_relu"), then either
+    """hp: D (or node_dim), latent, K, activation ("relu" | "leaky_relu"), then either
          agg ("sum" | "mean"), combine ("agg" | "concat"), epsilon             (run_grevnet.py:154-180)
        or attn = dict(num_heads, kq_dim, v_dim, out_dim, concat, kq_dim_division, residual[, layer_norm])
                                                                                 (run_grevnet.py:199-211)
        or attn = dict(scope="graph", kq_dim, v_dim[, num_heads, out_dim, kq_dim_division, layer_norm]): whole-graph
           attention, MultiheadSelfAttention - or SelfAttention without out_dim (run_grevnet.py:214-237)."""
     act = gnn.leaky_relu if hp["activation"] == "leaky_relu" else gnn.relu
-    mk_mlp = partial(gnn.make_mlp_model, hp["latent"], hp["D"] / 2, hp["K"], act, 0.01, hp.get("bias_init_stddev", 0.1))
+    # the MLPs map to a coupling half, D / 2 - or, for a GNN outside a flow (the encoder), to hp["node_dim"], the node width
+    out_dim = hp["node_dim"] if "node_dim" in hp else hp["D"] / 2
+    mk_mlp = partial(gnn.make_mlp_model, hp["latent"], out_dim, hp["K"], act, 0.01, hp.get("bias_init_stddev", 0.1))
     a = hp.get("attn")
     if a and a.get("scope") == "graph":   # whole-graph attention (run_grevnet.py:214-237): no out_dim = SelfAttention
         if a.get("out_dim") is None:

@@ -935,3 +935,205 @@ class GRevNet:
         return func(input)
 
     __call__ = _build
+
+
+# ----------------------------------------------------------------------------------------------
+# TimestepGNN (gnn.py:183-235): the encoder of the graph auto-encoder (run_gnn.py:230-239)
+# ----------------------------------------------------------------------------------------------
+class SntBatchNorm:
+    """snt.BatchNorm(scale=True) of one encoder timestep (gnn.py:210-213): gamma (ones), beta (zeros), moving_mean (zeros),
+    moving_variance (ones), created at first connection; eps 1e-3 and decay_rate 0.999 are Sonnet-1's constructor defaults
+    (third party, absent: UNPINNED - include/gnf_timestep_gnn.h lists what is restated).  The arithmetic AND the
+    moving-average update of a training call run inside gnf_timestep_gnn_f32; this object owns the variables and the batch
+    moments of the last call that took them."""
+    KEYS = ("gamma", "beta", "moving_mean", "moving_variance")
+
+    def __init__(self):
+        self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+        self.batch_mean = self.batch_variance = None
+
+    def ensure_built(self, width, device):
+        if self.gamma is None:
+            self.gamma, self.beta = torch.ones(width), torch.zeros(width)
+            self.moving_mean, self.moving_variance = torch.zeros(width), torch.ones(width)
+        if self.gamma.shape[0] != width:
+            raise ValueError(f"batch norm built for width {self.gamma.shape[0]}, connected to {width}")
+        if self.gamma.device != torch.device(device) or self.batch_mean is None:
+            for k in self.KEYS:
+                setattr(self, k, getattr(self, k).to(device=device, dtype=torch.float32).contiguous())
+            self.batch_mean = torch.zeros(width, dtype=torch.float32, device=device)
+            self.batch_variance = torch.zeros(width, dtype=torch.float32, device=device)
+        return self
+
+    def set_params(self, d):
+        for k in self.KEYS:
+            v = d[k]
+            v = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(torch.float32).contiguous().clone()
+            if v.ndim != 1:
+                raise ValueError(f"batch norm {k} must be 1-D [D]")
+            setattr(self, k, v)
+        self.batch_mean = None
+
+    def get_params(self):
+        return {k: getattr(self, k).detach().cpu().numpy().copy() for k in self.KEYS}
+
+    def fill_desc(self, desc):
+        for k in self.KEYS + ("batch_mean", "batch_variance"):
+            setattr(desc, k, getattr(self, k).data_ptr())
+
+
+class RowLayerNorm:
+    """snt.LayerNorm() of one encoder timestep (gnn.py:214-215): gamma (ones), beta (zeros) of the node width."""
+    KEYS = ("gamma", "beta")
+
+    def __init__(self):
+        self.gamma = self.beta = None
+
+    def ensure_built(self, width, device):
+        if self.gamma is None:
+            self.gamma, self.beta = torch.ones(width), torch.zeros(width)
+        if self.gamma.shape[0] != width:
+            raise ValueError(f"layer norm built for width {self.gamma.shape[0]}, connected to {width}")
+        if self.gamma.device != torch.device(device):
+            for k in self.KEYS:
+                setattr(self, k, getattr(self, k).to(device=device, dtype=torch.float32).contiguous())
+        return self
+
+    def set_params(self, d):
+        for k in self.KEYS:
+            v = d[k]
+            v = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(torch.float32).contiguous().clone()
+            if v.ndim != 1:
+                raise ValueError(f"layer norm {k} must be 1-D [D]")
+            setattr(self, k, v)
+
+    def get_params(self):
+        return {k: getattr(self, k).detach().cpu().numpy().copy() for k in self.KEYS}
+
+
+class TimestepGNN:
+    """gnn.py:183-235: runs the input GNN for num_timesteps timesteps - per timestep an optional snt.BatchNorm(scale=True),
+    an optional snt.LayerNorm(), then the GNN (one shared GNN with weight_sharing, the norms stay per timestep) - and adds
+    the input nodes at the end when `residual`.  `__call__(graph, is_training)` as the reference's; forward only (its
+    backward pass and a trainer are not here).  One library call, gnf_timestep_gnn_f32 (include/gnf_timestep_gnn.h):
+    asynchronous, nothing read back, capturable once the variables exist (make one eager call first).  With
+    use_batch_norm, a call with is_training=True updates the moving statistics on the device (what UPDATE_OPS does,
+    run_gnn.py:295-296); `last_batch_moments` is [(batch_mean, batch_variance)] * T of the last call if it took batch
+    moments (is_training or test_local_stats), else None.  The tensors are the batch norms' own device buffers, written in
+    place by every such call and by every replay of a captured one - clone them to keep a call's values.  HIP only: CPU tensors raise GnfError."""
+    bn_eps = 1e-3        # Sonnet-1 snt.BatchNorm defaults (UNPINNED)
+    bn_decay_rate = 0.999
+
+    def __init__(self, make_gnn_fn, num_timesteps, weight_sharing=False, use_batch_norm=False, residual=True,
+                 test_local_stats=False, use_layer_norm=False, name="TimestepGNN"):
+        self.num_timesteps = int(num_timesteps)
+        if self.num_timesteps < 1:
+            raise ValueError("num_timesteps must be >= 1")
+        self.weight_sharing = bool(weight_sharing)
+        self.use_batch_norm = bool(use_batch_norm)
+        self.residual = bool(residual)
+        self.test_local_stats = bool(test_local_stats)
+        self.use_layer_norm = bool(use_layer_norm)
+        self.name = name
+        self.gnns = [make_gnn_fn()] if self.weight_sharing else [make_gnn_fn() for _ in range(self.num_timesteps)]
+        self.bns = [SntBatchNorm() for _ in range(self.num_timesteps)] if self.use_batch_norm else []
+        self.lns = [RowLayerNorm() for _ in range(self.num_timesteps)] if self.use_layer_norm else []
+        self.last_batch_moments = None
+
+    def blocks(self):
+        """node blocks in ABI order: one per timestep, or the one shared block"""
+        return [GRevNet._block_of(g) for g in self.gnns]
+
+    # ---- parameters: {"nets": [net] * (T or 1), "bn": [{gamma, beta, moving_mean, moving_variance}] * T, "ln": [{gamma, beta}] * T}
+    # net = [(W, b), ...] or, for an attention block, {"attn": {...}, "mlp": [(W, b), ...]} - GRevNet's layout of one net
+    def set_params(self, params):
+        nets = list(params["nets"])
+        if len(nets) != len(self.gnns):
+            raise ValueError(f"{self.name}: expected {len(self.gnns)} nets, got {len(nets)}")
+        for blk, net in zip(self.blocks(), nets):
+            if isinstance(net, dict):
+                blk.set_attn_params(net["attn"])
+                blk._mlp.set_params(net["mlp"])
+            else:
+                blk._mlp.set_params(net)
+        for key, objs in (("bn", self.bns), ("ln", self.lns)):
+            if objs and params.get(key) is not None:
+                if len(params[key]) != len(objs):
+                    raise ValueError(f"{self.name}: expected {len(objs)} '{key}' entries, got {len(params[key])}")
+                for o, d in zip(objs, params[key]):
+                    o.set_params(d)
+        return self
+
+    def get_params(self):
+        out = {"nets": [({"attn": b.get_attn_params(), "mlp": b._mlp.get_params()} if hasattr(b, "get_attn_params")
+                         else b._mlp.get_params()) for b in self.blocks()]}
+        if self.bns and self.bns[0].gamma is not None:
+            out["bn"] = [b.get_params() for b in self.bns]
+        if self.lns and self.lns[0].gamma is not None:
+            out["ln"] = [l.get_params() for l in self.lns]
+        return out
+
+    def _desc(self, d, dev, is_training):
+        """(GnfTimestepGnn for nodes of width d on dev, whatever it points to) - variables are created at first connection"""
+        blocks = self.blocks()
+        b0 = blocks[0]
+        for b in blocks:
+            if b.signature() != b0.signature():
+                raise ValueError("all GNNs of a TimestepGNN must come from the same make_gnn_fn")
+        mlps = [b._mlp.ensure_built(b0.in_dim(d), dev) for b in blocks]
+        if mlps[0].layer_sizes[-1] != d:
+            raise ValueError(f"{self.name}: the GNN maps to width {mlps[0].layer_sizes[-1]}, the nodes have {d} "
+                             "(every timestep feeds the next: make_mlp_fn's output_dim must be the node width)")
+        nets = (_abi.GnfMlp * len(mlps))()
+        attn = (_abi.GnfAttn * len(mlps))()
+        for q, (b, m) in enumerate(zip(blocks, mlps)):
+            m.fill_desc(nets[q], 0)
+            ad = b.attn_desc(d, dev)
+            if ad is not None:
+                attn[q] = ad
+                nets[q].attn = C.cast(C.byref(attn, q * C.sizeof(_abi.GnfAttn)), C.POINTER(_abi.GnfAttn))
+        bn_arr = ln_arr = None
+        if self.bns:
+            bn_arr = (_abi.GnfSntBatchNorm * self.num_timesteps)()
+            for q, b in enumerate(self.bns):
+                b.ensure_built(d, dev).fill_desc(bn_arr[q])
+        if self.lns:
+            ln_arr = (_abi.GnfRowNorm * self.num_timesteps)()
+            for q, l in enumerate(self.lns):
+                l.ensure_built(d, dev)
+                ln_arr[q].gamma, ln_arr[q].beta = l.gamma.data_ptr(), l.beta.data_ptr()
+        desc = _abi.GnfTimestepGnn(self.num_timesteps, int(self.weight_sharing), C.cast(nets, C.POINTER(_abi.GnfMlp)), b0.spec(),
+                                   C.cast(bn_arr, C.POINTER(_abi.GnfSntBatchNorm)) if bn_arr is not None else None,
+                                   C.cast(ln_arr, C.POINTER(_abi.GnfRowNorm)) if ln_arr is not None else None,
+                                   int(self.residual), int(bool(is_training)), int(self.test_local_stats),
+                                   float(self.bn_eps), float(self.bn_decay_rate))
+        return desc, (nets, attn, bn_arr, ln_arr, mlps, blocks)
+
+    def _build(self, graph, is_training):
+        lib = _abi.lib()
+        x = graph.nodes
+        if x.device.type != "cuda":
+            raise _abi.GnfError("TimestepGNN runs on a HIP device only (no CPU path)")
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise ValueError(f"nodes must be [N, D] with D >= 1; got {tuple(x.shape)}")
+        x = x.to(torch.float32)
+        n, d = x.shape
+        if n > 0 and (x.stride(1) != 1 or x.stride(0) < d):
+            x = x.contiguous()
+        dev = x.device
+        desc, keep = self._desc(d, dev, is_training)
+        csr = csr_desc(graph, csr_of(graph), self.blocks()[0].graph_scope)
+        out = torch.empty((n, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws_bytes = lib.gnf_timestep_gnn_workspace_bytes(n, d, C.byref(desc))
+            ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+            _abi.check(lib.gnf_timestep_gnn_f32(C.byref(csr), C.byref(desc), _abi.ptr(x), x.stride(0) if n > 1 else max(int(x.stride(0)), d),
+                                                _abi.ptr(out), d, d, _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                       "gnf_timestep_gnn_f32")
+        del keep
+        took = self.bns and n > 0 and (bool(is_training) or self.test_local_stats)
+        self.last_batch_moments = [(b.batch_mean, b.batch_variance) for b in self.bns] if took else None
+        return graph.replace(nodes=out)
+
+    def __call__(self, graph, is_training):
+        return self._build(graph, is_training)
