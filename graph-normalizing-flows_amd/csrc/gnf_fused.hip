@@ -116,6 +116,102 @@ int launch_pack_mlp(const GnfMlp* m, float* packed, hipStream_t st) {
 #include "gnf_attn_front_dev.h"
 namespace gnf {
 
+// ---- C: coupling update + block-reduced sum(s) of one row tile (both-nets shapes): s and t rows in LDS, [TM][LS] -----------
+// xn_lds: a free [TM][LS] buffer (the updated rows, for the next bijector's column sums).  PLAIN: the caller is the
+// compile-time-geometry instance (k_half_fused_geo), whose arguments carry no residual, batch-norm or stash fields.
+template <int TM, bool STASH, bool FRONT, bool ROWLD, bool PLAIN, class Args, class FArgs, class RArgs>
+__device__ __forceinline__ void couple_tile(const Args& a, const FArgs& fa, const RArgs& rla, const int H, const int LS, float* s_lds,
+                                            const float* t_lds, float* xn_lds, const float* bn_lds, double* red, int tile, int row0,
+                                            int tid, int wave, int lane) {
+    [[maybe_unused]] auto bn_part = [&]() -> double* {
+        if constexpr (PLAIN) return nullptr; else return a.bn_part;
+    };
+    double local = 0.0, local2 = 0.0;
+    for (int idx = tid; idx < TM * H; idx += kFusedThreads) {
+        const int rl = idx / H, f = idx - rl * H;
+        const int r = row0 + rl;
+        if (bn_part()) xn_lds[rl * LS + f] = 0.f;
+        if (r < a.n_nodes) {
+            float sv = s_lds[rl * LS + f], tv = t_lds[rl * LS + f];
+            [[maybe_unused]] const int HPb = (H + 15) & ~15;
+            if constexpr (!PLAIN) {
+                if (a.residual) {
+                    float xr = a.x_cond[(int64_t)r * a.ld + f];
+                    if constexpr (FRONT) {
+                        if (fa.bn_part) xr = xr * bn_lds[f] + bn_lds[HPb + f];  // (the conditioning rows in memory are raw)
+                    }
+                    sv += xr;
+                    tv += xr;
+                }
+            }
+            float xv = a.x_upd_src[(int64_t)r * a.ld + f];
+            if constexpr (FRONT) {
+                if (a.bnu_const) xv = xv * bn_lds[2 * HPb + f] + bn_lds[3 * HPb + f];  // the previous half-step's bijector, deferred
+                else if (a.bnu_inv[0]) xv = (xv - bn_lds[f]) / bn_lds[HPb + f] * bn_lds[2 * HPb + f] + bn_lds[3 * HPb + f];
+            }
+            const float xn = a.inverse ? (xv - tv) * expf(-sv) : xv * expf(sv) + tv;
+            a.x_upd[(int64_t)r * a.ld + f] = xn;
+            local += (double)sv;
+            local2 += (double)xn * (double)xn;
+            if constexpr (ROWLD) s_lds[rl * LS + f] = sv;  // (what the coupling used: a residual block's x_cond is in)
+            if (bn_part()) xn_lds[rl * LS + f] = xn;
+            if constexpr (STASH) {  // (what the coupling used: a residual block's x_cond is already in)
+                a.stash_st[0][(int64_t)r * H + f] = sv;
+                a.stash_st[1][(int64_t)r * H + f] = tv;
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+    if (lane == 0) red[wave] = local;
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0.0;
+        for (int w = 0; w < kFusedThreads / 64; ++w) tot += red[w];
+        a.partials[tile] = tot;
+    }
+    if constexpr (!PLAIN) {
+        if (a.bn_part) {  // (workgroup-uniform) column sums over the tile's rows, fixed order
+            __syncthreads();
+            for (int i = tid; i < 2 * H; i += kFusedThreads) {
+                const int f = i >> 1, which = i & 1;
+                double acc = 0.0;
+                for (int rl = 0; rl < TM; ++rl) {
+                    const double v = (double)xn_lds[rl * LS + f];
+                    acc += which ? v * v : v;
+                }
+                a.bn_part[((int64_t)tile * H + f) * 2 + which] = acc;
+            }
+        }
+    }
+    if (a.sq_partials) {  // (workgroup-uniform) the same fixed-order reduction for sum(x_new^2)
+        for (int off = 32; off > 0; off >>= 1) local2 += __shfl_down(local2, off, 64);
+        __syncthreads();
+        if (lane == 0) red[wave] = local2;
+        __syncthreads();
+        if (tid == 0) {
+            double tot = 0.0;
+            for (int w = 0; w < kFusedThreads / 64; ++w) tot += red[w];
+            a.sq_partials[tile] = tot;
+        }
+    }
+    if constexpr (ROWLD) {  // sum_j s[r, j] of the tile's rows: 512 / TM threads per row, fixed order, fp64
+        __syncthreads();
+        constexpr int TPR = kFusedThreads / TM;
+        const int rl = tid / TPR, l = tid % TPR;
+        double acc = 0.0;
+        for (int f = l; f < H; f += TPR) acc += (double)s_lds[rl * LS + f];
+        for (int off = TPR / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, TPR);
+        if (l == 0 && row0 + rl < a.n_nodes) rla.row[row0 + rl] = acc;
+    }
+}
+
+// blockIdx -> row tile of the both-nets shapes.  Block b is dispatched to XCD b % 8: XCD-aware bijective remap,
+// consecutive tiles (neighbouring nodes) share an XCD.
+__device__ __forceinline__ int nets2_tile(int bid, int nwg) {
+    const int xcd = bid & 7, qd = nwg >> 3, rm = nwg & 7;
+    return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
+}
+
 // FRONT (MT = 1, NETS = 2, attention GNNs on sparse batches): the attention front-end (gnf_attn_front_dev.h) runs as this
 // kernel's prologue and leaves the layer-0 input rows of both nets in the activation buffers - no launch boundary, no
 // trip of those rows through global memory.  Its staging area (x rows, q | v of the sender window: 149 KB at the
@@ -141,14 +237,13 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused(const FusedArgs a,
     double* red = reinterpret_cast<double*>(bias_lds + NETS * a.bias_tot + ((NETS * a.bias_tot) & 1));
 
     // blockIdx -> (tile, net).  Block b is dispatched to XCD b % 8.
-    //  NETS = 2: XCD-aware bijective remap, consecutive tiles (neighbouring nodes) share an XCD.
+    //  NETS = 2: nets2_tile.
     //  NETS = 1: XCDs 0-3 run the s-net, XCDs 4-7 the t-net (each XCD L2 caches one net's weights).
     int tile, net0;
     {
         const int bid = blockIdx.x;
         if (NETS == 2) {
-            const int nwg = gridDim.x, xcd = bid & 7, qd = nwg >> 3, rm = nwg & 7;
-            tile = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + (bid >> 3);
+            tile = nets2_tile(bid, gridDim.x);
             net0 = 0;
         } else {
             const int xcd = bid & 7;
@@ -448,86 +543,137 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused(const FusedArgs a,
                 dst[(int64_t)r * H + f] = o_lds[rl * LS + f] + (a.residual ? a.x_cond[(int64_t)r * a.ld + f] : 0.f);
         }
     } else {
-        // ---- C: coupling update + block-reduced sum(s) -----------------------------------------
-        const float* s_lds = buf(0, pp);
-        const float* t_lds = buf(1, pp);
-        double local = 0.0, local2 = 0.0;
-        float* xn_lds = buf(0, pp ^ 1);  // (free by now) the updated rows, for the column sums below
-        for (int idx = tid; idx < TM * H; idx += kFusedThreads) {
-            const int rl = idx / H, f = idx - rl * H;
-            const int r = row0 + rl;
-            if (a.bn_part) xn_lds[rl * LS + f] = 0.f;
-            if (r < a.n_nodes) {
-                float sv = s_lds[rl * LS + f], tv = t_lds[rl * LS + f];
-                [[maybe_unused]] const int HPb = (H + 15) & ~15;
-                if (a.residual) {
-                    float xr = a.x_cond[(int64_t)r * a.ld + f];
-                    if constexpr (FRONT) {
-                        if (fa.bn_part) xr = xr * bn_lds[f] + bn_lds[HPb + f];  // (the conditioning rows in memory are raw)
-                    }
-                    sv += xr;
-                    tv += xr;
-                }
-                float xv = a.x_upd_src[(int64_t)r * a.ld + f];
-                if constexpr (FRONT) {
-                    if (a.bnu_const) xv = xv * bn_lds[2 * HPb + f] + bn_lds[3 * HPb + f];  // the previous half-step's bijector, deferred
-                    else if (a.bnu_inv[0]) xv = (xv - bn_lds[f]) / bn_lds[HPb + f] * bn_lds[2 * HPb + f] + bn_lds[3 * HPb + f];
-                }
-                const float xn = a.inverse ? (xv - tv) * expf(-sv) : xv * expf(sv) + tv;
-                a.x_upd[(int64_t)r * a.ld + f] = xn;
-                local += (double)sv;
-                local2 += (double)xn * (double)xn;
-                if constexpr (ROWLD) buf(0, pp)[rl * LS + f] = sv;  // (what the coupling used: a residual block's x_cond is in)
-                if (a.bn_part) xn_lds[rl * LS + f] = xn;
-                if constexpr (STASH) {  // (what the coupling used: a residual block's x_cond is already in)
-                    a.stash_st[0][(int64_t)r * H + f] = sv;
-                    a.stash_st[1][(int64_t)r * H + f] = tv;
-                }
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
-        if (lane == 0) red[wave] = local;
-        __syncthreads();
-        if (tid == 0) {
-            double tot = 0.0;
-            for (int w = 0; w < kFusedThreads / 64; ++w) tot += red[w];
-            a.partials[tile] = tot;
-        }
-        if (a.bn_part) {  // (workgroup-uniform) column sums over the tile's rows, fixed order
-            __syncthreads();
-            for (int i = tid; i < 2 * H; i += kFusedThreads) {
-                const int f = i >> 1, which = i & 1;
-                double acc = 0.0;
-                for (int rl = 0; rl < TM; ++rl) {
-                    const double v = (double)xn_lds[rl * LS + f];
-                    acc += which ? v * v : v;
-                }
-                a.bn_part[((int64_t)tile * H + f) * 2 + which] = acc;
-            }
-        }
-        if (a.sq_partials) {  // (workgroup-uniform) the same fixed-order reduction for sum(x_new^2)
-            for (int off = 32; off > 0; off >>= 1) local2 += __shfl_down(local2, off, 64);
-            __syncthreads();
-            if (lane == 0) red[wave] = local2;
-            __syncthreads();
-            if (tid == 0) {
-                double tot = 0.0;
-                for (int w = 0; w < kFusedThreads / 64; ++w) tot += red[w];
-                a.sq_partials[tile] = tot;
-            }
-        }
-        if constexpr (ROWLD) {  // sum_j s[r, j] of the tile's rows: 512 / TM threads per row, fixed order, fp64
-            __syncthreads();
-            constexpr int TPR = kFusedThreads / TM;
-            const int rl = tid / TPR, l = tid % TPR;
-            double acc = 0.0;
-            for (int f = l; f < H; f += TPR) acc += (double)s_lds[rl * LS + f];
-            for (int off = TPR / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, TPR);
-            if (l == 0 && row0 + rl < a.n_nodes) rla.row[row0 + rl] = acc;
-        }
+        couple_tile<TM, STASH, FRONT, ROWLD, false>(a, fa, rla, H, LS, buf(0, pp), buf(1, pp), buf(0, pp ^ 1), bn_lds, red, tile, row0, tid,
+                                                    wave, lane);
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Compile-time-geometry instance of the 16-row both-nets forward / inverse kernel (message-passing GNN, combine = agg,
+// no stash / attention / per-row log-det / batch-norm moments): the MLP is in0 = 16 IN0G -> (K - 1) x 16 LG -> H = 16 HG,
+// both nets alike.  Everything the generic instance looks up per launch, per layer and per chunk - the LDS layer table,
+// next_chunk's search, the nv dispatch, the bias block in LDS, the run-time widths in the address arithmetic - is a
+// constant here; the arithmetic (tile_aggregate, mlp_chunk<1, 4>, mlp_chunk_thin, couple_tile) is the generic instance's
+// own code, so the results are bitwise its results (tests/test_fused_geo_gpu.py).  launch_half_fused has the dispatch rule.
+struct GeoArgs {  // what the plain forward reads, and nothing else (FusedArgs + FrontArgs + RowLdArgs: 1.2 KB)
+    const int32_t* rowptr;
+    const int32_t* col;
+    const float* x_cond;
+    float* x_upd;
+    const float* x_upd_src;
+    float* cond_copy;
+    double* partials;
+    double* sq_partials;
+    const float* wp[2];    // [net] packed weights of layer 0; the other layers and the bias block follow at constant offsets
+    int64_t ld;
+    int32_t n_nodes, n_tiles;
+    float eps, alpha;
+    int32_t mean, act, inverse;
+};
+
+template <int IN0G, int LG, int K, int HG>
+struct GeoLayout {  // the packed layout (launch_pack_mlp) of this geometry, in floats
+    static constexpr int kWpn = 4;       // waves per net
+    static constexpr int kFragFloats = 64 * 4;  // one (k-group, column tile) fragment block: 64 lanes x 4 floats = 1 KiB
+    static_assert(kFragFloats * sizeof(float) == 1024 && sizeof(f32x4) == 16, "GNF_LOAD_B addresses 1 KiB fragment blocks, 16 bytes per lane");
+    static_assert(K >= 2 && IN0G >= 1 && IN0G == HG, "combine = agg: the layer-0 input is as wide as the half that is rewritten");
+    static_assert(LG == 4 * kWpn, "a wave owns exactly four column tiles of a hidden layer: one mlp_chunk<1, 4> per layer");
+    static_assert(HG <= kWpn && LG <= kThinStages, "the output layer is at most one thin chunk per wave");
+    static constexpr int ipg(int j) { return j == 0 ? IN0G : LG; }       // k-groups of layer j
+    static constexpr int ont(int j) { return j == K - 1 ? HG : LG; }      // column tiles of layer j
+    // Wp_j[ipg][ont][64][4], k-group major, layer after layer; then the bias block
+    static constexpr int woff(int j) { return j == 0 ? 0 : woff(j - 1) + ipg(j - 1) * ont(j - 1) * kFragFloats; }
+    static constexpr int boff(int j) { return j == 0 ? 0 : boff(j - 1) + 16 * ont(j - 1); }  // inside the bias block
+    static constexpr int kBias = woff(K);                                 // bias block behind the weights
+    static constexpr int kLS = 16 * (LG > IN0G ? LG : IN0G) + 4;          // LDS row stride: widest layer + 4 floats
+    static constexpr size_t kLds = (size_t)2 * 2 * 16 * kLS * sizeof(float) + 8 * sizeof(double) + (kRowptrPad + kColCap) * sizeof(int);
+    static_assert(woff(1) == 16 * IN0G * 16 * LG && kBias == 16 * IN0G * 16 * LG + (K - 2) * 256 * LG * LG + 16 * LG * 16 * HG,
+                  "sum of Ip x Op over the layers");
+    static_assert(kLds <= (size_t)kLdsLimit, "activation buffers in LDS");
+};
+
+template <int IN0G, int LG, int K, int HG>
+__global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    using G = GeoLayout<IN0G, LG, K, HG>;
+    constexpr int TM = 16, WPN = G::kWpn, LS = G::kLS, H = 16 * HG, IN0 = 16 * IN0G;
+    // [net][pingpong][TM][LS] | reduction scratch | rowptr slice | col slice
+    auto buf = [&](int net_, int pp_) -> float* { return smem + (2 * net_ + pp_) * TM * LS; };
+    double* red = reinterpret_cast<double*>(smem + 2 * 2 * TM * LS);
+    int* s_rowptr = reinterpret_cast<int*>(red + 8);
+    int* s_col = s_rowptr + kRowptrPad;
+
+    const int tile = nets2_tile(blockIdx.x, gridDim.x);
+    const int row0 = tile * TM;
+    const int tid = threadIdx.x;
+    // (wave ids, the second net's rotated column-tile ownership: as in k_half_fused)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int nl = wave / WPN;
+    const int wl = (wave % WPN + nl * (WPN / 2)) % WPN;
+    const int voff = lane * 16;
+    const float* wnet = a.wp[nl];
+
+    // this wave's chunk of layer j: column tiles {wl, wl + 4, wl + 8, wl + 12} of a hidden layer, tile wl of the output layer
+    auto chunk = [&](auto jc) -> WChunk {
+        constexpr int j = decltype(jc)::value;
+        WChunk c;
+        c.wbase = wnet + G::woff(j);
+        c.wbytes = (unsigned)G::ipg(j) * (unsigned)G::ont(j) * 1024u;
+        c.ipg = G::ipg(j);
+        c.ont = G::ont(j);
+        c.boff = G::boff(j);
+        c.nt0 = wl;
+        c.nv = j == K - 1 ? 1 : 4;
+        c.layer = j;
+        return c;
+    };
+    const bool last_mine = wl < HG;  // (wave-uniform) the output layer has HG tiles for WPN waves
+
+    // ---- the first chunk's weights, then every other independent read of the prologue: rowptr of the tile and this
+    // wave's biases (one float per lane and column tile, K - 1 layers x 4 tiles + the output layer's), all into registers ----
+    f32x4 b_pre[kPF][4];
+    prefetch_chunk(chunk(std::integral_constant<int, 0>{}), WPN, voff, b_pre, true);
+    int rp_reg = 0;
+    if (tid <= TM) {
+        const int r = row0 + tid;
+        rp_reg = a.rowptr[r < a.n_nodes ? r : a.n_nodes];
+    }
+    const float* bnet = wnet + G::kBias + 16 * wl + (lane & 15);
+    BiasRegs<4> bias_h[K - 1];
+#pragma unroll
+    for (int j = 0; j < K - 1; ++j)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) bias_h[j].v[b] = bnet[G::boff(j) + 16 * WPN * b];
+    const BiasRegs<1> bias_o{{bnet[G::boff(K - 1) - (last_mine ? 0 : 16 * wl)]}};  // (a wave without a tile reads tile 0's: in bounds)
+    if (tid <= TM) s_rowptr[tid] = rp_reg;
+    __syncthreads();
+    const TileAgg ta{a.col, a.x_cond, a.ld, a.n_nodes, row0, H, IN0, IN0, a.mean, 0, a.eps, a.cond_copy};
+    tile_aggregate<TM, kFusedThreads, kColCap>(ta, s_rowptr, s_col, buf(0, 0), buf(1, 0), LS, nullptr, tid);
+    __syncthreads();
+
+    // ---- B: the K layers, unrolled; the chunk after a wave's last one is that chunk again (harmless re-load) ----
+    const float slope_h = a.act == GNF_ACT_RELU ? 0.f : a.alpha;
+    epi_static_for<K>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const float* in_lds = buf(nl, j & 1);
+        float* out_lds = buf(nl, (j & 1) ^ 1);
+        const WChunk c = chunk(jc);
+        if constexpr (j < K - 2) {
+            mlp_chunk<1, 4>(in_lds, LS, c, chunk(std::integral_constant<int, j + 1>{}), WPN, bias_h[j], out_lds, slope_h, lane, b_pre, EpiArgs{}, true);
+        } else if constexpr (j == K - 2) {
+            const WChunk nx = last_mine ? chunk(std::integral_constant<int, K - 1>{}) : c;
+            mlp_chunk<1, 4>(in_lds, LS, c, nx, WPN, bias_h[j], out_lds, slope_h, lane, b_pre, EpiArgs{}, true);
+        } else {
+            if (last_mine) mlp_chunk_thin(in_lds, LS, c, c, WPN, bias_o, out_lds, 1.f, lane, b_pre);
+        }
+        __syncthreads();
+    });
+
+    // ---- C ----
+    constexpr int pp = K & 1;
+    couple_tile<TM, false, false, false, true>(a, 0, 0, H, LS, buf(0, pp), buf(1, pp), buf(0, pp ^ 1), nullptr, red, tile, row0, tid, wave, lane);
+}
 
 // ------------------------------------------------------------------------------------------------
 static int max_padded_width(const GnfMlp* m) {
@@ -574,7 +720,9 @@ bool fused_supports_oop(const HalfStep& hs) {
 }
 
 // (MT, NETS) choice, from measurements on MI355X at L=256, K=5 (profiles/):
-//   (1,2) 16 nodes x both nets : 37.5 us per launch, any tile count <= 256 (one tile per CU)
+//   (1,2) 16 nodes x both nets : 37.5 us per launch, any tile count <= 256 (one tile per CU); 35.1 us since round 6, and
+//                                30.3 us in its compile-time-geometry instance (k_half_fused_geo: in0 = H = 32, L = 256,
+//                                K = 5, combine = agg - geo_matches below; any forced shape keeps the generic instance)
 //   (2,2) 32 nodes x both nets : 64 us per launch = 32 us per 16 nodes -> wins once there is more than
 //                                one 16-node tile per CU
 //   (*,1) one net per workgroup + k_coupling: never faster at these widths, but its LDS footprint is
@@ -747,6 +895,38 @@ bool fused_stash_shape(const GnfMlp* s, const GnfMlp* t, int64_t n) {
     return (n + 15) / 16 <= big_cu_count() && fused_lds_bytes(s, 1, 2) <= (size_t)kLdsLimit;
 }
 
+// The compile-time-geometry instance (k_half_fused_geo<IN0G, LG, K, HG>) takes a launch only when ALL of this holds; the
+// callers have already settled the rest of the rule (the (1,2) shape, not the large-batch form, no attention front-end):
+//   - no forced shape of any kind: gnf_set_option("force_shape", 12) is how tests and A/B runs reach the generic instance;
+//   - message-passing GNN with combine = agg, no MLP-row stash, no per-row log-det, no batch-norm moments;
+//   - the MLP is exactly in0 = 16 IN0G -> (K - 1) x 16 LG -> H = 16 HG, and its packed copy has the layout the kernel's
+//     constants (GeoLayout) were derived from.
+// The rule looks at the geometry only, never at the batch size: every batch of up to one tile per CU runs the same instance.
+template <int IN0G, int LG, int K, int HG>
+static bool geo_matches(const HalfStep& hs, const FusedArgs& a) {
+    using G = GeoLayout<IN0G, LG, K, HG>;
+    const GnfMlp* s = hs.s_net;
+    if (opt(OPT_FORCE_SHAPE) || s->attn || hs.mlp_stash || hs.row_logdet || a.bn_part || a.concat || a.h0[0]) return false;
+    if (a.K != K || a.H != 16 * HG || a.in0 != 16 * IN0G || s->dims[K] != 16 * HG) return false;
+    for (int j = 0; j < K; ++j) {
+        if (s->dims[j] != 16 * G::ipg(j) || a.ipg[j] != G::ipg(j) || a.ont[j] != G::ont(j) || a.boff[j] != G::boff(j)) return false;
+        if (a.wp[0][j] != a.wp[0][0] + G::woff(j) || a.wp[1][j] != a.wp[1][0] + G::woff(j)) return false;
+    }
+    return a.bias[0] == a.wp[0][0] + G::kBias && a.bias[1] == a.wp[1][0] + G::kBias && a.LS == G::kLS;
+}
+
+template <int IN0G, int LG, int K, int HG>
+static int launch_geo(const FusedArgs& a, unsigned tiles, hipStream_t st) {
+    GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_fused_geo<IN0G, LG, K, HG>),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit)));
+    const GeoArgs g{a.rowptr, a.col, a.x_cond, a.x_upd, a.x_upd_src, a.cond_copy, a.partials, a.sq_partials, {a.wp[0][0], a.wp[1][0]},
+                    a.ld, a.n_nodes, a.n_tiles, a.eps, a.alpha, a.mean, a.act, a.inverse};
+    constexpr size_t lds = GeoLayout<IN0G, LG, K, HG>::kLds;
+    hipLaunchKernelGGL((k_half_fused_geo<IN0G, LG, K, HG>), dim3(tiles), dim3(kFusedThreads), lds, st, g);
+    GNF_LAUNCH_CHECK("k_half_fused_geo");
+    return GNF_OK;
+}
+
 // the both-nets instance for this launch: plain, the attention front-end folded in (any geometry / the fixed one), or
 // two row tiles per workgroup - each as it is, or (ROWLD) leaving the per-row log-dets as well
 template <bool ROWLD>
@@ -907,6 +1087,9 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
             a.stash_mld = L.mld;
             rc = fold ? launch_shape<1, 2, true, true, true>(a, (unsigned)tiles, front_lds, st, &fa)
                       : launch_shape<1, 2, true>(a, (unsigned)tiles, lds + (size_t)L.mask_words * sizeof(unsigned long long), st);
+        } else if (MT == 1 && !fold && geo_matches<2, 16, 5, 2>(hs, a)) {
+            // the reference's default MLP (in0 = H = 32, L = 256, K = 5): what a plain benchmark run is sixteen launches of
+            rc = launch_geo<2, 16, 5, 2>(a, (unsigned)tiles, st);
         } else {
             rc = rowld ? launch_nets2<true>(a, MT, fold, fa, &rla, (unsigned)tiles, lds, front_lds, st)
                        : launch_nets2<false>(a, MT, fold, fa, nullptr, (unsigned)tiles, lds, front_lds, st);

@@ -169,10 +169,21 @@ struct EpiArgs {
     float act_slope;           // act' on the negative side (alpha, or 0 for relu)
 };
 
+// Where a chunk's biases come from: the layer's part of the LDS bias block (indexed by output column), or - the
+// compile-time-geometry instance, k_half_fused_geo - this lane's own values already in registers, one per tile slot.
+template <int NV>
+struct BiasRegs {
+    float v[NV];
+};
+__device__ __forceinline__ float chunk_bias(const float* lds, int, int col) { return lds[col]; }
+template <int NV>
+__device__ __forceinline__ float chunk_bias(const BiasRegs<NV>& r, int b, int) { return r.v[b]; }
+
 // One-tile chunk with every stage's operands in flight before the first MFMA (see chunk_is_thin).  Same arithmetic and
 // the same k order as mlp_chunk<1, 1>: bitwise the same result.  b_pre holds stages 0 .. 4 kPF - 1 (thin packing).
+template <class Bias>
 __device__ __forceinline__ void mlp_chunk_thin(const float* __restrict__ in_lds, int LS, const WChunk& c, const WChunk& nx,
-                                               int ts, const float* __restrict__ bias_lds, float* __restrict__ out_lds,
+                                               int ts, const Bias& bias_src, float* __restrict__ out_lds,
                                                float slope, int lane, f32x4 (&b_pre)[kPF][4]) {
     constexpr int NS = kThinStages, NP = 4 * kPF;
     const int lrow = lane & 15, lgrp = lane >> 4;
@@ -191,7 +202,7 @@ __device__ __forceinline__ void mlp_chunk_thin(const float* __restrict__ in_lds,
     const float* arow = in_lds + lrow * LS + 4 * lgrp;
 #pragma unroll
     for (int s = 0; s < NS; ++s) ast[s] = *reinterpret_cast<const f32x4*>(arow + 16 * (s < ipg ? s : ipg - 1));
-    const float bias = bias_lds[16 * c.nt0 + lrow];
+    const float bias = chunk_bias(bias_src, 0, 16 * c.nt0 + lrow);
     f32x4 acc = {bias, bias, bias, bias};
     prefetch_chunk(nx, ts, voff, b_pre, true);  // (b_pre was copied above)
     __builtin_amdgcn_sched_barrier(0);
@@ -209,9 +220,9 @@ __device__ __forceinline__ void mlp_chunk_thin(const float* __restrict__ in_lds,
 }
 
 // (entered with full exec: the MFMAs, and EPI_EX's v_writelane / v_readlane hand-over of the mask words, need all 64 lanes)
-template <int MT, int NV, int EPI = EPI_PLAIN>
+template <int MT, int NV, int EPI = EPI_PLAIN, class Bias = const float*>
 __device__ __forceinline__ void mlp_chunk(const float* __restrict__ in_lds, int LS, const WChunk& c,
-                                          const WChunk& nx, int ts, const float* __restrict__ bias_lds,
+                                          const WChunk& nx, int ts, const Bias& bias_src,
                                           float* __restrict__ out_lds, float slope, int lane,
                                           f32x4 (&b_pre)[kPF][4], const EpiArgs& ea = EpiArgs{}, bool thin_ok = false) {
     constexpr int PF = kPF;
@@ -221,7 +232,7 @@ __device__ __forceinline__ void mlp_chunk(const float* __restrict__ in_lds, int 
     f32x4 acc[MT][NV];
 #pragma unroll
     for (int b = 0; b < NV; ++b) {
-        const float bias = bias_lds[16 * (nt0 + ts * b) + lrow];
+        const float bias = chunk_bias(bias_src, b, 16 * (nt0 + ts * b) + lrow);
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[m][b] = f32x4{bias, bias, bias, bias};
     }
