@@ -1,0 +1,123 @@
+"""Stage 1 of the pipeline on the device: train the graph auto-encoder (the reference driver run_gnn.py's loop with its flag
+names, kept small) and save it where examples/train_grevnet_with_data.py --make_chunks --encoder_params FILE reads it.
+
+    python examples/run_gnn.py --dataset graph_rnn_community_small --num_train_iters 200 --save_path encoder.npz
+    python examples/train_grevnet_with_data.py --make_chunks --encoder_params encoder.npz --attn_type avg_then_mlp ...
+
+Batches come from datasets.GraphDataset (random Gaussian node features on the dataset's topologies); every iteration is
+train.EncoderTrainer.step (train-forward, binary_loss, backward, Adam); every --eval_every_n_steps a random test batch goes
+through encoder.evaluate, and the figures run_gnn.py:441-465 logs are printed.  The message-passing --attn_type values train;
+the attention ones exit with the library's GNF_EUNSUPPORTED text (their encoder backward is not built).
+
+As in the reference, a pair whose logit lies inside Keras' clip gets no gradient: unit-scale random
+features put nearly every pair of a fresh encoder's embeddings that far apart, and the loss then hardly moves.  A smaller
+--gaussian_scale (0.3) starts the pairs inside the clip's range."""
+import argparse
+import os
+import random
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from gnf_amd import _abi, adj_loss, datasets as D, encoder as E, gnn   # noqa: E402
+from gnf_amd.train import EncoderTrainer                                # noqa: E402
+
+MESSAGE_PASSING = {"avg_then_mlp": ("mean", "agg"), "sum_then_mlp": ("sum", "agg"), "sum_concat_then_mlp": ("sum", "concat"),
+                   "avg_concat_then_mlp": ("mean", "concat")}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dataset", default="graph_rnn_community_small")
+    ap.add_argument("--attn_type", default="avg_then_mlp", choices=list(MESSAGE_PASSING) + ["dm_attn"])
+    ap.add_argument("--node_embedding_dim", type=int, default=100)
+    ap.add_argument("--gaussian_scale", type=float, default=1.0)
+    ap.add_argument("--latent_dim", type=int, default=2048)
+    ap.add_argument("--num_layers", type=int, default=3)
+    ap.add_argument("--num_processing_steps", type=int, default=10)
+    ap.add_argument("--bias_init_stddev", type=float, default=0.3)
+    ap.add_argument("--node_weighting_epsilon", type=float, default=2.0)
+    ap.add_argument("--no_weight_sharing", action="store_true")
+    ap.add_argument("--no_batch_norm", action="store_true")
+    ap.add_argument("--use_layer_norm", action="store_true")
+    ap.add_argument("--no_residual", action="store_true")
+    ap.add_argument("--no_bn_test_local_stats", action="store_true")
+    ap.add_argument("--use_soft_labels", action="store_true")
+    ap.add_argument("--train_batch_size", type=int, default=8)
+    ap.add_argument("--num_train_iters", type=int, default=200000)
+    ap.add_argument("--log_every_n_steps", type=int, default=100)
+    ap.add_argument("--eval_every_n_steps", type=int, default=100)
+    ap.add_argument("--no_run_eval", action="store_true")
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--lr_type", default="polynomial_decay", choices=list(EncoderTrainer.LR_TYPES))
+    ap.add_argument("--lr_fixed_decay_steps", type=int, default=1000)
+    ap.add_argument("--lr_fixed_decay_rate", type=float, default=0.99)
+    ap.add_argument("--lr_fixed_decay_staircase", action="store_true")
+    ap.add_argument("--adam_beta1", type=float, default=0.9)
+    ap.add_argument("--adam_beta2", type=float, default=0.999)
+    ap.add_argument("--adam_epsilon", type=float, default=1e-8)
+    ap.add_argument("--random_seed", type=int, default=12345)
+    ap.add_argument("--save_path", default="encoder.npz")
+    F = ap.parse_args()
+    random.seed(F.random_seed)
+    np.random.seed(F.random_seed)
+    torch.manual_seed(F.random_seed)
+    gnn.set_random_seed(F.random_seed)
+    dev = torch.device("cuda", 0)
+
+    hp = dict(node_dim=F.node_embedding_dim, latent=F.latent_dim, K=F.num_layers, activation="leaky_relu",
+              bias_init_stddev=F.bias_init_stddev, num_timesteps=F.num_processing_steps, weight_sharing=not F.no_weight_sharing,
+              use_batch_norm=not F.no_batch_norm, use_layer_norm=F.use_layer_norm, residual=not F.no_residual,
+              test_local_stats=not F.no_bn_test_local_stats)
+    if F.attn_type in MESSAGE_PASSING:
+        agg, combine = MESSAGE_PASSING[F.attn_type]
+        hp.update(agg=agg, combine=combine, epsilon=F.node_weighting_epsilon if combine == "agg" else 0.0)
+    else:   # run_gnn.py's dm_attn defaults; the library refuses its backward pass below
+        hp.update(agg="sum", combine="agg", epsilon=0.0,
+                  attn=dict(num_heads=8, kq_dim=10, v_dim=10, out_dim=80, concat=True, kq_dim_division=False, residual=False))
+    enc = E.make_encoder(hp)
+    trainer = EncoderTrainer(enc, lr=F.lr, adam_beta1=F.adam_beta1, adam_beta2=F.adam_beta2, adam_epsilon=F.adam_epsilon,
+                             lr_type=F.lr_type, num_train_iters=F.num_train_iters, lr_fixed_decay_steps=F.lr_fixed_decay_steps,
+                             lr_fixed_decay_rate=F.lr_fixed_decay_rate, lr_fixed_decay_staircase=F.lr_fixed_decay_staircase,
+                             use_soft_labels=F.use_soft_labels)
+    dataset = D.GraphDataset(F.dataset, F.node_embedding_dim, F.gaussian_scale, seed=F.random_seed)
+
+    def log(prefix, it, n_node, res, out_nodes=None):
+        per_graph = adj_loss.incorrect_edges_per_graph(res).cpu().numpy()
+        total = float(adj_loss.total_incorrect_edges(res))
+        print("*" * 100)
+        print(f"iteration num: {it}")
+        print("NUM_NODES:NUM_INCORRECT")
+        print(", ".join(f"{a}:{b}" for a, b in zip(n_node.cpu().numpy(), per_graph)))
+        print(f"{prefix}sum loss: {float(res['sum_loss'])}")
+        print(f"{prefix}mean loss: {float(res['mean_loss'])}")
+        print(f"{prefix}total incorrect edges: {total}")
+        print(f"{prefix}incorrect edges per node: {total / max(int(n_node.sum()), 1)}")
+        print(f"{prefix}false positive edges: {float(adj_loss.false_positive_edges(res))}")
+        print(f"{prefix}false negative edges: {float(adj_loss.false_negative_edges(res))}")
+        if out_nodes is not None:
+            print(f"gnn output norm:{float(out_nodes.norm(dim=1).mean())}")
+
+    for iteration in range(F.num_train_iters):
+        graph = dataset.get_next_train_batch(F.train_batch_size, dev)
+        try:
+            res = trainer.step(graph)
+        except _abi.GnfError as e:
+            raise SystemExit(str(e))
+        if iteration % F.log_every_n_steps == 0:
+            log("", iteration, graph.n_node, res, res["gnn_output"].nodes)
+            print(f"learning rate: {trainer.current_learning_rate()}")
+            if not np.isfinite(float(res["sum_loss"])):
+                raise SystemExit("loss is not finite")
+        if not F.no_run_eval and iteration % F.eval_every_n_steps == 0:
+            test = dataset.get_random_test_batch(F.train_batch_size, dev)
+            log("eval ", iteration, test.n_node, E.evaluate(enc, test, use_soft_labels=F.use_soft_labels)["loss"])
+    E.save_encoder(F.save_path, hp, enc)
+    print(f"encoder saved to {F.save_path} after {trainer.global_step} steps")
+
+
+if __name__ == "__main__":
+    main()

@@ -186,10 +186,23 @@ _ENCODER_SIGNATURES = {
                                        C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/gnf_timestep_gnn_train.h (included by gnf.h behind gnf_timestep_gnn.h, added within ABI v10): the encoder's training
+# forward that keeps a stash, and its backward pass.  A table of its own for the same reason.
+_ENCODER_TRAIN_SIGNATURES = {
+    "gnf_timestep_gnn_stash_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.POINTER(GnfTimestepGnn)]),
+    "gnf_timestep_gnn_train_forward_f32": (C.c_int, [C.POINTER(GnfCsr), C.POINTER(GnfTimestepGnn), C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_timestep_gnn_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.POINTER(GnfTimestepGnn)]),
+    "gnf_timestep_gnn_backward_f32": (C.c_int, [C.POINTER(GnfCsr), C.POINTER(GnfCsr), C.POINTER(GnfTimestepGnn),
+                                                C.POINTER(GnfTimestepGnn), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 ORBIT_SYMBOLS = tuple(_ORBIT_SIGNATURES)
 ADJ_LOSS_SYMBOLS = tuple(_ADJ_LOSS_SIGNATURES)
 ENCODER_SYMBOLS = tuple(_ENCODER_SIGNATURES)
+ENCODER_TRAIN_SYMBOLS = tuple(_ENCODER_TRAIN_SIGNATURES)
 
 _lib = None
 
@@ -203,7 +216,8 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES,
+                                  **_ENCODER_TRAIN_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

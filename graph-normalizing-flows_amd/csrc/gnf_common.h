@@ -365,6 +365,32 @@ struct LnArgs {
 };
 int launch_layer_norm(const LnArgs& a, int nets, hipStream_t st);
 int launch_half_layer_norm(const HalfStep& hs, float* sbuf, float* tbuf, const float* xres, hipStream_t st);
+// ---- the encoder (gnf_timestep_gnn.hip: forward; gnf_timestep_gnn_train.hip: backward) ---------------------------------------
+static constexpr int64_t kEncMaxNodes = (int64_t)65535 * 128;   // training entry points: grid.y of the generic GEMM tile over the node axis
+static constexpr int kSntMaxWidth = 4096;   // widest batch norm: the normalising kernels keep per-column constants in LDS
+int validate_encoder(const GnfCsr* csr, const GnfTimestepGnn* g, int64_t ldx, int64_t ldo, int32_t D, const char* what);
+// ... and what the two training entry points add: message-passing nets only, is_training
+int validate_encoder_train(const GnfTimestepGnn* g, const char* what);
+// the training forward's stash (include/gnf_timestep_gnn_train.h), offsets in floats:
+//   in[i], i = 1 .. T-1 at (i - 1) * buf_floats  |  v[i], i = 0 .. T-1 at v_off + i * buf_floats (norms only)  |
+//   mean[i] at mom_off + 2 i dpad, var[i] at mom_off + (2 i + 1) dpad (bns only)
+struct EncoderStash {
+    bool norms;
+    size_t buf_floats, dpad, v_off, mom_off, total_bytes;
+};
+EncoderStash encoder_stash(int64_t n, int32_t D, const GnfTimestepGnn* g);
+// one-net forms of the layered path's / the generic backward's building blocks, for the encoder's backward:
+//   the hidden layers of one net again, exactly as launch_gnn_layered ran them (gnf_layered.hip): hidden[j] = layer j's output
+int launch_mlp_hidden(const GnfMlp* mlp, const float* h0, int64_t ld0, float* const* hidden, int64_t ldh, int64_t n,
+                      const GnfGnnSpec& g, hipStream_t st);
+//   dx = (dy W^T) * act'(h) through the generic GEMM tile (gnf_train.hip; h == NULL: no mask)
+int launch_linear_dx_one(const float* dy, int64_t lddy, const float* W, float* dx, int64_t lddx, const float* h, int64_t ldh,
+                         int64_t n, int32_t I, int32_t O, int act, float alpha, hipStream_t st);
+//   gw (+)= h^T dy, gb (+)= colsum dy: the slab GEMM over `chunks` runs of kchunk rows (a multiple of 32) and its fixed-order reduce
+int launch_weight_grad_one(const float* h, int64_t ldh, const float* dy, int64_t lddy, int64_t n, int32_t I, int32_t O,
+                           int32_t chunks, int64_t kchunk, float* wslab, float* bslab, float* gw, float* gb, int accumulate,
+                           hipStream_t st);
+
 // dst[r, 0:W) += src[r, 0:W)
 int launch_add_rows(float* dst, int64_t ldd, const float* src, int64_t lds_, int64_t n, int32_t W, hipStream_t st);
 

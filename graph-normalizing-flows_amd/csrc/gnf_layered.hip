@@ -529,12 +529,14 @@ int launch_finalize(const double* a, int64_t na, const double* b, int64_t nb, do
 // (j < K - 1: the training forward's stash of the hidden activations, row stride ldbuf)
 static int run_mlps(const GnfMlp* const* nets, int nj, const float* const* h0, int64_t ld0, float* const* bufA,
                     float* const* bufB, int64_t ldbuf, float* const* outp, int64_t ldout, int64_t n,
-                    const GnfGnnSpec& g, hipStream_t st, float* const* keep = nullptr, SlabSrc* fuse = nullptr) {
+                    const GnfGnnSpec& g, hipStream_t st, float* const* keep = nullptr, SlabSrc* fuse = nullptr,
+                    int layers = 0) {   // layers > 0: only the first `layers` layers run (the encoder backward's recompute)
     const GnfMlp* m = nets[0];
+    const int n_run = layers > 0 ? layers : m->num_layers;
     const float* in[2] = {h0[0], h0[nj - 1]};
     int64_t ldin = ld0;
     if (fuse) fuse->n_slab = 0;
-    for (int j = 0; j < m->num_layers; ++j) {
+    for (int j = 0; j < n_run; ++j) {
         const bool last = (j == m->num_layers - 1);
         if (fuse && nj == 2 && j + 2 == m->num_layers && linear_big_fused_last(m, j + 1) &&
             (int64_t)linear_big_fused_slabs(m->dims[j + 1]) * m->dims[j + 2] <= ldbuf) {
@@ -655,6 +657,17 @@ int launch_layer_norm(const LnArgs& a, int nets, hipStream_t st) {
     hipLaunchKernelGGL(k_layer_norm, dim3((unsigned)blocks, (unsigned)nets), dim3(256), 0, st, a);
     GNF_LAUNCH_CHECK("k_layer_norm");
     return GNF_OK;
+}
+
+// The hidden layers of one net again, exactly as launch_gnn_layered ran them (the same kernels on the same operands, so the
+// same bits and the same activation masks): layer j's output goes to hidden[j], j = 0 .. K-2, row stride ldh
+int launch_mlp_hidden(const GnfMlp* mlp, const float* h0, int64_t ld0, float* const* hidden, int64_t ldh, int64_t n,
+                      const GnfGnnSpec& g, hipStream_t st) {
+    if (mlp->num_layers < 2) return GNF_OK;
+    float* keep[GNF_MAX_LAYERS] = {};
+    for (int j = 0; j + 1 < mlp->num_layers; ++j) keep[j] = hidden[j];
+    float* none = nullptr;
+    return run_mlps(&mlp, 1, &h0, ld0, &none, &none, ldh, &none, 0, n, g, st, keep, nullptr, mlp->num_layers - 1);
 }
 
 // One GNN module call: the half-step scratch (HalfScratch) with one net's buffers in use

@@ -34,7 +34,7 @@ static constexpr int kSntRows = 16;       // rows per workgroup of the normalisi
 // partial rows launch_bn_stats leaves at most: bn_blocks cuts n rows into chunks of max(ceil(n / 16), 32) rows, so it never
 // yields more than 16 for any n (the workspace reserves exactly that many)
 static constexpr int kSntPartRows = 16;
-static constexpr int kSntMaxWidth = 4096; // inv | shift of every column in LDS: 32 KiB
+// (kSntMaxWidth, the widest batch norm - inv | shift of every column in LDS, 32 KiB - is in gnf_common.h: the backward shares it)
 
 struct SntNormArgs {
     const float* x;   // [n, D], leading dimension ldx: never written
@@ -198,8 +198,7 @@ static EncoderPlan encoder_plan(int64_t n, int32_t D, const GnfTimestepGnn* g) {
 
 static bool uses_batch_stats(const GnfTimestepGnn* g) { return g->is_training || g->test_local_stats; }
 
-static int validate_encoder(const GnfCsr* csr, const GnfTimestepGnn* g, int64_t ldx, int64_t ldo, int32_t D) {
-    const char* what = "gnf_timestep_gnn_f32";
+int validate_encoder(const GnfCsr* csr, const GnfTimestepGnn* g, int64_t ldx, int64_t ldo, int32_t D, const char* what) {
     int rc = validate_csr(csr);
     if (rc) return rc;
     if (!g || !g->nets) {
@@ -280,8 +279,10 @@ static int validate_encoder(const GnfCsr* csr, const GnfTimestepGnn* g, int64_t 
     return GNF_OK;
 }
 
+// keep_mean / keep_var (the training forward's stash, or NULL): where the batch moments go instead of bns[i].batch_mean /
+// batch_variance, which then receive a copy
 static int launch_snt_norm(const GnfTimestepGnn* g, int i, const float* x, int64_t ldx, float* y, int64_t n, int32_t D,
-                           double* part, hipStream_t st) {
+                           double* part, hipStream_t st, float* keep_mean = nullptr, float* keep_var = nullptr) {
     const GnfSntBatchNorm* b = &g->bns[i];
     SntNormArgs a;
     memset(&a, 0, sizeof(a));
@@ -291,7 +292,7 @@ static int launch_snt_norm(const GnfTimestepGnn* g, int i, const float* x, int64
         const int rc = launch_bn_stats(x, ldx, n, D, part, st, &rows);
         if (rc) return rc;
         a.part = part, a.nparts = rows;
-        a.batch_mean = b->batch_mean, a.batch_var = b->batch_variance;
+        a.batch_mean = keep_mean ? keep_mean : b->batch_mean, a.batch_var = keep_var ? keep_var : b->batch_variance;
     }
     a.gamma = b->gamma, a.beta = b->beta, a.moving_mean = b->moving_mean, a.moving_var = b->moving_variance;
     a.eps = g->bn_eps;
@@ -301,6 +302,110 @@ static int launch_snt_norm(const GnfTimestepGnn* g, int i, const float* x, int64
     const int64_t blocks = (n + kSntRows - 1) / kSntRows;
     hipLaunchKernelGGL(k_snt_norm, dim3((unsigned)blocks), dim3(256), (size_t)2 * D * sizeof(float), st, a);
     GNF_LAUNCH_CHECK("k_snt_norm");
+    if (keep_mean && b->batch_mean) {
+        const int rc = launch_copy_rows(keep_mean, D, b->batch_mean, D, 1, D, st);
+        if (rc) return rc;
+    }
+    if (keep_var && b->batch_variance) return launch_copy_rows(keep_var, D, b->batch_variance, D, 1, D, st);
+    return GNF_OK;
+}
+
+EncoderStash encoder_stash(int64_t n, int32_t D, const GnfTimestepGnn* g) {
+    EncoderStash s;
+    const size_t T = (size_t)g->num_timesteps;
+    s.norms = g->bns || g->lns;
+    s.buf_floats = ((size_t)n * (size_t)D + 63) / 64 * 64;
+    s.dpad = ((size_t)D + 63) / 64 * 64;
+    s.v_off = (T - 1) * s.buf_floats;
+    s.mom_off = s.v_off + (s.norms ? T * s.buf_floats : 0);
+    const size_t floats = s.mom_off + (g->bns ? 2 * T * s.dpad : 0);
+    s.total_bytes = (floats ? floats : 64) * sizeof(float);
+    return s;
+}
+
+// the walk of both forward entry points.  stash == NULL: gnf_timestep_gnn_f32, the rows ping-pong between two workspace
+// buffers.  Else the same launches write the rows the backward pass needs straight into their stash regions.
+static int run_encoder(const GnfCsr* csr, const GnfTimestepGnn* g, const float* x, int64_t ldx, float* out, int64_t ldo,
+                       int32_t D, float* stash, void* ws, hipStream_t st) {
+    const int64_t n = csr->n_nodes;
+    const EncoderPlan p = encoder_plan(n, D, g);
+    const EncoderStash sp = encoder_stash(n, D, g);
+    double* part = (double*)ws;
+    float* buf[2];
+    buf[0] = (float*)((char*)ws + p.part_bytes);
+    buf[1] = buf[0] + p.buf_floats;
+    float* scratch = buf[1] + p.buf_floats;
+    const int T = g->num_timesteps;
+    // the rows walk from x through the two buffers to out: every stage writes the buffer its input is not in
+    const float* cur = x;
+    int64_t ldc = ldx;
+    int rc;
+    for (int i = 0; i < T; ++i) {
+        if (g->bns || g->lns) {
+            float* dst = stash ? stash + sp.v_off + (size_t)i * sp.buf_floats : (cur == buf[0] ? buf[1] : buf[0]);
+            if (g->bns) {
+                float* km = stash ? stash + sp.mom_off + (size_t)(2 * i) * sp.dpad : nullptr;
+                rc = launch_snt_norm(g, i, cur, ldc, dst, n, D, part, st, km, km ? km + sp.dpad : nullptr);   // (with this timestep's layer norm, if any)
+            } else {
+                LnArgs a;
+                memset(&a, 0, sizeof(a));
+                a.job[0] = LnJob{cur, dst, nullptr, g->lns[i].gamma, g->lns[i].beta};
+                a.ldin = ldc, a.ldy = D, a.n = n, a.W = D;
+                rc = launch_layer_norm(a, 1, st);
+            }
+            if (rc) return rc;
+            cur = dst, ldc = D;
+        }
+        const bool last = i == T - 1;
+        float* dst = last ? out : (stash ? stash + (size_t)i * sp.buf_floats : (cur == buf[0] ? buf[1] : buf[0]));
+        const int64_t ldd = last ? ldo : D;
+        rc = launch_gnn_layered(csr->rowptr, csr->col, n, cur, ldc, D, g->gnn, &g->nets[g->weight_sharing ? 0 : i], dst, ldd,
+                                scratch, st, csr->node_offsets, csr->n_graphs);
+        if (rc) return rc;
+        cur = dst, ldc = ldd;
+    }
+    if (g->residual) return launch_add_rows(out, ldo, x, ldx, n, D, st);
+    return GNF_OK;
+}
+
+// what both forward entry points check behind validate_encoder
+static int check_forward_buffers(const char* what, int64_t n, int32_t D, const GnfTimestepGnn* g, const float* x, int64_t ldx,
+                                 const float* out, int64_t ldo, const void* ws, size_t ws_bytes) {
+    if (!x || !out || !ws) {
+        set_error("%s: null x/out/ws", what);
+        return GNF_EINVAL;
+    }
+    {
+        const uintptr_t x0 = (uintptr_t)x, x1 = x0 + ((size_t)(n - 1) * (size_t)ldx + (size_t)D) * sizeof(float);
+        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + ((size_t)(n - 1) * (size_t)ldo + (size_t)D) * sizeof(float);
+        if (x0 < o1 && o0 < x1) {
+            set_error("%s: x and out overlap (x is never written; the residual reads it last)", what);
+            return GNF_EINVAL;
+        }
+    }
+    if ((uintptr_t)ws % sizeof(double)) {
+        set_error("%s: ws must be 8-byte aligned (it starts with fp64 moment partials)", what);
+        return GNF_EINVAL;
+    }
+    const EncoderPlan p = encoder_plan(n, D, g);
+    if (ws_bytes < p.total_bytes) {
+        set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, p.total_bytes);
+        return GNF_EWORKSPACE;
+    }
+    return GNF_OK;
+}
+
+int validate_encoder_train(const GnfTimestepGnn* g, const char* what) {
+    const int n_nets = g->weight_sharing ? 1 : g->num_timesteps;
+    for (int q = 0; q < n_nets; ++q)
+        if (g->nets[q].attn) {
+            set_error("%s: net %d has an attention front-end; the encoder's backward pass covers the message-passing nets only", what, q);
+            return GNF_EUNSUPPORTED;
+        }
+    if (!g->is_training) {
+        set_error("%s: needs is_training (the backward pass goes through the batch moments)", what);
+        return GNF_EINVAL;
+    }
     return GNF_OK;
 }
 
@@ -317,66 +422,47 @@ size_t gnf_timestep_gnn_workspace_bytes(int64_t n_nodes, int32_t D, const GnfTim
 
 int gnf_timestep_gnn_f32(const GnfCsr* csr, const GnfTimestepGnn* g, const float* x, int64_t ldx, float* out, int64_t ldo,
                          int32_t D, void* ws, size_t ws_bytes, gnf_stream_t stream) {
-    int rc = validate_encoder(csr, g, ldx, ldo, D);
+    const char* what = "gnf_timestep_gnn_f32";
+    int rc = validate_encoder(csr, g, ldx, ldo, D, what);
     if (rc) return rc;
     const int64_t n = csr->n_nodes;
     if (n == 0) return GNF_OK;
-    if (!x || !out || !ws) {
-        set_error("gnf_timestep_gnn_f32: null x/out/ws");
+    rc = check_forward_buffers(what, n, D, g, x, ldx, out, ldo, ws, ws_bytes);
+    if (rc) return rc;
+    return run_encoder(csr, g, x, ldx, out, ldo, D, nullptr, ws, (hipStream_t)stream);
+}
+
+size_t gnf_timestep_gnn_stash_bytes(int64_t n_nodes, int32_t D, const GnfTimestepGnn* g) {
+    if (n_nodes < 0 || n_nodes > kEncMaxNodes || D < 1 || !g || !g->nets || g->num_timesteps < 1) return 0;
+    return encoder_stash(n_nodes, D, g).total_bytes;
+}
+
+int gnf_timestep_gnn_train_forward_f32(const GnfCsr* csr, const GnfTimestepGnn* g, const float* x, int64_t ldx, float* out,
+                                       int64_t ldo, int32_t D, void* stash, size_t stash_bytes, void* ws, size_t ws_bytes,
+                                       gnf_stream_t stream) {
+    const char* what = "gnf_timestep_gnn_train_forward_f32";
+    int rc = validate_encoder(csr, g, ldx, ldo, D, what);
+    if (rc) return rc;
+    rc = validate_encoder_train(g, what);
+    if (rc) return rc;
+    const int64_t n = csr->n_nodes;
+    if (n == 0) return GNF_OK;
+    if (n > kEncMaxNodes) {   // (the backward pass would refuse the stash: refused here already)
+        set_error("%s: n_nodes=%lld (at most %lld)", what, (long long)n, (long long)kEncMaxNodes);
+        return GNF_EUNSUPPORTED;
+    }
+    if (!stash || (uintptr_t)stash % sizeof(double)) {
+        set_error("%s: null or misaligned stash (8-byte alignment)", what);
         return GNF_EINVAL;
     }
-    {
-        const uintptr_t x0 = (uintptr_t)x, x1 = x0 + ((size_t)(n - 1) * (size_t)ldx + (size_t)D) * sizeof(float);
-        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + ((size_t)(n - 1) * (size_t)ldo + (size_t)D) * sizeof(float);
-        if (x0 < o1 && o0 < x1) {
-            set_error("gnf_timestep_gnn_f32: x and out overlap (x is never written; the residual reads it last)");
-            return GNF_EINVAL;
-        }
-    }
-    if ((uintptr_t)ws % sizeof(double)) {
-        set_error("gnf_timestep_gnn_f32: ws must be 8-byte aligned (it starts with fp64 moment partials)");
-        return GNF_EINVAL;
-    }
-    const EncoderPlan p = encoder_plan(n, D, g);
-    if (ws_bytes < p.total_bytes) {
-        set_error("gnf_timestep_gnn_f32: workspace %zu < %zu bytes", ws_bytes, p.total_bytes);
+    rc = check_forward_buffers(what, n, D, g, x, ldx, out, ldo, ws, ws_bytes);
+    if (rc) return rc;
+    const size_t need = encoder_stash(n, D, g).total_bytes;
+    if (stash_bytes < need) {
+        set_error("%s: stash %zu < %zu bytes", what, stash_bytes, need);
         return GNF_EWORKSPACE;
     }
-    hipStream_t st = (hipStream_t)stream;
-    double* part = (double*)ws;
-    float* buf[2];
-    buf[0] = (float*)((char*)ws + p.part_bytes);
-    buf[1] = buf[0] + p.buf_floats;
-    float* scratch = buf[1] + p.buf_floats;
-    const int T = g->num_timesteps;
-    // the rows walk from x through the two buffers to out: every stage writes the buffer its input is not in
-    const float* cur = x;
-    int64_t ldc = ldx;
-    for (int i = 0; i < T; ++i) {
-        if (g->bns || g->lns) {
-            float* dst = cur == buf[0] ? buf[1] : buf[0];
-            if (g->bns) {
-                rc = launch_snt_norm(g, i, cur, ldc, dst, n, D, part, st);   // (with this timestep's layer norm, if any)
-            } else {
-                LnArgs a;
-                memset(&a, 0, sizeof(a));
-                a.job[0] = LnJob{cur, dst, nullptr, g->lns[i].gamma, g->lns[i].beta};
-                a.ldin = ldc, a.ldy = D, a.n = n, a.W = D;
-                rc = launch_layer_norm(a, 1, st);
-            }
-            if (rc) return rc;
-            cur = dst, ldc = D;
-        }
-        const bool last = i == T - 1;
-        float* dst = last ? out : (cur == buf[0] ? buf[1] : buf[0]);
-        const int64_t ldd = last ? ldo : D;
-        rc = launch_gnn_layered(csr->rowptr, csr->col, n, cur, ldc, D, g->gnn, &g->nets[g->weight_sharing ? 0 : i], dst, ldd,
-                                scratch, st, csr->node_offsets, csr->n_graphs);
-        if (rc) return rc;
-        cur = dst, ldc = ldd;
-    }
-    if (g->residual) return launch_add_rows(out, ldo, x, ldx, n, D, st);
-    return GNF_OK;
+    return run_encoder(csr, g, x, ldx, out, ldo, D, (float*)stash, ws, (hipStream_t)stream);
 }
 
 }  // extern "C"

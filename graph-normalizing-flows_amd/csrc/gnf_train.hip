@@ -2013,6 +2013,48 @@ static int mlp_backward_generic(const BwdPlan& p, const BwdOperands& o, const Gn
     return GNF_OK;
 }
 
+// ---- one-net forms of the generic building blocks (the encoder's backward, gnf_timestep_gnn_train.hip) -----------------------
+// dx [n, I] = (dy [n, O] W^T) * act'(h)   (h [n, I], leading dimension ldh: the layer's activated input; NULL: no mask)
+int launch_linear_dx_one(const float* dy, int64_t lddy, const float* W, float* dx, int64_t lddx, const float* h, int64_t ldh,
+                         int64_t n, int32_t I, int32_t O, int act, float alpha, hipStream_t st) {
+    if (n == 0) return GNF_OK;
+    GemmJob job{dy, W, dx, h, nullptr};
+    GemmShape sh;
+    memset(&sh, 0, sizeof(sh));
+    sh.lda = lddy, sh.ldb = O, sh.ldc = lddx, sh.ldaux = ldh;
+    sh.M = n, sh.K = O, sh.N = I, sh.chunks = 1, sh.kchunk = TGK;
+    sh.act = act, sh.alpha = alpha;
+    return launch_gemm<OPND_KC, OPND_KC, EPI_MASK>(&job, 1, sh, st);
+}
+
+// gw [I, O] (+)= h^T dy, gb [O] (+)= colsum dy over the n rows: the rows are cut into `chunks` runs of kchunk (a multiple of
+// 32) whose products and column sums land in wslab [chunks][I * O] / bslab [chunks][O]; k_reduce_grouped adds them in chunk order
+int launch_weight_grad_one(const float* h, int64_t ldh, const float* dy, int64_t lddy, int64_t n, int32_t I, int32_t O,
+                           int32_t chunks, int64_t kchunk, float* wslab, float* bslab, float* gw, float* gb, int accumulate,
+                           hipStream_t st) {
+    if (n == 0) return GNF_OK;
+    GemmJob job{h, dy, wslab, nullptr, bslab};
+    GemmShape sh;
+    memset(&sh, 0, sizeof(sh));
+    sh.lda = ldh, sh.ldb = lddy, sh.ldc = O;
+    sh.M = I, sh.K = n, sh.N = O, sh.chunks = chunks, sh.kchunk = kchunk;
+    int rc = launch_gemm<OPND_MC, OPND_MC, EPI_SLAB>(&job, 1, sh, st);
+    if (rc) return rc;
+    GroupedReduce g;
+    memset(&g, 0, sizeof(g));
+    g.job[0] = ReduceJob{wslab, bslab, gw, gb};
+    g.nw[0] = (int64_t)I * O, g.nb[0] = O, g.chunks[0] = chunks, g.accumulate = accumulate;
+    if (!reduce_index_space(&g, 1)) {
+        set_error("weight gradient of %d x %d: too large for one reduce launch", I, O);
+        return GNF_EUNSUPPORTED;
+    }
+    int64_t blocks = (((int64_t)I * O + 3) / 4 + O + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    hipLaunchKernelGGL(k_reduce_grouped, dim3((unsigned)blocks), dim3(256), 0, st, g, 1);
+    GNF_LAUNCH_CHECK("k_reduce_grouped");
+    return GNF_OK;
+}
+
 }  // namespace gnf
 
 using namespace gnf;

@@ -1,6 +1,6 @@
 """What consumes the encoder's forward pass (gnn.TimestepGNN, gnf_timestep_gnn_f32): the evaluation figures run_gnn.py logs
-and the embedding chunks the GRevNet flow is trained on.  Both run the encoder with is_training=False; training the encoder
-(its backward pass) is not part of the library.
+and the embedding chunks the GRevNet flow is trained on.  Both run the encoder with is_training=False; training the encoder is
+train.EncoderTrainer (gnn.TimestepGNN.forward_train / backward), whose result save_encoder stores.
 
   evaluate                 run_gnn.py:441-465: encoder -> adj_loss.binary_loss and its counts
   write_embedding_chunks   generate_grevnet_training_data.py:78-120: encoder outputs cut into chunk files

@@ -1014,8 +1014,9 @@ class RowLayerNorm:
 class TimestepGNN:
     """gnn.py:183-235: runs the input GNN for num_timesteps timesteps - per timestep an optional snt.BatchNorm(scale=True),
     an optional snt.LayerNorm(), then the GNN (one shared GNN with weight_sharing, the norms stay per timestep) - and adds
-    the input nodes at the end when `residual`.  `__call__(graph, is_training)` as the reference's; forward only (its
-    backward pass and a trainer are not here).  One library call, gnf_timestep_gnn_f32 (include/gnf_timestep_gnn.h):
+    the input nodes at the end when `residual`.  `__call__(graph, is_training)` as the reference's; `forward_train` /
+    `backward` (include/gnf_timestep_gnn_train.h) are the pair a training step is made of (train.EncoderTrainer), for the
+    message-passing GNNs.  `__call__` is one library call, gnf_timestep_gnn_f32 (include/gnf_timestep_gnn.h):
     asynchronous, nothing read back, capturable once the variables exist (make one eager call first).  With
     use_batch_norm, a call with is_training=True updates the moving statistics on the device (what UPDATE_OPS does,
     run_gnn.py:295-296); `last_batch_moments` is [(batch_mean, batch_variance)] * T of the last call if it took batch
@@ -1137,3 +1138,128 @@ class TimestepGNN:
 
     def __call__(self, graph, is_training):
         return self._build(graph, is_training)
+
+    # ---- training: forward with a stash, backward (include/gnf_timestep_gnn_train.h) -------------------------------------------
+    def _prepare(self, graph):
+        x = graph.nodes
+        if x.device.type != "cuda":
+            raise _abi.GnfError("TimestepGNN runs on a HIP device only (no CPU path)")
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise ValueError(f"nodes must be [N, D] with D >= 1; got {tuple(x.shape)}")
+        x = x.to(torch.float32)
+        n, d = x.shape
+        if n > 0 and (x.stride(1) != 1 or x.stride(0) < d):
+            x = x.contiguous()
+        return x, int(n), int(d), (x.stride(0) if n > 1 else max(int(x.stride(0)), d))
+
+    def forward_train(self, graph):
+        """`self(graph, True)` - the same launches, the same bits, the same moving-average update - that also returns the
+        stash `backward` needs: (GraphsTuple, EncoderStash).  The stash holds O(T N D) floats (the rows that entered every
+        timestep and every GNN, the batch moments), never an MLP's hidden rows.  gnf_timestep_gnn_train_forward_f32."""
+        lib = _abi.lib()
+        x, n, d, ldx = self._prepare(graph)
+        dev = x.device
+        desc, keep = self._desc(d, dev, True)
+        csr = csr_desc(graph, csr_of(graph), self.blocks()[0].graph_scope)
+        out = torch.empty((n, d), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws_bytes = lib.gnf_timestep_gnn_workspace_bytes(n, d, C.byref(desc))
+            st_bytes = lib.gnf_timestep_gnn_stash_bytes(n, d, C.byref(desc))
+            ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+            buf = torch.empty(max(st_bytes, 8), dtype=torch.uint8, device=dev)
+            _abi.check(lib.gnf_timestep_gnn_train_forward_f32(C.byref(csr), C.byref(desc), _abi.ptr(x), ldx, _abi.ptr(out), d, d,
+                                                              _abi.ptr(buf), st_bytes, _abi.ptr(ws), ws_bytes,
+                                                              _abi.stream_ptr(dev)), "gnf_timestep_gnn_train_forward_f32")
+        del keep
+        self.last_batch_moments = [(b.batch_mean, b.batch_variance) for b in self.bns] if self.bns and n > 0 else None
+        return graph.replace(nodes=out), EncoderStash(buf, st_bytes, x, ldx)
+
+    def make_grads(self, d, device):
+        """Zeroed gradient tensors in get_params()'s layout (without the moving statistics), for `backward`:
+        {"nets": [[(dW, db), ...]] * (T or 1), "bn": [{"gamma", "beta"}] * T, "ln": [{"gamma", "beta"}] * T}"""
+        _desc, keep = self._desc(int(d), torch.device(device), True)
+        z = lambda t: torch.zeros_like(t, dtype=torch.float32, device=device)
+        out = {"nets": [[(z(w), z(b)) for (w, b) in m.params] for m in keep[4]]}
+        if self.bns:
+            out["bn"] = [{"gamma": z(b.gamma), "beta": z(b.beta)} for b in self.bns]
+        if self.lns:
+            out["ln"] = [{"gamma": z(l.gamma), "beta": z(l.beta)} for l in self.lns]
+        return out
+
+    def _grad_desc(self, grads, d, dev):
+        """GnfTimestepGnn whose parameter pointers are the caller's gradient tensors (shapes checked here)"""
+        mlps = [b._mlp for b in self.blocks()]
+        if len(grads["nets"]) != len(mlps):
+            raise ValueError(f"grads has {len(grads['nets'])} nets, the encoder {len(mlps)}")
+
+        def ok(t, like):
+            if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous()
+                    or tuple(t.shape) != tuple(like.shape)):
+                raise ValueError(f"a gradient tensor must be a contiguous float32 {tuple(like.shape)} tensor on {dev}")
+            return t.data_ptr()
+        nets = (_abi.GnfMlp * len(mlps))()
+        for q, (m, layers) in enumerate(zip(mlps, grads["nets"])):
+            if len(layers) != len(m.params):
+                raise ValueError(f"grads net {q} has {len(layers)} layers, the encoder's {len(m.params)}")
+            nets[q].num_layers = len(m.layer_sizes)
+            for j, w in enumerate(m.dims()):
+                nets[q].dims[j] = w
+            for j, ((gw, gb), (w, b)) in enumerate(zip(layers, m.params)):
+                nets[q].W[j], nets[q].b[j] = ok(gw, w), ok(gb, b)
+        bn_arr = ln_arr = None
+        if self.bns:
+            bn_arr = (_abi.GnfSntBatchNorm * self.num_timesteps)()
+            for q, (b, gd) in enumerate(zip(self.bns, grads["bn"])):
+                bn_arr[q].gamma, bn_arr[q].beta = ok(gd["gamma"], b.gamma), ok(gd["beta"], b.beta)
+        if self.lns:
+            ln_arr = (_abi.GnfRowNorm * self.num_timesteps)()
+            for q, (l, gd) in enumerate(zip(self.lns, grads["ln"])):
+                ln_arr[q].gamma, ln_arr[q].beta = ok(gd["gamma"], l.gamma), ok(gd["beta"], l.beta)
+        desc = _abi.GnfTimestepGnn(self.num_timesteps, int(self.weight_sharing), C.cast(nets, C.POINTER(_abi.GnfMlp)),
+                                   self.blocks()[0].spec(),
+                                   C.cast(bn_arr, C.POINTER(_abi.GnfSntBatchNorm)) if bn_arr is not None else None,
+                                   C.cast(ln_arr, C.POINTER(_abi.GnfRowNorm)) if ln_arr is not None else None,
+                                   int(self.residual), 1, int(self.test_local_stats), float(self.bn_eps), float(self.bn_decay_rate))
+        return desc, (nets, bn_arr, ln_arr)
+
+    def backward(self, graph, stash, grad_out, grads, want_grad_x=False):
+        """dL/d(parameters) into the caller's `grads` (make_grads' layout; overwritten) from grad_out = dL/d(output nodes)
+        [N, D] and the stash of the `forward_train` call on the same graph and parameters; returns dL/d(input nodes) with
+        want_grad_x, else None.  gnf_timestep_gnn_backward_f32: asynchronous, nothing read back, no float atomics."""
+        lib = _abi.lib()
+        if not isinstance(stash, EncoderStash):
+            raise TypeError("stash: what forward_train returned")
+        x, ldx = stash.x, stash.ldx
+        n, d = int(x.shape[0]), int(x.shape[1])
+        dev = x.device
+        if grad_out.device.type != "cuda":
+            raise _abi.GnfError("TimestepGNN runs on a HIP device only (no CPU path)")
+        if tuple(grad_out.shape) != (n, d) or int(graph.nodes.shape[0]) != n:
+            raise ValueError(f"grad_out {tuple(grad_out.shape)} and the graph's nodes must be [{n}, {d}] as in forward_train")
+        g = grad_out.to(torch.float32)
+        if n > 0 and (g.stride(1) != 1 or g.stride(0) < d):
+            g = g.contiguous()
+        ldg = g.stride(0) if n > 1 else max(int(g.stride(0)), d)
+        desc, keep = self._desc(d, dev, True)
+        gdesc, gkeep = self._grad_desc(grads, d, dev)
+        csr = csr_desc(graph, csr_of(graph), self.blocks()[0].graph_scope)
+        csr_t = csr_of(graph, by_sender=True)
+        gx = torch.empty((n, d), dtype=torch.float32, device=dev) if want_grad_x else None
+        with torch.cuda.device(dev):
+            ws_bytes = lib.gnf_timestep_gnn_backward_workspace_bytes(n, d, C.byref(desc))
+            ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+            _abi.check(lib.gnf_timestep_gnn_backward_f32(C.byref(csr), C.byref(csr_t.desc), C.byref(desc), C.byref(gdesc), _abi.ptr(x),
+                                                         ldx, _abi.ptr(g), ldg, _abi.ptr(gx), d, d, _abi.ptr(stash.buf), stash.nbytes,
+                                                         _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                       "gnf_timestep_gnn_backward_f32")
+        del keep, gkeep
+        return gx
+
+
+class EncoderStash:
+    """What TimestepGNN.forward_train leaves for TimestepGNN.backward: the library's stash buffer and the input rows it
+    belongs to (kept alive and unchanged until the backward pass has run)."""
+    __slots__ = ("buf", "nbytes", "x", "ldx")
+
+    def __init__(self, buf, nbytes, x, ldx):
+        self.buf, self.nbytes, self.x, self.ldx = buf, int(nbytes), x, int(ldx)

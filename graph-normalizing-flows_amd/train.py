@@ -457,3 +457,187 @@ def save_checkpoint(tr, path):
 
 def load_checkpoint(tr, path):
     load_trainer_state(tr, torch.load(path, map_location="cpu"))
+
+
+# ==== stage 1: the graph auto-encoder's training step (run_gnn.py:230-296) ======================================================
+class EncoderTrainer:
+    """total_loss = binary_loss' sum_loss (run_gnn.py:255-270; the reference's regularisers are commented out, gnn.py:175-178),
+    its gradient through gnn.TimestepGNN and the Adam update, for the message-passing GNNs:
+
+        gnn(graph, is_training=True)                  -> gnf_timestep_gnn_train_forward_f32 (the moving statistics advance here,
+                                                         once per step: what the UPDATE_OPS dependency does, run_gnn.py:295)
+        binary_loss(gnn_output, true_graph, ...)      -> gnf_adj_loss_f32 with grad="sum"
+        optimizer.minimize(total_loss)                -> gnf_timestep_gnn_backward_f32 + gnf_adam_f32
+
+    Every trainable variable (the nets' W / b, the batch norms' and layer norms' gamma / beta) lives in ONE flat fp32 device
+    vector `theta`, the gradient and Adam's two moment vectors share its layout, so the optimiser is one launch.  The defaults
+    are run_gnn.py's flags (lr 1e-4, beta1 0.9, beta2 0.999, epsilon 1e-8, lr_type polynomial_decay over num_train_iters
+    200000); lr_type "schedule" is not built.  No clipping: run_gnn.py has none.  With max_nodes_per_graph given,
+    loss_and_grads neither copies to the host nor synchronises and can be captured; apply_gradients is one more launch whose
+    step size is a host scalar that changes every step (it is passed by value, so it stays outside a captured region)."""
+
+    LR_TYPES = ("constant", "fixed_decay", "polynomial_decay")
+
+    def __init__(self, encoder, lr=1e-4, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, lr_type="polynomial_decay",
+                 num_train_iters=200000, lr_fixed_decay_steps=1000, lr_fixed_decay_rate=0.99, lr_fixed_decay_staircase=False,
+                 distance_fn=None, use_soft_labels=False, max_nodes_per_graph=None):
+        from .flow import scaled_hacky_sigmoid_l2
+        if lr_type not in self.LR_TYPES:
+            raise ValueError(f"lr_type={lr_type!r}: one of {self.LR_TYPES} ('schedule' is not built)")
+        self.net = encoder
+        self.lr, self.beta1, self.beta2, self.epsilon = float(lr), float(adam_beta1), float(adam_beta2), float(adam_epsilon)
+        self.lr_type, self.num_train_iters = lr_type, int(num_train_iters)
+        self.lr_fixed_decay_steps, self.lr_fixed_decay_rate = int(lr_fixed_decay_steps), float(lr_fixed_decay_rate)
+        self.lr_fixed_decay_staircase = bool(lr_fixed_decay_staircase)
+        self.distance_fn = scaled_hacky_sigmoid_l2 if distance_fn is None else distance_fn
+        self.use_soft_labels = bool(use_soft_labels)
+        self.max_nodes_per_graph = max_nodes_per_graph
+        self.global_step = 0
+        self.theta = self.grad = self.m = self.v = None
+        self._grads = None     # views of self.grad in TimestepGNN.make_grads' layout
+        self._bound = None     # [(owner description, data_ptr)] of every view handed out: detects a set_params since
+
+    # ---- parameter arena ---------------------------------------------------------------------
+    def _variables(self):
+        """[(get, set, tensor)] in arena order: nets (W, b per layer), then bn gamma / beta per timestep, then ln"""
+        out = []
+        for m in (b._mlp for b in self.net.blocks()):
+            for j in range(len(m.params)):
+                out.append((m, j, 0)), out.append((m, j, 1))
+        for o in list(self.net.bns) + list(self.net.lns):
+            out.append((o, "gamma", None)), out.append((o, "beta", None))
+        return out
+
+    @staticmethod
+    def _get(var):
+        o, k, h = var
+        return o.params[k][h] if h is not None else getattr(o, k)
+
+    def _ensure_arena(self, d, device):
+        net = self.net
+        device = torch.device(device)
+        net._desc(d, device, True)               # creates the variables at first connection (Sonnet style)
+        variables = self._variables()
+        if self.theta is not None and self.theta.device == device and \
+                [self._get(v).data_ptr() for v in variables] == self._bound:
+            return
+        old_m, old_v = self.m, self.v
+        tensors = [self._get(v) for v in variables]
+        total = sum(t.numel() for t in tensors)
+        theta = torch.empty(total, dtype=torch.float32, device=device)
+        grad = torch.zeros_like(theta)
+        views, gviews, off = [], [], 0
+        for t in tensors:
+            view = theta[off:off + t.numel()].view(t.shape)
+            view.copy_(t)
+            views.append(view)
+            gviews.append(grad[off:off + t.numel()].view(t.shape))
+            off += t.numel()
+        it, git = iter(views), iter(gviews)
+        grads = {"nets": []}
+        for m in (b._mlp for b in net.blocks()):
+            m.params = [(next(it), next(it)) for _ in m.params]
+            m.version += 1
+            _gnn_touch()
+            grads["nets"].append([(next(git), next(git)) for _ in m.params])
+        for key, objs in (("bn", net.bns), ("ln", net.lns)):
+            if objs:
+                grads[key] = []
+                for o in objs:
+                    o.gamma, o.beta = next(it), next(it)
+                    grads[key].append({"gamma": next(git), "beta": next(git)})
+        keep = old_m is not None and old_m.numel() == total and old_m.device == device
+        self.theta, self.grad, self._grads = theta, grad, grads
+        self.m = old_m if keep else torch.zeros_like(theta)
+        self.v = old_v if keep else torch.zeros_like(theta)
+        self._bound = [self._get(v).data_ptr() for v in variables]
+
+    def named_gradients(self):
+        """The gradients in TimestepGNN.get_params()'s layout (without the moving statistics) as numpy arrays (host copy)."""
+        cp = lambda t: t.detach().cpu().numpy().copy()
+        out = {"nets": [[(cp(w), cp(b)) for (w, b) in net] for net in self._grads["nets"]]}
+        for key in ("bn", "ln"):
+            if key in self._grads:
+                out[key] = [{k: cp(v) for k, v in d.items()} for d in self._grads[key]]
+        return out
+
+    # ---- compute_gradients -----------------------------------------------------------------------
+    def loss_and_grads(self, graph, true_graph=None):
+        """Train-forward, binary_loss against true_graph (default: the batch itself; another one is the denoising case of
+        run_gnn.py:238) and the backward pass.  Leaves the gradient of total_loss = sum_loss in self.grad and returns
+        binary_loss' result dict plus "gnn_output" and "total_loss" (device tensors, nothing read back)."""
+        from . import adj_loss
+        x = graph.nodes
+        if x.device.type != "cuda":
+            raise _abi.GnfError("training runs on a HIP device only (no CPU path)")
+        self._ensure_arena(int(x.shape[1]), x.device)
+        out, stash = self.net.forward_train(graph)
+        res = adj_loss.binary_loss(out, graph if true_graph is None else true_graph, distance_fn=self.distance_fn,
+                                   use_soft_labels=self.use_soft_labels, grad="sum",
+                                   max_nodes_per_graph=self.max_nodes_per_graph)
+        self.net.backward(graph, stash, res["grad_nodes"], self._grads)
+        res["gnn_output"], res["total_loss"] = out, res["sum_loss"]
+        return res
+
+    # ---- apply_gradients -------------------------------------------------------------------------
+    def current_learning_rate(self):
+        """run_gnn.py:275-288 on the host: constant | tf.train.exponential_decay | tf.train.polynomial_decay(decay_steps =
+        num_train_iters, end_learning_rate = lr / 100, power = 0.5)"""
+        return encoder_learning_rate(self.lr_type, self.lr, self.global_step, self.num_train_iters, self.lr_fixed_decay_steps,
+                                     self.lr_fixed_decay_rate, self.lr_fixed_decay_staircase)
+
+    def apply_gradients(self, learning_rate=None):
+        """tf.train.AdamOptimizer(lr, beta1, beta2, epsilon).apply_gradients: one gnf_adam_f32 over the arena"""
+        lib = _abi.lib()
+        dev = self.theta.device
+        lr = self.current_learning_rate() if learning_rate is None else float(learning_rate)
+        t = self.global_step + 1
+        lr_t = lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
+        with torch.cuda.device(dev):
+            _abi.check(lib.gnf_adam_f32(_abi.ptr(self.theta), _abi.ptr(self.grad), _abi.ptr(self.m), _abi.ptr(self.v),
+                                        self.theta.numel(), lr_t, self.beta1, self.beta2, self.epsilon, _abi.stream_ptr(dev)),
+                       "gnf_adam_f32")
+        self.global_step = t
+
+    def step(self, graph, true_graph=None, learning_rate=None):
+        """One iteration of run_gnn.py's loop: returns loss_and_grads' dict."""
+        out = self.loss_and_grads(graph, true_graph)
+        self.apply_gradients(learning_rate)
+        return out
+
+
+def encoder_learning_rate(lr_type, lr, global_step, num_train_iters=200000, decay_steps=1000, decay_rate=0.99, staircase=False):
+    """run_gnn.py:275-288 (pure arithmetic)"""
+    if lr_type == "constant":
+        return float(lr)
+    if lr_type == "fixed_decay":                 # tf.train.exponential_decay
+        p = global_step / float(decay_steps)
+        return lr * decay_rate ** (math.floor(p) if staircase else p)
+    if lr_type == "polynomial_decay":            # tf.train.polynomial_decay, cycle=False
+        end = lr / 100.0
+        s = min(global_step, num_train_iters)
+        return (lr - end) * (1.0 - s / float(num_train_iters)) ** 0.5 + end
+    raise ValueError(f"lr_type={lr_type!r}")
+
+
+def encoder_trainer_state(tr):
+    """What a resumed encoder run needs: parameters, Adam moments, step counter, the batch norms' moving statistics."""
+    if tr.theta is None:
+        raise RuntimeError("run a step (or loss_and_grads) first so that the variables exist")
+    return {"theta": tr.theta.detach().cpu(), "m": tr.m.detach().cpu(), "v": tr.v.detach().cpu(), "global_step": tr.global_step,
+            "bn_moving": [(b.moving_mean.detach().cpu(), b.moving_variance.detach().cpu()) for b in tr.net.bns]}
+
+
+def load_encoder_trainer_state(tr, state):
+    """Restore encoder_trainer_state's dict into a connected trainer."""
+    if tr.theta is None:
+        raise RuntimeError("connect the trainer first (run loss_and_grads on a batch)")
+    if state["theta"].numel() != tr.theta.numel():
+        raise ValueError(f"checkpoint has {state['theta'].numel()} parameters, the encoder has {tr.theta.numel()}")
+    tr.theta.copy_(state["theta"])
+    tr.m.copy_(state["m"])
+    tr.v.copy_(state["v"])
+    tr.global_step = int(state["global_step"])
+    for b, (mm, mv) in zip(tr.net.bns, state["bn_moving"]):
+        b.moving_mean.copy_(mm)
+        b.moving_variance.copy_(mv)

@@ -512,6 +512,8 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 #include "gnf_adj_loss.h"
 /* Added within ABI v10: the encoder's forward pass, TimestepGNN with its batch / layer norms (gnf_timestep_gnn.h) - likewise. */
 #include "gnf_timestep_gnn.h"
+/* Added within ABI v10: the encoder's training forward (with a stash) and its backward pass (gnf_timestep_gnn_train.h) - likewise. */
+#include "gnf_timestep_gnn_train.h"
 
 #ifdef __cplusplus
 }

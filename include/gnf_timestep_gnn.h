@@ -9,8 +9,9 @@
 
 /* Added within ABI v10 (new entry points only: no existing signature or struct changed, GNF_ABI_VERSION stays 10).
  * The encoder of the graph auto-encoder (built at run_gnn.py:230-239): num_timesteps GNN module calls in a row on the
- * nodes of one batch, each optionally preceded by a batch norm and / or a layer norm, and a final residual.  Forward only,
- * in training and in evaluation mode; its backward pass is not part of the library.
+ * nodes of one batch, each optionally preceded by a batch norm and / or a layer norm, and a final residual.  This header is
+ * the forward pass, in training and in evaluation mode; the training forward that keeps a stash and the backward pass are
+ * in gnf_timestep_gnn_train.h.
  *
  *   nodes = x
  *   for i in 0 .. T-1, in this order (gnn.py:219-232):
