@@ -116,13 +116,53 @@ int launch_pack_mlp(const GnfMlp* m, float* packed, hipStream_t st) {
 #include "gnf_attn_front_dev.h"
 namespace gnf {
 
+// Diagnostic build only (-DGNF_TRACE, tools/probe_trace.py; never the shipped library): every wave of the instance stamps
+// the cycle counter (s_memtime) at the phase boundaries into LDS, and the waves of workgroup 0 and of the mid-grid workgroup
+// copy their stamps to a buffer nothing else reads.  Slots: 0 entry, 1 behind barrier 1 (rowptr in LDS), 2 behind the col
+// barrier, 3 behind the gather barrier, 4 + 2 j the operands of layer j's first MFMA have landed (the stamp waits for this
+// wave's stage-0 weights), 5 + 2 j behind layer j's barrier, kTraceCoupled behind the coupling store, kTraceEnd kernel end.
+#ifdef GNF_TRACE
+static constexpr int kTraceSlots = 32, kTraceCoupled = kTraceSlots - 2, kTraceEnd = kTraceSlots - 1;
+__shared__ unsigned long long s_trace[kFusedThreads / 64][kTraceSlots];
+static unsigned long long* g_trace_buf = nullptr;
+static int g_trace_cap = 0, g_trace_next = 0;
+// launches take the slots 0 .. cap - 1 of buf in turn ([cap][2][8][kTraceSlots] uint64); NULL switches the copy off
+extern "C" __attribute__((visibility("default"))) void gnf_trace_set_buffer(unsigned long long* buf, int cap) {
+    g_trace_buf = buf, g_trace_cap = cap, g_trace_next = 0;
+}
+__device__ __forceinline__ void geo_stamp(int slot) {
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long t = __builtin_readcyclecounter();
+    if ((threadIdx.x & 63) == 0) s_trace[threadIdx.x >> 6][slot] = t;
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void geo_stamp_after(int slot, float landed) {
+    asm volatile("" ::"v"(landed));  // (a use: the compiler waits for the load that produces it)
+    geo_stamp(slot);
+}
+#define GNF_STAMP(SLOT) geo_stamp(SLOT)
+#define GNF_STAMP_AFTER(SLOT, V) geo_stamp_after(SLOT, V)
+#else
+#define GNF_STAMP(SLOT) ((void)0)
+#define GNF_STAMP_AFTER(SLOT, V) ((void)0)
+#endif
+
 // ---- C: coupling update + block-reduced sum(s) of one row tile (both-nets shapes): s and t rows in LDS, [TM][LS] -----------
 // xn_lds: a free [TM][LS] buffer (the updated rows, for the next bijector's column sums).  PLAIN: the caller is the
-// compile-time-geometry instance (k_half_fused_geo), whose arguments carry no residual, batch-norm or stash fields.
+// compile-time-geometry instance (k_half_fused_geo), whose arguments carry no residual, batch-norm or stash fields; it
+// hands in what the epilogue reads (CoupleOwn: TM * H = kFusedThreads there, so one element per thread; no global load and
+// no kernel-argument read here) and has sum(s) and sum(x_new^2) reduced in one pass (red: 16 doubles), same adds, same order.
+struct CoupleOwn {  // held in vector registers since kernel entry
+    float xu = 0.f;              // the old x_upd_src[r, f]
+    float* dst = nullptr;        // &x_upd[r, f]; NULL: the row is past n_nodes
+    double* part = nullptr;      // &partials[tile]
+    double* sq_part = nullptr;   // &sq_partials[tile], or NULL (workgroup-uniform)
+    int inverse = 0;
+};
 template <int TM, bool STASH, bool FRONT, bool ROWLD, bool PLAIN, class Args, class FArgs, class RArgs>
 __device__ __forceinline__ void couple_tile(const Args& a, const FArgs& fa, const RArgs& rla, const int H, const int LS, float* s_lds,
                                             const float* t_lds, float* xn_lds, const float* bn_lds, double* red, int tile, int row0,
-                                            int tid, int wave, int lane) {
+                                            int tid, int wave, int lane, [[maybe_unused]] const CoupleOwn& own = CoupleOwn{}) {
     [[maybe_unused]] auto bn_part = [&]() -> double* {
         if constexpr (PLAIN) return nullptr; else return a.bn_part;
     };
@@ -131,7 +171,9 @@ __device__ __forceinline__ void couple_tile(const Args& a, const FArgs& fa, cons
         const int rl = idx / H, f = idx - rl * H;
         const int r = row0 + rl;
         if (bn_part()) xn_lds[rl * LS + f] = 0.f;
-        if (r < a.n_nodes) {
+        bool live;
+        if constexpr (PLAIN) live = own.dst != nullptr; else live = r < a.n_nodes;
+        if (live) {
             float sv = s_lds[rl * LS + f], tv = t_lds[rl * LS + f];
             [[maybe_unused]] const int HPb = (H + 15) & ~15;
             if constexpr (!PLAIN) {
@@ -144,13 +186,16 @@ __device__ __forceinline__ void couple_tile(const Args& a, const FArgs& fa, cons
                     tv += xr;
                 }
             }
-            float xv = a.x_upd_src[(int64_t)r * a.ld + f];
+            float xv;
+            if constexpr (PLAIN) xv = own.xu; else xv = a.x_upd_src[(int64_t)r * a.ld + f];
             if constexpr (FRONT) {
                 if (a.bnu_const) xv = xv * bn_lds[2 * HPb + f] + bn_lds[3 * HPb + f];  // the previous half-step's bijector, deferred
                 else if (a.bnu_inv[0]) xv = (xv - bn_lds[f]) / bn_lds[HPb + f] * bn_lds[2 * HPb + f] + bn_lds[3 * HPb + f];
             }
-            const float xn = a.inverse ? (xv - tv) * expf(-sv) : xv * expf(sv) + tv;
-            a.x_upd[(int64_t)r * a.ld + f] = xn;
+            int inverse;
+            if constexpr (PLAIN) inverse = own.inverse; else inverse = a.inverse;
+            const float xn = inverse ? (xv - tv) * expf(-sv) : xv * expf(sv) + tv;
+            if constexpr (PLAIN) *own.dst = xn; else a.x_upd[(int64_t)r * a.ld + f] = xn;
             local += (double)sv;
             local2 += (double)xn * (double)xn;
             if constexpr (ROWLD) s_lds[rl * LS + f] = sv;  // (what the coupling used: a residual block's x_cond is in)
@@ -161,7 +206,30 @@ __device__ __forceinline__ void couple_tile(const Args& a, const FArgs& fa, cons
             }
         }
     }
+    if constexpr (PLAIN) GNF_STAMP(kTraceCoupled);
     for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
+    if constexpr (PLAIN) {  // both sums behind ONE barrier: red[0 .. 7] sum(s), red[8 .. 15] sum(x_new^2), each summed in wave order
+        constexpr int NW = kFusedThreads / 64;
+        const bool sq = own.sq_part != nullptr;
+        if (sq)
+            for (int off = 32; off > 0; off >>= 1) local2 += __shfl_down(local2, off, 64);
+        if (lane == 0) {
+            red[wave] = local;
+            if (sq) red[NW + wave] = local2;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double tot = 0.0;
+            for (int w = 0; w < NW; ++w) tot += red[w];
+            *own.part = tot;
+            if (sq) {
+                double tot2 = 0.0;
+                for (int w = 0; w < NW; ++w) tot2 += red[NW + w];
+                *own.sq_part = tot2;
+            }
+        }
+        return;
+    }
     if (lane == 0) red[wave] = local;
     __syncthreads();
     if (tid == 0) {
@@ -570,7 +638,24 @@ struct GeoArgs {  // what the plain forward reads, and nothing else (FusedArgs +
     int32_t n_nodes, n_tiles;
     float eps, alpha;
     int32_t mean, act, inverse;
+#ifdef GNF_TRACE
+    unsigned long long* trace;  // this launch's [2 workgroups][8 waves][kTraceSlots] stamps, or NULL
+#endif
 };
+
+// a value parked in vector registers from here on (scalar registers are what the unrolled layers run short of: left
+// alone, the compiler reads the epilogue's arguments again behind the last layer barrier).  A pointer comes back as a generic
+// one - the cast to the global address space does not survive the statement - so the epilogue's three stores are flat stores.
+template <class T>
+__device__ __forceinline__ T hold_v(T v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+template <class T>
+__device__ __forceinline__ T* hold_v(T* p) {
+    asm volatile("" : "+v"(p));
+    return (T*)(__attribute__((address_space(1))) T*)p;
+}
 
 template <int IN0G, int LG, int K, int HG>
 struct GeoLayout {  // the packed layout (launch_pack_mlp) of this geometry, in floats
@@ -587,32 +672,74 @@ struct GeoLayout {  // the packed layout (launch_pack_mlp) of this geometry, in 
     static constexpr int boff(int j) { return j == 0 ? 0 : boff(j - 1) + 16 * ont(j - 1); }  // inside the bias block
     static constexpr int kBias = woff(K);                                 // bias block behind the weights
     static constexpr int kLS = 16 * (LG > IN0G ? LG : IN0G) + 4;          // LDS row stride: widest layer + 4 floats
-    static constexpr size_t kLds = (size_t)2 * 2 * 16 * kLS * sizeof(float) + 8 * sizeof(double) + (kRowptrPad + kColCap) * sizeof(int);
+    static constexpr int kRed = 2 * (kFusedThreads / 64);                 // reduction scratch: sum(s) and sum(x_new^2) of every wave
+    static constexpr size_t kLds = (size_t)2 * 2 * 16 * kLS * sizeof(float) + kRed * sizeof(double) + (kRowptrPad + kColCap) * sizeof(int);
     static_assert(woff(1) == 16 * IN0G * 16 * LG && kBias == 16 * IN0G * 16 * LG + (K - 2) * 256 * LG * LG + 16 * LG * 16 * HG,
                   "sum of Ip x Op over the layers");
     static_assert(kLds <= (size_t)kLdsLimit, "activation buffers in LDS");
 };
 
+// Memory order of the prologue: what has a known address goes out first - the rowptr slice, then this thread's own
+// x_cond[r, f] and old x_upd_src[r, f] (TM * H = kFusedThreads: one element per thread, held in two registers through the
+// MLP) - and every kernel argument is read once at entry.  Behind barrier 1 the col segment's first kFusedThreads entries are
+// requested BEFORE the layer-0 weights and the biases: vmcnt retires in issue order, so a col entry requested behind them
+// would wait for the launch's first (cold) touch of the weights.  (Its LDS write still comes behind the ISSUE of those 25
+// loads, which holds the wave for ~1.4 k cycles - profiles/r8a_trace_geo.txt; requesting them in front of barrier 1 instead
+// measured slower.)  The weights still have the gather's two round trips to land in, and do: a layer's first operands are
+// there 128 cycles behind its barrier.  Only the order of requests and waits differs from the generic instance; every
+// product and sum is its own.
 template <int IN0G, int LG, int K, int HG>
 __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using G = GeoLayout<IN0G, LG, K, HG>;
     constexpr int TM = 16, WPN = G::kWpn, LS = G::kLS, H = 16 * HG, IN0 = 16 * IN0G;
+    static_assert(TM * H == kFusedThreads && IN0 == H, "one own-row element per thread, the same one in the gather and in the coupling");
+    GNF_STAMP(0);
     // [net][pingpong][TM][LS] | reduction scratch | rowptr slice | col slice
     auto buf = [&](int net_, int pp_) -> float* { return smem + (2 * net_ + pp_) * TM * LS; };
     double* red = reinterpret_cast<double*>(smem + 2 * 2 * TM * LS);
-    int* s_rowptr = reinterpret_cast<int*>(red + 8);
+    int* s_rowptr = reinterpret_cast<int*>(red + G::kRed);
     int* s_col = s_rowptr + kRowptrPad;
 
-    const int tile = nets2_tile(blockIdx.x, gridDim.x);
-    const int row0 = tile * TM;
     const int tid = threadIdx.x;
     // (wave ids, the second net's rotated column-tile ownership: as in k_half_fused)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int nl = wave / WPN;
     const int wl = (wave % WPN + nl * (WPN / 2)) % WPN;
     const int voff = lane * 16;
+
+    // ---- every argument, once, in ONE scalar round trip: the empty statement uses them all in scalar registers, so no
+    // s_load can sink below this point (left alone, an argument is read where it is first used: a scalar round trip behind
+    // a barrier or in the epilogue).  The values stay the compiler's - a pointer is still known to be a global one.  The
+    // tile comes from n_tiles (= gridDim.x, launch_geo): the grid size sits in the hidden arguments, a round trip of its own.
     const float* wnet = a.wp[nl];
+#ifdef GNF_TRACE
+    asm volatile("" ::"s"(a.trace));
+#endif
+    asm volatile("" ::"s"(a.rowptr), "s"(a.col), "s"(a.x_cond), "s"(a.x_upd), "s"(a.x_upd_src), "s"(a.cond_copy), "s"(a.partials),
+                 "s"(a.sq_partials), "s"(wnet), "s"(a.ld), "s"(a.n_nodes), "s"(a.n_tiles), "s"(a.eps), "s"(a.alpha), "s"(a.mean), "s"(a.act),
+                 "s"(a.inverse));
+    const int tile = nets2_tile(blockIdx.x, a.n_tiles);
+    const int row0 = tile * TM;
+
+    // ---- loads with known addresses: the rowptr slice first (barrier 1 waits for it alone), then the thread's own row ----
+    // (unconditional, clamped addresses: a load inside a branch made the wait in front of barrier 1 a vmcnt(0))
+    const int rp_row = row0 + (tid < TM ? tid : TM);
+    const int rp_reg = a.rowptr[rp_row < a.n_nodes ? rp_row : a.n_nodes];
+    CoupleOwn own;
+    float xc_own;
+    {
+        const int r = row0 + tid / H, f = tid % H;
+        const bool live = r < a.n_nodes;
+        const int64_t at = (int64_t)(live ? r : a.n_nodes - 1) * a.ld + f;  // (n_nodes >= 1: launch_half_fused)
+        xc_own = a.x_cond[at];
+        own.xu = a.x_upd_src[at];
+        own.dst = hold_v(live ? a.x_upd + at : nullptr);
+        own.part = hold_v(a.partials + tile);
+        own.sq_part = hold_v(a.sq_partials ? a.sq_partials + tile : nullptr);
+        own.inverse = hold_v(a.inverse);
+    }
+    __builtin_amdgcn_sched_barrier(0);
 
     // this wave's chunk of layer j: column tiles {wl, wl + 4, wl + 8, wl + 12} of a hidden layer, tile wl of the output layer
     auto chunk = [&](auto jc) -> WChunk {
@@ -630,15 +757,20 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
     };
     const bool last_mine = wl < HG;  // (wave-uniform) the output layer has HG tiles for WPN waves
 
-    // ---- the first chunk's weights, then every other independent read of the prologue: rowptr of the tile and this
-    // wave's biases (one float per lane and column tile, K - 1 layers x 4 tiles + the output layer's), all into registers ----
+    if (tid <= TM) s_rowptr[tid] = rp_reg;
+    __syncthreads();  // barrier 1
+    GNF_STAMP(1);
+
+    // ---- the col segment's first kFusedThreads entries into a register, THEN the first chunk's weights and this wave's
+    // biases (one float per lane and column tile, K - 1 layers x 4 tiles + the output layer's), then the LDS write ----
+    const int seg_beg = s_rowptr[0];
+    const int seg_len = s_rowptr[TM] - seg_beg;
+    const bool staged = seg_len <= kColCap;  // workgroup-uniform (tile_gather has the same rule)
+    int col_reg = 0;
+    if (staged && tid < seg_len) col_reg = a.col[seg_beg + tid];
+    __builtin_amdgcn_sched_barrier(0);
     f32x4 b_pre[kPF][4];
     prefetch_chunk(chunk(std::integral_constant<int, 0>{}), WPN, voff, b_pre, true);
-    int rp_reg = 0;
-    if (tid <= TM) {
-        const int r = row0 + tid;
-        rp_reg = a.rowptr[r < a.n_nodes ? r : a.n_nodes];
-    }
     const float* bnet = wnet + G::kBias + 16 * wl + (lane & 15);
     BiasRegs<4> bias_h[K - 1];
 #pragma unroll
@@ -646,11 +778,17 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
 #pragma unroll
         for (int b = 0; b < 4; ++b) bias_h[j].v[b] = bnet[G::boff(j) + 16 * WPN * b];
     const BiasRegs<1> bias_o{{bnet[G::boff(K - 1) - (last_mine ? 0 : 16 * wl)]}};  // (a wave without a tile reads tile 0's: in bounds)
-    if (tid <= TM) s_rowptr[tid] = rp_reg;
+    __builtin_amdgcn_sched_barrier(0);
+    if (staged) {
+        if (tid < seg_len) s_col[tid] = col_reg;
+        for (int i = tid + kFusedThreads; i < seg_len; i += kFusedThreads) s_col[i] = a.col[seg_beg + i];
+    }
     __syncthreads();
+    GNF_STAMP(2);
     const TileAgg ta{a.col, a.x_cond, a.ld, a.n_nodes, row0, H, IN0, IN0, a.mean, 0, a.eps, a.cond_copy};
-    tile_aggregate<TM, kFusedThreads, kColCap>(ta, s_rowptr, s_col, buf(0, 0), buf(1, 0), LS, nullptr, tid);
+    tile_gather<TM, kFusedThreads, kColCap>(ta, s_rowptr, s_col, buf(0, 0), buf(1, 0), LS, nullptr, tid, OwnRow{xc_own});
     __syncthreads();
+    GNF_STAMP(3);
 
     // ---- B: the K layers, unrolled; the chunk after a wave's last one is that chunk again (harmless re-load) ----
     const float slope_h = a.act == GNF_ACT_RELU ? 0.f : a.alpha;
@@ -659,6 +797,7 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
         const float* in_lds = buf(nl, j & 1);
         float* out_lds = buf(nl, (j & 1) ^ 1);
         const WChunk c = chunk(jc);
+        GNF_STAMP_AFTER(4 + 2 * j, b_pre[0][0][0]);
         if constexpr (j < K - 2) {
             mlp_chunk<1, 4>(in_lds, LS, c, chunk(std::integral_constant<int, j + 1>{}), WPN, bias_h[j], out_lds, slope_h, lane, b_pre, EpiArgs{}, true);
         } else if constexpr (j == K - 2) {
@@ -668,11 +807,18 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
             if (last_mine) mlp_chunk_thin(in_lds, LS, c, c, WPN, bias_o, out_lds, 1.f, lane, b_pre);
         }
         __syncthreads();
+        GNF_STAMP(5 + 2 * j);
     });
 
     // ---- C ----
     constexpr int pp = K & 1;
-    couple_tile<TM, false, false, false, true>(a, 0, 0, H, LS, buf(0, pp), buf(1, pp), buf(0, pp ^ 1), nullptr, red, tile, row0, tid, wave, lane);
+    couple_tile<TM, false, false, false, true>(a, 0, 0, H, LS, buf(0, pp), buf(1, pp), buf(0, pp ^ 1), nullptr, red, tile, row0, tid, wave, lane, own);
+    GNF_STAMP(kTraceEnd);
+#ifdef GNF_TRACE
+    static_assert(4 + 2 * K <= kTraceCoupled, "stamp slots");
+    if (a.trace && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2) && lane < kTraceSlots)
+        a.trace[((blockIdx.x != 0) * (kFusedThreads / 64) + wave) * kTraceSlots + lane] = s_trace[wave][lane];
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -917,10 +1063,19 @@ static bool geo_matches(const HalfStep& hs, const FusedArgs& a) {
 
 template <int IN0G, int LG, int K, int HG>
 static int launch_geo(const FusedArgs& a, unsigned tiles, hipStream_t st) {
+#ifdef GNF_TRACE
+    constexpr int lds_limit = kLdsLimit - (int)sizeof(unsigned long long) * (kFusedThreads / 64) * kTraceSlots;  // (s_trace is static LDS)
+#else
+    constexpr int lds_limit = kLdsLimit;
+#endif
     GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_fused_geo<IN0G, LG, K, HG>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit)));
-    const GeoArgs g{a.rowptr, a.col, a.x_cond, a.x_upd, a.x_upd_src, a.cond_copy, a.partials, a.sq_partials, {a.wp[0][0], a.wp[1][0]},
-                    a.ld, a.n_nodes, a.n_tiles, a.eps, a.alpha, a.mean, a.act, a.inverse};
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit)));
+    GeoArgs g{a.rowptr, a.col, a.x_cond, a.x_upd, a.x_upd_src, a.cond_copy, a.partials, a.sq_partials, {a.wp[0][0], a.wp[1][0]},
+              a.ld, a.n_nodes, a.n_tiles, a.eps, a.alpha, a.mean, a.act, a.inverse};
+#ifdef GNF_TRACE
+    const size_t per_launch = (size_t)2 * (kFusedThreads / 64) * kTraceSlots;
+    g.trace = g_trace_buf && g_trace_cap > 0 ? g_trace_buf + (size_t)(g_trace_next++ % g_trace_cap) * per_launch : nullptr;
+#endif
     constexpr size_t lds = GeoLayout<IN0G, LG, K, HG>::kLds;
     hipLaunchKernelGGL((k_half_fused_geo<IN0G, LG, K, HG>), dim3(tiles), dim3(kFusedThreads), lds, st, g);
     GNF_LAUNCH_CHECK("k_half_fused_geo");

@@ -440,12 +440,19 @@ struct TileAgg {
     float* cond_copy = nullptr;  // NULL, or [n, H] destination (leading dimension ld) for the tile's own x_cond rows
 };
 
+// The thread's own x_cond[r, f] when the caller has it in a register already (the compile-time-geometry instance requests
+// it at kernel entry: TM * in0p = NTHR there, one element per thread); NoOwnRow: tile_gather loads it behind the gather.
+struct NoOwnRow {};
+struct OwnRow {
+    float xc;
+};
+
 // The gather itself.  s_rowptr[0 .. TM] and - when the segment is short enough (seg_len <= COLCAP) - s_col[0 .. seg_len)
 // must already be in LDS and visible (barrier behind the staging stores).
-template <int TM, int NTHR, int COLCAP>
+template <int TM, int NTHR, int COLCAP, class Own = NoOwnRow>
 __device__ __forceinline__ void tile_gather(const TileAgg& t, const int* __restrict__ s_rowptr, const int* __restrict__ s_col,
                                             float* __restrict__ buf0, float* __restrict__ buf1, int LS,
-                                            float* __restrict__ h0_out, int tid) {
+                                            float* __restrict__ h0_out, int tid, const Own& own = Own{}) {
     const int seg_beg = s_rowptr[0];
     const int seg_len = s_rowptr[TM] - seg_beg;
     const bool staged = seg_len <= COLCAP;  // workgroup-uniform
@@ -498,7 +505,8 @@ __device__ __forceinline__ void tile_gather(const TileAgg& t, const int* __restr
                 if (t.concat) {
                     v = s;
                 } else {
-                    const float xc = t.x_cond[(int64_t)r * t.ld + f];
+                    float xc;
+                    if constexpr (std::is_same_v<Own, OwnRow>) xc = own.xc; else xc = t.x_cond[(int64_t)r * t.ld + f];
                     if (t.cond_copy) t.cond_copy[(int64_t)r * t.ld + f] = xc;
                     v = t.eps * xc + s;
                 }
