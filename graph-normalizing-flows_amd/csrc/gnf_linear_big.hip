@@ -13,7 +13,12 @@
 //     registers while the current one is multiplied; 66.7 KB of LDS = two workgroups per CU, each filling the other's
 //     chunk boundaries and epilogue;
 //   * every accumulator sees bias, then its k-groups and the four MFMAs inside a k-group in the generic tile's order:
-//     bitwise the same sums.
+//     bitwise the same sums (tests/test_wide_linear_gpu.py: forward, inverse and every gradient against net.fused = False,
+//     over the row deals, the width edges and the transposed product with and without its mask).  The thin last layer
+//     out of the accumulators adds its column blocks' slabs in another order and is NOT bitwise;
+//   * a net reaches these kernels only where the LDS-resident kernels do not hold it (fused_fits_lds / fused_bwd_fits_lds
+//     look at the net's WIDEST layer, input and output included): a 100 -> 1040 -> 1040 -> 100 net runs its forward and
+//     inverse passes in k_half_fused and only its backward walk (the recompute and dX) here.
 // gnn.py:159-180 (snt.nets.MLP: MatMul + Add, activation between layers).
 #include "gnf_common.h"
 #include "gnf_fused_dev.h"
@@ -398,6 +403,9 @@ int linear_big_fused_slabs(int O) { return (lb_pad16(O) + kLbCols - 1) / kLbCols
 //     the next row tile's fragments in flight behind this one's MFMAs,
 //   * a lane stores four consecutive columns of its row.
 // The four waves of a workgroup share the row loads through L1 and differ in their column tiles.
+// Every accumulator starts from the bias and takes its k-groups, and the four MFMAs of a k-group, in the generic tile's
+// order: bitwise the same sums, in all four instances (tests/test_wide_linear_gpu.py: 1 to 13 k-groups, a last k-group cut
+// to one float4, column blocks with dead waves, both row deals).
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct LinShortArgs {
     const float* x[2];

@@ -1024,9 +1024,11 @@ def test_wide_layer_takes_the_thin_last_layer_along(community_medium, d, latent,
     blocks' partial products and the bias.  Output widths that are no multiple of 4 or 16, a hidden width that is no
     multiple of 256 (a column block with dead waves) and the widest last layer it takes (128): forward against the oracle,
     the inverse through the same kernels, every gradient (stash mode: the coupling kernel also writes s, t into the slot).
-    The first layer of these nets is the short-reduction kernel's (k_linear_short: 100 -> 1040 with a column block of dead waves,
-    128 -> 1280 = 8 k-groups exactly, 200 -> 1280 = the widest reduction it holds in registers; 7 -> 1280 is not whole float4s
-    and stays on the generic tile)."""
+    The first layer of these nets is the short-reduction kernel's (128 -> 1280 = 8 k-groups exactly, 200 -> 1280 = the widest
+    reduction it holds in registers; 7 -> 1280 is not whole float4s and stays on the generic tile).  The 1040-wide case is
+    NOT the wide kernels' in this direction: the LDS-resident forward kernel holds hidden widths up to about 1130
+    (fused_fits_lds), so its forward and inverse run there and only its backward walk reaches k_linear_big / k_linear_short;
+    tests/test_wide_linear_gpu.py proves the routes and reaches the dead-wave column block at widths that stay layered."""
     from gnf_amd.flow import log_prob_terms
     from gnf_amd.train import GRevNetTrainer
     t = 2
