@@ -6,7 +6,9 @@ names, kept small) and save it where examples/train_grevnet_with_data.py --make_
 
 Batches come from datasets.GraphDataset (random Gaussian node features on the dataset's topologies); every iteration is
 train.EncoderTrainer.step (train-forward, binary_loss, backward, Adam); every --eval_every_n_steps a random test batch goes
-through encoder.evaluate, and the figures run_gnn.py:441-465 logs are printed.  The message-passing --attn_type values train;
+through encoder.evaluate, and the figures run_gnn.py:441-465 logs are printed.  --binary_dist_fn picks the decoder's distance
+function and --tune_sigmoid (with sigmoid_l2) trains its temp and shift from 10 and 1 (run_gnn.py:146-165); the function, with
+the trained values, is saved with the encoder.  The message-passing --attn_type values train;
 the attention ones exit with the library's GNF_EUNSUPPORTED text (their encoder backward is not built).
 
 As in the reference, a pair whose logit lies inside Keras' clip gets no gradient: unit-scale random
@@ -23,6 +25,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gnf_amd import _abi, adj_loss, datasets as D, encoder as E, gnn   # noqa: E402
+from gnf_amd.flow import scaled_hacky_sigmoid_l2                        # noqa: E402
 from gnf_amd.train import EncoderTrainer                                # noqa: E402
 
 MESSAGE_PASSING = {"avg_then_mlp": ("mean", "agg"), "sum_then_mlp": ("sum", "agg"), "sum_concat_then_mlp": ("sum", "concat"),
@@ -46,6 +49,9 @@ def main():
     ap.add_argument("--no_residual", action="store_true")
     ap.add_argument("--no_bn_test_local_stats", action="store_true")
     ap.add_argument("--use_soft_labels", action="store_true")
+    ap.add_argument("--binary_dist_fn", default="scaled_hacky_sigmoid_l2",
+                    choices=["scaled_hacky_sigmoid_l2", "hacky_sigmoid_l2", "sigmoid_l2"])
+    ap.add_argument("--tune_sigmoid", action="store_true")
     ap.add_argument("--train_batch_size", type=int, default=8)
     ap.add_argument("--num_train_iters", type=int, default=200000)
     ap.add_argument("--log_every_n_steps", type=int, default=100)
@@ -62,6 +68,8 @@ def main():
     ap.add_argument("--random_seed", type=int, default=12345)
     ap.add_argument("--save_path", default="encoder.npz")
     F = ap.parse_args()
+    if F.tune_sigmoid and F.binary_dist_fn != "sigmoid_l2":
+        ap.error("--tune_sigmoid trains the parameters of --binary_dist_fn sigmoid_l2")
     random.seed(F.random_seed)
     np.random.seed(F.random_seed)
     torch.manual_seed(F.random_seed)
@@ -79,10 +87,13 @@ def main():
         hp.update(agg="sum", combine="agg", epsilon=0.0,
                   attn=dict(num_heads=8, kq_dim=10, v_dim=10, out_dim=80, concat=True, kq_dim_division=False, residual=False))
     enc = E.make_encoder(hp)
+    dist_fn = {"scaled_hacky_sigmoid_l2": scaled_hacky_sigmoid_l2, "hacky_sigmoid_l2": adj_loss.hacky_sigmoid_l2,
+               "sigmoid_l2": adj_loss.sigmoid_l2(10.0, 1.0)}[F.binary_dist_fn]   # run_gnn.py:146-147
     trainer = EncoderTrainer(enc, lr=F.lr, adam_beta1=F.adam_beta1, adam_beta2=F.adam_beta2, adam_epsilon=F.adam_epsilon,
                              lr_type=F.lr_type, num_train_iters=F.num_train_iters, lr_fixed_decay_steps=F.lr_fixed_decay_steps,
                              lr_fixed_decay_rate=F.lr_fixed_decay_rate, lr_fixed_decay_staircase=F.lr_fixed_decay_staircase,
-                             use_soft_labels=F.use_soft_labels)
+                             use_soft_labels=F.use_soft_labels, distance_fn=dist_fn, tune_sigmoid=F.tune_sigmoid)
+    dist_fn = trainer.distance_fn   # (with --tune_sigmoid: the token whose parameters the trainer moves)
     dataset = D.GraphDataset(F.dataset, F.node_embedding_dim, F.gaussian_scale, seed=F.random_seed)
 
     def log(prefix, it, n_node, res, out_nodes=None):
@@ -110,13 +121,19 @@ def main():
         if iteration % F.log_every_n_steps == 0:
             log("", iteration, graph.n_node, res, res["gnn_output"].nodes)
             print(f"learning rate: {trainer.current_learning_rate()}")
+            if F.tune_sigmoid:
+                temp, shift = dist_fn.values()
+                print(f"temp: {temp!r} shift: {shift!r}")
             if not np.isfinite(float(res["sum_loss"])):
                 raise SystemExit("loss is not finite")
         if not F.no_run_eval and iteration % F.eval_every_n_steps == 0:
             test = dataset.get_random_test_batch(F.train_batch_size, dev)
-            log("eval ", iteration, test.n_node, E.evaluate(enc, test, use_soft_labels=F.use_soft_labels)["loss"])
-    E.save_encoder(F.save_path, hp, enc)
+            log("eval ", iteration, test.n_node, E.evaluate(enc, test, distance_fn=dist_fn, use_soft_labels=F.use_soft_labels)["loss"])
+    E.save_encoder(F.save_path, hp, enc, distance_fn=dist_fn)
     print(f"encoder saved to {F.save_path} after {trainer.global_step} steps")
+    if F.tune_sigmoid:
+        temp, shift = dist_fn.values()
+        print(f"final temp: {temp!r} shift: {shift!r}")
 
 
 if __name__ == "__main__":

@@ -12,7 +12,8 @@ embeddings are synthetic (two well-separated clusters per graph, so that the dec
 --encoder_params FILE (an .npz written by gnf_amd.encoder.save_encoder: an encoder's hyper-parameters and
 TimestepGNN.get_params()) --make_chunks runs that encoder's forward pass over --dataset instead
 (encoder.write_embedding_chunks, the loop of generate_grevnet_training_data.py) and the flow trains on its outputs;
---node_embedding_dim is then the encoder's node width.
+--node_embedding_dim is then the encoder's node width, and when the file names the distance function the encoder was
+trained against (run_gnn.py --binary_dist_fn / --tune_sigmoid) the sampled embeddings are decoded with it.
 
     python examples/train_grevnet_with_data.py --make_chunks --num_train_iters 200 --clip_gradient_by_norm
 
@@ -91,6 +92,7 @@ def main():
     rng = np.random.default_rng(F.random_seed)
     dev = torch.device("cuda", 0)
     tmp = None
+    decode_with = {}   # generate_graphs' distance_fn: the one the encoder of --encoder_params was trained against, if it says
     if F.train_data_dir is None:
         if not F.make_chunks:
             raise SystemExit("give --train_data_dir or --make_chunks")
@@ -102,6 +104,9 @@ def main():
             from gnf_amd import encoder as E
             enc, enc_hp = E.load_encoder(F.encoder_params)
             F.node_embedding_dim = int(enc_hp["node_dim"])
+            if "distance" in enc_hp:
+                decode_with = {"distance_fn": E.distance_of(enc_hp)}
+                print(f"decoding with {enc_hp['distance']}")
             paths = E.write_embedding_chunks(enc, D.GraphDataset(F.dataset, F.node_embedding_dim, seed=F.random_seed),
                                              F.train_data_dir, 30 * F.train_batch_size, F.train_batch_size, device=dev,
                                              chunk_bytes=10 * F.train_batch_size * 16 * F.node_embedding_dim * 4)
@@ -149,7 +154,7 @@ def main():
     # ---- sampling pipeline (train_grevnet_with_data.py:397-416, 526-540) ---------------------------------------
     n_node = np.asarray(random.sample(list(data.n_node) * F.sample_size, F.sample_size), np.int32)
     shell = D.transform_example(np.zeros((int(n_node.sum()), F.node_embedding_dim), np.float32), n_node, dev)
-    out = generate_graphs(grevnet, shell)      # sample -> flow in reverse -> edge lists + CSR, all on the device
+    out = generate_graphs(grevnet, shell, **decode_with)      # sample -> flow in reverse -> edge lists + CSR, all on the device
     rows = torch.stack([out["graph"].n_node.to(dev, torch.float64), out["graph"].n_edge.to(torch.float64),
                         out["sample_log_prob_per_graph"]]).cpu().numpy()          # the one device-to-host copy of the tail
     for i, (nodes, edges, mean_lp) in enumerate(rows.T):

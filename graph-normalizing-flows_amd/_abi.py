@@ -75,6 +75,10 @@ class GnfAdjLossSpec(C.Structure):   # include/gnf_adj_loss.h
                 ("label_epsilon", C.c_float), ("abs_tol", C.c_float)]
 
 
+class GnfDistance(C.Structure):      # include/gnf_distance.h
+    _fields_ = [("temp", C.c_float), ("shift", C.c_float), ("scale_by_sqrt_dim", C.c_int32), ("params", C.c_void_p)]
+
+
 class GnfSntBatchNorm(C.Structure):   # include/gnf_timestep_gnn.h: snt.BatchNorm(scale=True) of one encoder timestep
     _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("moving_mean", C.c_void_p), ("moving_variance", C.c_void_p),
                 ("batch_mean", C.c_void_p), ("batch_variance", C.c_void_p)]
@@ -178,6 +182,22 @@ _ADJ_LOSS_SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/gnf_distance.h (included by gnf.h, added within ABI v10): the loss and the two decoders under a distance function given
+# as an argument, whose temp / shift may live on the device, and the loss's gradient with respect to them.  A table of its own
+# for the same reason.
+_DISTANCE_SIGNATURES = {
+    "gnf_pred_adj_dist_f32": (C.c_int, [C.POINTER(GnfDistance), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_adj_edges_count_dist_f32": (C.c_int, [C.POINTER(GnfDistance), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                               C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_adj_loss_dist_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_adj_loss_dist_f32": (C.c_int, [C.POINTER(GnfCsr), C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                        C.POINTER(GnfAdjLossSpec), C.POINTER(GnfDistance), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
+}
+
 # include/gnf_timestep_gnn.h (included by gnf.h, added within ABI v10): the encoder's forward pass, TimestepGNN with its batch /
 # layer norms.  A table of its own for the same reason.
 _ENCODER_SIGNATURES = {
@@ -203,6 +223,7 @@ ORBIT_SYMBOLS = tuple(_ORBIT_SIGNATURES)
 ADJ_LOSS_SYMBOLS = tuple(_ADJ_LOSS_SIGNATURES)
 ENCODER_SYMBOLS = tuple(_ENCODER_SIGNATURES)
 ENCODER_TRAIN_SYMBOLS = tuple(_ENCODER_TRAIN_SIGNATURES)
+DISTANCE_SYMBOLS = tuple(_DISTANCE_SIGNATURES)
 
 _lib = None
 
@@ -217,7 +238,7 @@ def lib():
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES,
-                                  **_ENCODER_TRAIN_SIGNATURES}.items():
+                                  **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -1,5 +1,7 @@
 """How well do embeddings reconstruct the graph they belong to: loss.py's binary_loss, its edge-error counts and the gradient
-of the loss with respect to the embeddings, on the device (gnf_adj_loss_f32, include/gnf_adj_loss.h).
+of the loss with respect to the embeddings, on the device (gnf_adj_loss_f32, include/gnf_adj_loss.h) - and, for a sigmoid_l2
+whose temp and shift are trained with the encoder (run_gnn.py --tune_sigmoid), the gradient with respect to those two as well
+(TunedSigmoidL2, gnf_adj_loss_dist_f32, include/gnf_distance.h).
 
 The reference builds a dense [N, N] true adjacency, a dense distance_fn(nodes) and their element-wise cross-entropy
 (loss.py:162-188), counts wrong entries on those matrices (loss.py:88-116) and lets tf.gradients differentiate through
@@ -40,6 +42,68 @@ class sigmoid_l2:
         return f"sigmoid_l2(temp={self.temp}, shift={self.shift})"
 
 
+class TunedSigmoidL2:
+    """Token for sigmoid_l2 with trainable parameters (run_gnn.py:146-165, --tune_sigmoid): temp and shift live in a device
+    fp32 [2] tensor, `.params`, which the kernels read at run time - an optimiser step on the device changes what the next
+    launch computes.  The tensor is created with (temp, shift) on first use, on the embeddings'
+    device, or adopted with bind(); values() reads the two floats back and is the only call here that synchronises.
+    scale_by_sqrt_dim=False drops the 1 / sqrt(D) on the squared distance (hacky_sigmoid_l2's form, loss.py:36-42)."""
+
+    def __init__(self, temp=10.0, shift=1.0, scale_by_sqrt_dim=True):
+        self._initial = (float(temp), float(shift))
+        self.scale_by_sqrt_dim = bool(scale_by_sqrt_dim)
+        self.params = None
+
+    def bind(self, tensor):
+        """adopt a device fp32 [2] tensor {temp, shift} (a view of a trainer's theta, say) as it is, values included"""
+        if tensor.device.type != "cuda":
+            raise _abi.GnfError("TunedSigmoidL2.params lives on a HIP device (no CPU path)")
+        if tensor.dtype != torch.float32 or tuple(tensor.shape) != (2,) or not tensor.is_contiguous():
+            raise ValueError(f"bind takes a contiguous float32 [2] tensor, got {tensor.dtype} {tuple(tensor.shape)}")
+        self.params = tensor
+        return self
+
+    def on(self, device):
+        """`.params`, created on `device` at first use"""
+        if self.params is None:
+            self.params = torch.tensor(self._initial, dtype=torch.float32, device=device)
+        elif self.params.device != torch.device(device):
+            raise _abi.GnfError(f"TunedSigmoidL2.params is on {self.params.device}, the embeddings on {device}")
+        return self.params
+
+    def values(self):
+        """(temp, shift) as host floats: one 8-byte copy from the device once `.params` exists"""
+        if self.params is None:
+            return self._initial
+        t, s = self.params.detach().cpu().tolist()
+        return float(t), float(s)
+
+    def __repr__(self):
+        return "TunedSigmoidL2(temp={}, shift={}{})".format(*self.values(), "" if self.scale_by_sqrt_dim else ", unscaled")
+
+
+def check_token(distance_fn, what):
+    """NotImplementedError unless distance_fn is one of the four tokens"""
+    if isinstance(distance_fn, TunedSigmoidL2):
+        return
+    try:
+        _distance_params(distance_fn)
+    except NotImplementedError:
+        raise NotImplementedError(f"{what} supports distance_fn = scaled_hacky_sigmoid_l2 (loss.py:45-53), hacky_sigmoid_l2 "
+                                  "(loss.py:36-42), sigmoid_l2(temp, shift) (loss.py:56-62) or TunedSigmoidL2(temp, shift)") \
+            from None
+
+
+def distance_desc(distance_fn, device, what="this call"):
+    """_abi.GnfDistance of any of the four tokens (include/gnf_distance.h); the struct keeps no reference to a
+    TunedSigmoidL2's tensor: hold the token while a launch may be pending"""
+    check_token(distance_fn, what)
+    if isinstance(distance_fn, TunedSigmoidL2):
+        return _abi.GnfDistance(10.0, 1.0, int(distance_fn.scale_by_sqrt_dim), distance_fn.on(device).data_ptr())
+    temp, shift, by_sqrt = _distance_params(distance_fn)
+    return _abi.GnfDistance(temp, shift, by_sqrt, None)
+
+
 def _distance_params(distance_fn):
     """(temp, shift, scale_by_sqrt_dim) of a distance-function token"""
     if distance_fn is scaled_hacky_sigmoid_l2:
@@ -53,7 +117,7 @@ def _distance_params(distance_fn):
 
 
 def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_soft_labels=False, epsilon=0.1, grad=None,
-                abs_tol=0.5, max_nodes_per_graph=None, n_node_host=None):
+                abs_tol=0.5, max_nodes_per_graph=None, n_node_host=None, grad_params=False):
     """loss.py:162-188 with the counts of loss.py:88-116 and, on request, dL/dnodes: gnn_output.nodes are the embeddings,
     graph_phs gives the true topology and n_node.  Returns a dict of device tensors:
       "sum_loss", "mean_loss"     0-d float64: the masked cross-entropy summed over the ordered pairs (i, j), i != j, inside each
@@ -62,6 +126,11 @@ def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_
       "false_positive_pairs", "false_negative_pairs"  int64 [B]: ordered pairs with p - a > abs_tol / a - p > abs_tol against the
                                   hard label a (the helpers below halve them as loss.py does)
       "grad_nodes"                float32 [N, D], with grad="sum" (d sum_loss / d nodes) or grad="mean" (d mean_loss / d nodes)
+      "grad_params"               float32 [2], with grad_params and a TunedSigmoidL2 token: d loss / d (temp, shift) of the
+                                  loss `grad` names (sum_loss without grad).  grad_params=True allocates it; a device float32
+                                  [2] tensor is written in place (a trainer's view of its gradient vector).  Any other token:
+                                  ValueError.  The call then goes through gnf_adj_loss_dist_f32, and so does every call with
+                                  a TunedSigmoidL2 token; the other tokens keep gnf_adj_loss_f32.
     The dense true_adj, pred_adj and ce_loss the reference also returns are NOT produced.  Per pair: p = sigmoid(u),
     ce = softplus(u_c) - t u_c with u_c = u clipped to +-log((1 - 1e-7) / 1e-7) - Keras' binary_crossentropy - and no gradient
     where the clip is active: a true edge whose endpoints lie far apart gets none, as in the reference.  t is the hard label,
@@ -71,7 +140,11 @@ def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_
     max_nodes_per_graph (any upper bound on n_node, at most 65536) or n_node_host (the sizes as a host sequence) nothing is
     copied to the host and nothing synchronises, so the call can be captured; otherwise n_node is read once."""
     from .graphs import csr_desc, csr_of
-    temp, shift, by_sqrt = _distance_params(distance_fn)
+    tuned = isinstance(distance_fn, TunedSigmoidL2)
+    temp, shift, by_sqrt = (10.0, 1.0, 1) if tuned else _distance_params(distance_fn)   # (tuned: the device values override)
+    want_gp = grad_params is not None and grad_params is not False
+    if want_gp and not tuned:
+        raise ValueError("grad_params needs distance_fn=TunedSigmoidL2(...): the other tokens' parameters are constants")
     if grad not in (None, "sum", "mean"):
         raise ValueError(f"grad={grad!r}: None, 'sum' or 'mean'")
     if not 0.0 <= float(epsilon) <= 0.5:
@@ -105,6 +178,27 @@ def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_
     g = torch.empty((n, d), dtype=torch.float32, device=dev) if grad else None
     pairs = float(n) * float(n) - float(n)
     grad_scale = 1.0 if grad != "mean" else (1.0 / pairs if n >= 2 else 0.0)
+    if tuned:
+        dist = distance_desc(distance_fn, dev)
+        gp = None
+        if want_gp:
+            gp = torch.empty(2, dtype=torch.float32, device=dev) if grad_params is True else grad_params
+            if gp.device != dev or gp.dtype != torch.float32 or tuple(gp.shape) != (2,) or not gp.is_contiguous():
+                raise ValueError("grad_params: True or a contiguous float32 [2] tensor on the embeddings' device")
+        ws_bytes = lib.gnf_adj_loss_dist_workspace_bytes(b, n, cap)
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _abi.check(lib.gnf_adj_loss_dist_f32(C.byref(desc), _abi.ptr(z), ld, d, cap, C.byref(spec), C.byref(dist),
+                                                 _abi.ptr(out["loss_per_graph"]), _abi.ptr(sums2),
+                                                 _abi.ptr(out["false_positive_pairs"]), _abi.ptr(out["false_negative_pairs"]),
+                                                 _abi.ptr(g), d, grad_scale, _abi.ptr(gp), _abi.ptr(ws), ws_bytes,
+                                                 _abi.stream_ptr(dev)), "gnf_adj_loss_dist_f32")
+        out["sum_loss"], out["mean_loss"] = sums2[0], sums2[1]
+        if grad:
+            out["grad_nodes"] = g
+        if want_gp:
+            out["grad_params"] = gp
+        return out
     ws_bytes = lib.gnf_adj_loss_workspace_bytes(b, n, cap)
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):

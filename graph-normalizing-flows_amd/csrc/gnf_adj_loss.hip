@@ -19,6 +19,12 @@
 // (same arithmetic in the same order, operands read from global memory).
 // Row sums (fp64 loss, int32 counts) leave through a fixed shuffle tree and go to the workspace; one wave per graph adds
 // its rows up, one wave the graphs: no floating-point atomics anywhere, two calls give the same bits.
+//
+// gnf_adj_loss_dist_f32 (include/gnf_distance.h) launches the pair kernel over AdjLossDistParams: temp and shift may come from
+// device memory (every workgroup loads them once and derives coef), the logit is gnf_distance_dev.h's spelled-out form, and
+// two more fp64 row sums - (p - t) w and p - t over the pairs the clip leaves alone - ride the same shuffle tree; siblings of
+// the two reducing kernels add them up in the loss's order and round dL/dtemp, dL/dshift to fp32 once.
+#include "gnf_distance_dev.h"
 #include "gnf_graph_bitmap.h"
 
 namespace gnf {
@@ -34,6 +40,10 @@ struct AdjLossWs {
     size_t in, out, row_loss, row_fp, row_fn, total;
     int64_t W;
 };
+// gnf_adj_loss_dist_f32's: AdjLossWs | row dtemp double [N] | row dshift double [N] | graph dtemp double [B] | graph dshift double [B]
+struct AdjLossDistWs {
+    size_t row_dtemp, row_dshift, graph_dtemp, graph_dshift, total;
+};
 inline AdjLossWs adj_loss_ws(int64_t n_nodes, int32_t max_nodes) {
     AdjLossWs L;
     L.W = ((int64_t)max_nodes + 63) / 64;
@@ -44,6 +54,16 @@ inline AdjLossWs adj_loss_ws(int64_t n_nodes, int32_t max_nodes) {
     L.row_fp = L.row_loss + (size_t)n_nodes * sizeof(double);
     L.row_fn = L.row_fp + (size_t)n_nodes * sizeof(int32_t);
     L.total = (L.row_fn + (size_t)n_nodes * sizeof(int32_t) + 7) / 8 * 8;
+    return L;
+}
+
+inline AdjLossDistWs adj_loss_dist_ws(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes) {
+    AdjLossDistWs L;
+    L.row_dtemp = adj_loss_ws(n_nodes, max_nodes).total;
+    L.row_dshift = L.row_dtemp + (size_t)n_nodes * sizeof(double);
+    L.graph_dtemp = L.row_dshift + (size_t)n_nodes * sizeof(double);
+    L.graph_dshift = L.graph_dtemp + (size_t)n_graphs * sizeof(double);
+    L.total = L.graph_dshift + (size_t)n_graphs * sizeof(double);
     return L;
 }
 
@@ -86,15 +106,24 @@ struct AdjLossParams {
     float abs_tol;
     float coef;                 // -2 temp scale
     float grad_scale;
+    static constexpr bool kDist = false;
+};
+
+// gnf_adj_loss_dist_f32's: temp / shift (and with them coef) are re-read from `params` when it is set
+struct AdjLossDistParams : AdjLossParams {
+    const float* params;        // NULL, or device {temp, shift}
+    double* row_dtemp;          // NULL (no grad_params), or [n_nodes]: sum_j (p_ij - t_ij) w_ij, |u_ij| < U
+    double* row_dshift;         // ... sum_j (p_ij - t_ij)
+    static constexpr bool kDist = true;
 };
 
 // LDS: cs [kAdjTile][CJ] | zi [kAdjTile][D] (ZI_LDS) | zj [CJ][Dp], Dp = D | 1 (ZJ_LDS: an odd row stride, lanes = columns)
-template <int CJ, bool ZI_LDS, bool ZJ_LDS>
+template <int CJ, bool ZI_LDS, bool ZJ_LDS, class PT>
 __global__ __launch_bounds__(256) void k_adj_loss_pairs(const float* __restrict__ z, int64_t ld, int D,
                                                         const int32_t* __restrict__ off, int64_t n_graphs, int64_t n_nodes,
                                                         int max_nodes, int64_t W,
                                                         const unsigned long long* __restrict__ in_bits,
-                                                        const unsigned long long* __restrict__ out_bits, AdjLossParams P,
+                                                        const unsigned long long* __restrict__ out_bits, PT P,
                                                         double* __restrict__ row_loss, int32_t* __restrict__ row_fp,
                                                         int32_t* __restrict__ row_fn, float* __restrict__ grad, int64_t ldg) {
     constexpr int RPT = CJ / kAdjTile;   // rows of the tile per lane
@@ -105,6 +134,13 @@ __global__ __launch_bounds__(256) void k_adj_loss_pairs(const float* __restrict_
     float* zj = zi + (ZI_LDS ? kAdjTile * D : 0);
     const int Dp = D | 1;
     const int i0 = blockIdx.y * kAdjTile;
+    if constexpr (PT::kDist) {
+        if (P.params) {   // (uniform: device-resident parameters, once per workgroup)
+            P.temp = load_dist_param(P.params);
+            P.shift = load_dist_param(P.params + 1);
+            P.coef = __fmul_rn(-2.f * P.temp, P.scale);
+        }
+    }
     for (int64_t g = blockIdx.x; g < n_graphs; g += gridDim.x) {   // (everything up to the lane's own pairs is uniform)
         int64_t n0;
         int ng;
@@ -121,11 +157,13 @@ __global__ __launch_bounds__(256) void k_adj_loss_pairs(const float* __restrict_
             }
         }
         double ls[RPT];
+        double dts[PT::kDist ? RPT : 1], dss[PT::kDist ? RPT : 1];   // (dist only) the parameter gradient's row sums
         int fpc[RPT], fnc[RPT];
         const float* zr[RPT];
 #pragma unroll
         for (int k = 0; k < RPT; ++k) {
             ls[k] = 0.0;
+            if constexpr (PT::kDist) dts[k] = dss[k] = 0.0;
             fpc[k] = fnc[k] = 0;
             int r = r0 + k * RSTEP;
             if (r >= rows) r = rows - 1;   // a row past the tile's end reads the last one; its results are dropped
@@ -166,7 +204,13 @@ __global__ __launch_bounds__(256) void k_adj_loss_pairs(const float* __restrict_
                     const int r = r0 + k * RSTEP;
                     const int i = i0 + r;
                     if (r >= rows || i == j) continue;
-                    const float u = P.temp * (P.shift - d2[k] * P.scale);
+                    float u, wij = 0.f;   // (dist) w_ij = shift - d2 scale
+                    if constexpr (PT::kDist) {
+                        wij = fmaf(-d2[k], P.scale, P.shift);
+                        u = __fmul_rn(P.temp, wij);   // sigmoid_l2_logit, with w_ij kept
+                    } else {
+                        u = P.temp * (P.shift - d2[k] * P.scale);
+                    }
                     const float p = 1.f / (1.f + expf(-u));
                     const int64_t word = (n0 + i) * W + w;
                     const bool aij = (out_bits[word] >> bit) & 1ull, aji = (in_bits[word] >> bit) & 1ull;
@@ -176,7 +220,14 @@ __global__ __launch_bounds__(256) void k_adj_loss_pairs(const float* __restrict_
                     const float tij = aij ? P.t1 : P.t0, tji = aji ? P.t1 : P.t0;
                     const float uc = fminf(fmaxf(u, -kAdjClipU), kAdjClipU);
                     ls[k] += ((double)fmaxf(uc, 0.f) + (double)log1pf(expf(-fabsf(uc)))) - (double)tij * (double)uc;
-                    if (fabsf(u) < kAdjClipU) cij[k] = P.coef * ((p - tij) + (p - tji));
+                    if (fabsf(u) < kAdjClipU) {
+                        cij[k] = P.coef * ((p - tij) + (p - tji));
+                        if constexpr (PT::kDist) {
+                            const double e = (double)(p - tij);
+                            dts[k] += e * (double)wij;
+                            dss[k] += e;
+                        }
+                    }
                 }
             }
             if (grad) {   // (uniform)
@@ -216,6 +267,17 @@ __global__ __launch_bounds__(256) void k_adj_loss_pairs(const float* __restrict_
                 row_loss[n0 + i0 + r] = l;
                 row_fp[n0 + i0 + r] = a;
                 row_fn[n0 + i0 + r] = b;
+            }
+            if constexpr (PT::kDist) {
+                double dt = dts[k], ds = dss[k];
+                for (int o = CJ / 2; o > 0; o >>= 1) {
+                    dt += __shfl_down(dt, o, CJ);
+                    ds += __shfl_down(ds, o, CJ);
+                }
+                if (c == 0 && r < rows && P.row_dtemp) {
+                    P.row_dtemp[n0 + i0 + r] = dt;
+                    P.row_dshift[n0 + i0 + r] = ds;
+                }
             }
         }
     }
@@ -262,21 +324,83 @@ __global__ __launch_bounds__(64) void k_adj_loss_total(int64_t n_graphs, int64_t
     }
 }
 
-}  // namespace gnf
-
-using namespace gnf;
-
-extern "C" {
-
-size_t gnf_adj_loss_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph) {
-    if (n_graphs < 0 || n_nodes < 0 || max_nodes_per_graph < 0) return 0;
-    return adj_loss_ws(n_nodes, max_nodes_per_graph).total;
+// siblings of the two kernels above for gnf_adj_loss_dist_f32 with grad_params: the same sums in the same order, and beside
+// them the two row sums of the parameter gradient
+__global__ __launch_bounds__(256) void k_adj_loss_graphs_dist(const int32_t* __restrict__ off, int64_t n_graphs, int64_t n_nodes,
+                                                              int max_nodes, const double* __restrict__ row_loss,
+                                                              const int32_t* __restrict__ row_fp,
+                                                              const int32_t* __restrict__ row_fn,
+                                                              const double* __restrict__ row_dtemp,
+                                                              const double* __restrict__ row_dshift,
+                                                              double* __restrict__ loss_per_graph, int64_t* __restrict__ fp_pairs,
+                                                              int64_t* __restrict__ fn_pairs, double* __restrict__ graph_dtemp,
+                                                              double* __restrict__ graph_dshift) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < n_graphs; g += (int64_t)gridDim.x * 4) {
+        int64_t n0;
+        int ng;
+        stats_graph_range(off, (int)g, n_nodes, max_nodes, n0, ng);
+        double l = 0.0, dt = 0.0, ds = 0.0;
+        unsigned long long a = 0, b = 0;
+        for (int r = lane; r < ng; r += 64) {
+            l += row_loss[n0 + r];
+            a += (unsigned long long)row_fp[n0 + r];
+            b += (unsigned long long)row_fn[n0 + r];
+            dt += row_dtemp[n0 + r];
+            ds += row_dshift[n0 + r];
+        }
+        l = wave_sum_f64(l);
+        a = wave_sum_u64(a);
+        b = wave_sum_u64(b);
+        dt = wave_sum_f64(dt);
+        ds = wave_sum_f64(ds);
+        if (lane == 0) {
+            loss_per_graph[g] = l;
+            fp_pairs[g] = (int64_t)a;
+            fn_pairs[g] = (int64_t)b;
+            graph_dtemp[g] = dt;
+            graph_dshift[g] = ds;
+        }
+    }
 }
 
-int gnf_adj_loss_f32(const GnfCsr* csr, const float* z, int64_t ld, int32_t D, int32_t max_nodes_per_graph,
-                     const GnfAdjLossSpec* spec, double* loss_per_graph, double* sums2, int64_t* fp_pairs, int64_t* fn_pairs,
-                     float* grad, int64_t ld_grad, float grad_scale, void* ws, size_t ws_bytes, gnf_stream_t stream) {
-    const char* what = "gnf_adj_loss_f32";
+// one wave: sums2 as k_adj_loss_total, grad_params = grad_scale * { sum_g dtemp[g], temp * sum_g dshift[g] } rounded to fp32 once
+__global__ __launch_bounds__(64) void k_adj_loss_total_dist(int64_t n_graphs, int64_t n_nodes,
+                                                            const double* __restrict__ loss_per_graph,
+                                                            const double* __restrict__ graph_dtemp,
+                                                            const double* __restrict__ graph_dshift, float temp,
+                                                            const float* __restrict__ params, float grad_scale,
+                                                            double* __restrict__ sums2, float* __restrict__ grad_params) {
+    double l = 0.0, dt = 0.0, ds = 0.0;
+    for (int64_t g = threadIdx.x; g < n_graphs; g += 64) {
+        l += loss_per_graph[g];
+        dt += graph_dtemp[g];
+        ds += graph_dshift[g];
+    }
+    l = wave_sum_f64(l);
+    dt = wave_sum_f64(dt);
+    ds = wave_sum_f64(ds);
+    if (threadIdx.x == 0) {
+        sums2[0] = l;
+        sums2[1] = n_nodes < 2 ? 0.0 : l / ((double)n_nodes * (double)n_nodes - (double)n_nodes);
+        if (params) temp = load_dist_param(params);
+        grad_params[0] = (float)((double)grad_scale * dt);
+        grad_params[1] = (float)((double)grad_scale * ((double)temp * ds));
+    }
+}
+
+// gnf_adj_loss_dist_f32 zeroes its workspace with a kernel of its own: in a captured graph that is replayed, a memset node
+// is not reliably finished before the kernel nodes behind it start (bits of the bitmaps and whole row sums went missing from
+// the second replay on), and this entry point exists to be captured with parameters that change between replays
+__global__ __launch_bounds__(256) void k_adj_loss_zero(unsigned long long* __restrict__ ws, size_t words) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) ws[i] = 0ull;
+}
+
+// the two entry points.  dist == NULL: gnf_adj_loss_f32 (spec's distance, its workspace, the kernels it has always launched)
+static int adj_loss(const char* what, const GnfCsr* csr, const float* z, int64_t ld, int32_t D, int32_t max_nodes_per_graph,
+                    const GnfAdjLossSpec* spec, const GnfDistance* dist, double* loss_per_graph, double* sums2,
+                    int64_t* fp_pairs, int64_t* fn_pairs, float* grad, int64_t ld_grad, float grad_scale, float* grad_params,
+                    void* ws, size_t ws_bytes, gnf_stream_t stream) {
     if (!csr || !spec) {
         set_error("%s: null %s", what, csr ? "spec" : "csr");
         return GNF_EINVAL;
@@ -318,13 +442,16 @@ int gnf_adj_loss_f32(const GnfCsr* csr, const float* z, int64_t ld, int32_t D, i
         return GNF_ESHAPE;
     }
     const AdjLossWs L = adj_loss_ws(n, max_nodes_per_graph);
-    if (ws_bytes < L.total) {
-        set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, L.total);
+    const AdjLossDistWs LD = adj_loss_dist_ws(b, n, max_nodes_per_graph);
+    const size_t need = dist ? LD.total : L.total;
+    if (ws_bytes < need) {
+        set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, need);
         return GNF_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
     if (n == 0 || b == 0) {   // nothing to score: zeros
         GNF_HIP_TRY(hipMemsetAsync(sums2, 0, 2 * sizeof(double), st));
+        if (grad_params) GNF_HIP_TRY(hipMemsetAsync(grad_params, 0, 2 * sizeof(float), st));
         if (b > 0) {
             GNF_HIP_TRY(hipMemsetAsync(loss_per_graph, 0, (size_t)b * sizeof(double), st));
             GNF_HIP_TRY(hipMemsetAsync(fp_pairs, 0, (size_t)b * sizeof(int64_t), st));
@@ -337,25 +464,46 @@ int gnf_adj_loss_f32(const GnfCsr* csr, const float* z, int64_t ld, int32_t D, i
     double* row_loss = (double*)((char*)ws + L.row_loss);
     int32_t* row_fp = (int32_t*)((char*)ws + L.row_fp);
     int32_t* row_fn = (int32_t*)((char*)ws + L.row_fn);
-    GNF_HIP_TRY(hipMemsetAsync(ws, 0, L.total, st));   // bitmaps, and the sums of rows no tile covers
+    // bitmaps, and the sums of rows no tile covers (the parameter gradient's among them)
+    if (dist) {   // (every offset of both layouts is a multiple of 8, and so is ws: it starts with the uint64 bitmaps)
+        const size_t words = (grad_params ? LD.graph_dtemp : L.total) / sizeof(unsigned long long);
+        hipLaunchKernelGGL(k_adj_loss_zero, dim3(stats_grid((int64_t)((words + 255) / 256))), dim3(256), 0, st,
+                           (unsigned long long*)ws, words);
+        GNF_LAUNCH_CHECK("k_adj_loss_zero");
+    } else {
+        GNF_HIP_TRY(hipMemsetAsync(ws, 0, L.total, st));
+    }
     hipLaunchKernelGGL(k_adj_loss_bitmap, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->rowptr, csr->col, n,
                        csr->n_edges, csr->node_offsets, b, max_nodes_per_graph, L.W, in_bits, out_bits, grad, ld_grad, D);
     GNF_LAUNCH_CHECK("k_adj_loss_bitmap");
     AdjLossParams P;
-    P.temp = spec->temp;
-    P.shift = spec->shift;
-    P.scale = spec->scale_by_sqrt_dim ? 1.f / sqrtf((float)D) : 1.f;
+    P.temp = dist ? dist->temp : spec->temp;
+    P.shift = dist ? dist->shift : spec->shift;
+    P.scale = (dist ? dist->scale_by_sqrt_dim : spec->scale_by_sqrt_dim) ? 1.f / sqrtf((float)D) : 1.f;
     P.t1 = spec->soft_labels ? 1.f - spec->label_epsilon : 1.f;
     P.t0 = spec->soft_labels ? spec->label_epsilon : 0.f;
     P.abs_tol = spec->abs_tol;
-    P.coef = -2.f * spec->temp * P.scale;
+    P.coef = -2.f * P.temp * P.scale;
     P.grad_scale = grad_scale;
     const dim3 grid(stats_grid(b), (unsigned)((max_nodes_per_graph + kAdjTile - 1) / kAdjTile));
     const size_t tile = (size_t)kAdjTile * D * sizeof(float), dp = (size_t)(D | 1) * sizeof(float);
     const size_t cs64 = (size_t)kAdjTile * 64 * sizeof(float), cs32 = (size_t)kAdjTile * 32 * sizeof(float);
+    AdjLossDistParams PD;   // (dist) the same values; temp, shift and coef are re-read on the device when params is set
+    static_cast<AdjLossParams&>(PD) = P;
+    PD.params = dist ? dist->params : nullptr;
+    PD.row_dtemp = grad_params ? (double*)((char*)ws + LD.row_dtemp) : nullptr;
+    PD.row_dshift = grad_params ? (double*)((char*)ws + LD.row_dshift) : nullptr;
 #define GNF_ADJ_LAUNCH(CJ, ZI, ZJ, LDS)                                                                                   \
-    hipLaunchKernelGGL((k_adj_loss_pairs<CJ, ZI, ZJ>), grid, dim3(256), LDS, st, z, ld, D, csr->node_offsets, b, n,       \
-                       max_nodes_per_graph, L.W, in_bits, out_bits, P, row_loss, row_fp, row_fn, grad, ld_grad)
+    do {                                                                                                                  \
+        if (dist)                                                                                                         \
+            hipLaunchKernelGGL((k_adj_loss_pairs<CJ, ZI, ZJ, AdjLossDistParams>), grid, dim3(256), LDS, st, z, ld, D,     \
+                               csr->node_offsets, b, n, max_nodes_per_graph, L.W, in_bits, out_bits, PD, row_loss, row_fp, \
+                               row_fn, grad, ld_grad);                                                                    \
+        else                                                                                                              \
+            hipLaunchKernelGGL((k_adj_loss_pairs<CJ, ZI, ZJ, AdjLossParams>), grid, dim3(256), LDS, st, z, ld, D,         \
+                               csr->node_offsets, b, n, max_nodes_per_graph, L.W, in_bits, out_bits, P, row_loss, row_fp,  \
+                               row_fn, grad, ld_grad);                                                                    \
+    } while (0)
     if (cs64 + tile + 64 * dp <= kAdjLdsMax)
         GNF_ADJ_LAUNCH(64, true, true, cs64 + tile + 64 * dp);
     else if (cs32 + tile + 32 * dp <= kAdjLdsMax)
@@ -366,12 +514,59 @@ int gnf_adj_loss_f32(const GnfCsr* csr, const float* z, int64_t ld, int32_t D, i
         GNF_ADJ_LAUNCH(64, false, false, cs64);
 #undef GNF_ADJ_LAUNCH
     GNF_LAUNCH_CHECK("k_adj_loss_pairs");
+    if (grad_params) {
+        double* graph_dtemp = (double*)((char*)ws + LD.graph_dtemp);
+        double* graph_dshift = (double*)((char*)ws + LD.graph_dshift);
+        hipLaunchKernelGGL(k_adj_loss_graphs_dist, dim3(stats_grid((b + 3) / 4)), dim3(256), 0, st, csr->node_offsets, b, n,
+                           max_nodes_per_graph, row_loss, row_fp, row_fn, PD.row_dtemp, PD.row_dshift, loss_per_graph, fp_pairs,
+                           fn_pairs, graph_dtemp, graph_dshift);
+        GNF_LAUNCH_CHECK("k_adj_loss_graphs_dist");
+        hipLaunchKernelGGL(k_adj_loss_total_dist, dim3(1), dim3(64), 0, st, b, n, loss_per_graph, graph_dtemp, graph_dshift,
+                           P.temp, PD.params, grad_scale, sums2, grad_params);
+        GNF_LAUNCH_CHECK("k_adj_loss_total_dist");
+        return GNF_OK;
+    }
     hipLaunchKernelGGL(k_adj_loss_graphs, dim3(stats_grid((b + 3) / 4)), dim3(256), 0, st, csr->node_offsets, b, n,
                        max_nodes_per_graph, row_loss, row_fp, row_fn, loss_per_graph, fp_pairs, fn_pairs);
     GNF_LAUNCH_CHECK("k_adj_loss_graphs");
     hipLaunchKernelGGL(k_adj_loss_total, dim3(1), dim3(64), 0, st, b, n, loss_per_graph, sums2);
     GNF_LAUNCH_CHECK("k_adj_loss_total");
     return GNF_OK;
+}
+
+}  // namespace gnf
+
+using namespace gnf;
+
+extern "C" {
+
+size_t gnf_adj_loss_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph) {
+    if (n_graphs < 0 || n_nodes < 0 || max_nodes_per_graph < 0) return 0;
+    return adj_loss_ws(n_nodes, max_nodes_per_graph).total;
+}
+
+int gnf_adj_loss_f32(const GnfCsr* csr, const float* z, int64_t ld, int32_t D, int32_t max_nodes_per_graph,
+                     const GnfAdjLossSpec* spec, double* loss_per_graph, double* sums2, int64_t* fp_pairs, int64_t* fn_pairs,
+                     float* grad, int64_t ld_grad, float grad_scale, void* ws, size_t ws_bytes, gnf_stream_t stream) {
+    return adj_loss("gnf_adj_loss_f32", csr, z, ld, D, max_nodes_per_graph, spec, nullptr, loss_per_graph, sums2, fp_pairs,
+                    fn_pairs, grad, ld_grad, grad_scale, nullptr, ws, ws_bytes, stream);
+}
+
+size_t gnf_adj_loss_dist_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph) {
+    if (n_graphs < 0 || n_nodes < 0 || max_nodes_per_graph < 0) return 0;
+    return adj_loss_dist_ws(n_graphs, n_nodes, max_nodes_per_graph).total;
+}
+
+int gnf_adj_loss_dist_f32(const GnfCsr* csr, const float* z, int64_t ld, int32_t D, int32_t max_nodes_per_graph,
+                          const GnfAdjLossSpec* spec, const GnfDistance* dist, double* loss_per_graph, double* sums2,
+                          int64_t* fp_pairs, int64_t* fn_pairs, float* grad, int64_t ld_grad, float grad_scale,
+                          float* grad_params, void* ws, size_t ws_bytes, gnf_stream_t stream) {
+    if (!dist) {
+        set_error("gnf_adj_loss_dist_f32: null dist");
+        return GNF_EINVAL;
+    }
+    return adj_loss("gnf_adj_loss_dist_f32", csr, z, ld, D, max_nodes_per_graph, spec, dist, loss_per_graph, sums2, fp_pairs,
+                    fn_pairs, grad, ld_grad, grad_scale, grad_params, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

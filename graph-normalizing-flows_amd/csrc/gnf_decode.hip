@@ -7,7 +7,8 @@
 // consumer slices out (train_grevnet_with_data.py:538-540).  One workgroup per (graph, 16-row tile):
 // the tile's rows sit in LDS, every lane walks the columns j of its graph (rows z_j are coalesced reads).  Rows wider
 // than the LDS tile holds (D > 1024) are read from global memory instead - same order of additions, no bound on D.
-#include "gnf_common.h"
+// gnf_pred_adj_dist_f32 (include/gnf_distance.h) is the same kernel over another logit (gnf_distance_dev.h).
+#include "gnf_distance_dev.h"
 
 namespace gnf {
 
@@ -46,11 +47,11 @@ __global__ __launch_bounds__(256) void k_adj_offsets(const int32_t* __restrict__
     }
 }
 
-template <bool LDS_ROWS>
+template <bool LDS_ROWS, class Dist>
 __global__ __launch_bounds__(256) void k_pred_adj(const float* __restrict__ z, int64_t ld, int D,
                                                   const int64_t* __restrict__ node_off,
                                                   const int64_t* __restrict__ blk_off,
-                                                  float* __restrict__ out, float inv_sqrt_d) {
+                                                  float* __restrict__ out, Dist dist_arg) {
     extern __shared__ float zi[];  // [kDecTile][D]
     const int g = blockIdx.x;
     const int64_t n0 = node_off[g];
@@ -58,6 +59,7 @@ __global__ __launch_bounds__(256) void k_pred_adj(const float* __restrict__ z, i
     const int i0 = blockIdx.y * kDecTile;
     if (i0 >= ng) return;
     const int rows = ng - i0 < kDecTile ? ng - i0 : kDecTile;
+    const Dist dist = dist_arg.load();   // (device-resident parameters: once per workgroup)
     if constexpr (LDS_ROWS) {
         for (int i = threadIdx.x; i < rows * D; i += 256) {
             const int rl = i / D, f = i - rl * D;
@@ -75,10 +77,46 @@ __global__ __launch_bounds__(256) void k_pred_adj(const float* __restrict__ z, i
             const float df = zr[f] - zj[f];
             d2 = fmaf(df, df, d2);
         }
-        const float a = 10.f * (1.f - d2 * inv_sqrt_d);
+        const float a = dist.logit(d2);
         const float p = 1.f / (1.f + expf(-a));
         blk[(int64_t)(i0 + rl) * ng + j] = (i0 + rl == j) ? 0.f : p;  // remove_diag (loss.py:157)
     }
+}
+
+// the two entry points: same checks, same launches, the logit's type apart
+template <class Dist>
+static int pred_adj(const char* what, Dist dist, const float* z, int64_t ld, int32_t D, const int32_t* n_node, int64_t n_graphs,
+                    int32_t max_nodes_per_graph, float* out_blocks, int64_t* block_off, void* ws, size_t ws_bytes,
+                    gnf_stream_t stream) {
+    if (n_graphs < 0 || D < 1 || ld < D || max_nodes_per_graph < 0) {
+        set_error("%s: n_graphs=%lld D=%d ld=%lld max_nodes=%d", what, (long long)n_graphs, D, (long long)ld,
+                  max_nodes_per_graph);
+        return GNF_ESHAPE;
+    }
+    if (!ws || !block_off || (n_graphs > 0 && (!n_node || !z || !out_blocks))) {
+        set_error("%s: null pointer argument", what);
+        return GNF_EINVAL;
+    }
+    const size_t need = (size_t)(2 * (n_graphs + 1)) * sizeof(int64_t);   // gnf_pred_adj_workspace_bytes
+    if (ws_bytes < need) {
+        set_error("%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+        return GNF_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int64_t* node_off = (int64_t*)ws;
+    hipLaunchKernelGGL(k_adj_offsets, dim3(1), dim3(256), 0, st, n_node, n_graphs, node_off, block_off);
+    GNF_LAUNCH_CHECK("k_adj_offsets");
+    if (n_graphs == 0 || max_nodes_per_graph == 0) return GNF_OK;
+    const unsigned tiles = (unsigned)((max_nodes_per_graph + kDecTile - 1) / kDecTile);
+    const size_t row_tile = (size_t)kDecTile * D * sizeof(float);
+    if (row_tile <= 64 * 1024)
+        hipLaunchKernelGGL((k_pred_adj<true, Dist>), dim3((unsigned)n_graphs, tiles), dim3(256), row_tile, st, z, ld, D,
+                           node_off, block_off, out_blocks, dist);
+    else
+        hipLaunchKernelGGL((k_pred_adj<false, Dist>), dim3((unsigned)n_graphs, tiles), dim3(256), 0, st, z, ld, D, node_off,
+                           block_off, out_blocks, dist);
+    GNF_LAUNCH_CHECK("k_pred_adj");
+    return GNF_OK;
 }
 
 }  // namespace gnf
@@ -95,34 +133,19 @@ size_t gnf_pred_adj_workspace_bytes(int64_t n_graphs) {
 int gnf_pred_adj_f32(const float* z, int64_t ld, int32_t D, const int32_t* n_node, int64_t n_graphs,
                      int32_t max_nodes_per_graph, float* out_blocks, int64_t* block_off, void* ws,
                      size_t ws_bytes, gnf_stream_t stream) {
-    if (n_graphs < 0 || D < 1 || ld < D || max_nodes_per_graph < 0) {
-        set_error("gnf_pred_adj_f32: n_graphs=%lld D=%d ld=%lld max_nodes=%d", (long long)n_graphs, D,
-                  (long long)ld, max_nodes_per_graph);
-        return GNF_ESHAPE;
-    }
-    if (!ws || !block_off || (n_graphs > 0 && (!n_node || !z || !out_blocks))) {
-        set_error("gnf_pred_adj_f32: null pointer argument");
+    return pred_adj("gnf_pred_adj_f32", DistScaledHacky{D >= 1 ? 1.f / sqrtf((float)D) : 0.f}, z, ld, D, n_node, n_graphs,
+                    max_nodes_per_graph, out_blocks, block_off, ws, ws_bytes, stream);
+}
+
+int gnf_pred_adj_dist_f32(const GnfDistance* dist, const float* z, int64_t ld, int32_t D, const int32_t* n_node,
+                          int64_t n_graphs, int32_t max_nodes_per_graph, float* out_blocks, int64_t* block_off, void* ws,
+                          size_t ws_bytes, gnf_stream_t stream) {
+    if (!dist) {
+        set_error("gnf_pred_adj_dist_f32: null dist");
         return GNF_EINVAL;
     }
-    if (ws_bytes < gnf_pred_adj_workspace_bytes(n_graphs)) {
-        set_error("gnf_pred_adj_f32: workspace %zu < %zu bytes", ws_bytes, gnf_pred_adj_workspace_bytes(n_graphs));
-        return GNF_EWORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    int64_t* node_off = (int64_t*)ws;
-    hipLaunchKernelGGL(k_adj_offsets, dim3(1), dim3(256), 0, st, n_node, n_graphs, node_off, block_off);
-    GNF_LAUNCH_CHECK("k_adj_offsets");
-    if (n_graphs == 0 || max_nodes_per_graph == 0) return GNF_OK;
-    const unsigned tiles = (unsigned)((max_nodes_per_graph + kDecTile - 1) / kDecTile);
-    const size_t row_tile = (size_t)kDecTile * D * sizeof(float);
-    if (row_tile <= 64 * 1024)
-        hipLaunchKernelGGL(k_pred_adj<true>, dim3((unsigned)n_graphs, tiles), dim3(256), row_tile, st, z, ld, D, node_off,
-                           block_off, out_blocks, 1.f / sqrtf((float)D));
-    else
-        hipLaunchKernelGGL(k_pred_adj<false>, dim3((unsigned)n_graphs, tiles), dim3(256), 0, st, z, ld, D, node_off,
-                           block_off, out_blocks, 1.f / sqrtf((float)D));
-    GNF_LAUNCH_CHECK("k_pred_adj");
-    return GNF_OK;
+    return pred_adj("gnf_pred_adj_dist_f32", dist_sigmoid(*dist, D >= 1 ? D : 1), z, ld, D, n_node, n_graphs,
+                    max_nodes_per_graph, out_blocks, block_off, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

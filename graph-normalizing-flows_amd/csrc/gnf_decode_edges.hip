@@ -8,7 +8,8 @@
 // senders ascending within a receiver - (rowptr, senders) IS the receiver-sorted CSR of the edge list, and because
 // d2(i, j) and d2(j, i) are the same fp32 number the edge set is symmetric, so it is the by-sender CSR as well.
 // No atomics: every word, count and edge has exactly one writer.
-#include "gnf_common.h"
+// gnf_adj_edges_count_dist_f32 (include/gnf_distance.h) is pass 1 over another logit (gnf_distance_dev.h).
+#include "gnf_distance_dev.h"
 
 namespace gnf {
 
@@ -70,10 +71,10 @@ __device__ __forceinline__ void edge_graph_range(const int64_t* __restrict__ nod
 // pass 1.  One workgroup per (graph, 16-row tile), the tile's rows in LDS as in k_pred_adj; wave w owns rows 4 w .. 4 w + 3
 // of the tile and walks the graph's columns 64 at a time (lane = column): one read of z_j serves its four rows, one ballot
 // per row is the bitmap word, and the wave adds up its rows' popcounts in registers.
-template <bool LDS_ROWS>
+template <bool LDS_ROWS, class Dist>
 __global__ __launch_bounds__(256) void k_edge_count(const float* __restrict__ z, int64_t ld, int D,
                                                     const int64_t* __restrict__ node_off, int64_t n_nodes, int max_nodes,
-                                                    int64_t W, float threshold, int self_loops, float inv_sqrt_d,
+                                                    int64_t W, float threshold, int self_loops, Dist dist_arg,
                                                     unsigned long long* __restrict__ bitmap, int32_t* __restrict__ rowcnt) {
     extern __shared__ float zi[];  // [kEdgeTile][D]
     int64_t n0;
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(256) void k_edge_count(const float* __restrict__ z,
     edge_graph_range(node_off, blockIdx.x, n_nodes, max_nodes, n0, ng);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int words = (ng + 63) / 64;
+    const Dist dist = dist_arg.load();   // (device-resident parameters: once per workgroup)
     for (int i0 = blockIdx.y * kEdgeTile; i0 < ng; i0 += gridDim.y * kEdgeTile) {   // (uniform over the workgroup)
         const int rows = ng - i0 < kEdgeTile ? ng - i0 : kEdgeTile;
         if constexpr (LDS_ROWS) {
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(256) void k_edge_count(const float* __restrict__ z,
             }
             for (int q = 0; q < kEdgeWaveRows; ++q) {
                 const int i = i0 + r0 + q;
-                const float a = 10.f * (1.f - d2[q] * inv_sqrt_d);
+                const float a = dist.logit(d2[q]);
                 const float p = 1.f / (1.f + expf(-a));
                 const bool edge = col && (i == j ? self_loops != 0 : p > threshold);
                 const unsigned long long word = __ballot(edge);
@@ -219,21 +221,11 @@ static dim3 edge_grid(int64_t n_graphs, int32_t max_nodes) {
     return dim3((unsigned)n_graphs, (unsigned)tiles);
 }
 
-}  // namespace gnf
-
-using namespace gnf;
-
-extern "C" {
-
-size_t gnf_adj_edges_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph) {
-    if (n_graphs < 0 || n_nodes < 0 || max_nodes_per_graph < 0) return 0;
-    return edge_ws(n_graphs, n_nodes, max_nodes_per_graph).total;
-}
-
-int gnf_adj_edges_count_f32(const float* z, int64_t ld, int32_t D, const int32_t* n_node, int64_t n_graphs, int64_t n_nodes,
-                            int32_t max_nodes_per_graph, float threshold, int32_t self_loops, int32_t* rowptr,
-                            int32_t* n_edge, int64_t* total, void* ws, size_t ws_bytes, gnf_stream_t stream) {
-    const char* what = "gnf_adj_edges_count_f32";
+// the two counting entry points: same checks, same launches, the logit's type apart
+template <class Dist>
+static int edges_count(const char* what, Dist dist, const float* z, int64_t ld, int32_t D, const int32_t* n_node,
+                       int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph, float threshold, int32_t self_loops,
+                       int32_t* rowptr, int32_t* n_edge, int64_t* total, void* ws, size_t ws_bytes, gnf_stream_t stream) {
     if (D < 1 || ld < D) {
         set_error("%s: D=%d ld=%lld", what, D, (long long)ld);
         return GNF_ESHAPE;
@@ -261,19 +253,49 @@ int gnf_adj_edges_count_f32(const float* z, int64_t ld, int32_t D, const int32_t
     if (n_graphs > 0 && n_nodes > 0) {
         const dim3 grid = edge_grid(n_graphs, max_nodes_per_graph);
         const size_t row_tile = (size_t)kEdgeTile * D * sizeof(float);
-        const float inv_sqrt_d = 1.f / sqrtf((float)D);
         if (row_tile <= 64 * 1024)
-            hipLaunchKernelGGL(k_edge_count<true>, grid, dim3(256), row_tile, st, z, ld, D, node_off, n_nodes,
-                               max_nodes_per_graph, L.W, threshold, self_loops, inv_sqrt_d, bitmap, rowcnt);
+            hipLaunchKernelGGL((k_edge_count<true, Dist>), grid, dim3(256), row_tile, st, z, ld, D, node_off, n_nodes,
+                               max_nodes_per_graph, L.W, threshold, self_loops, dist, bitmap, rowcnt);
         else
-            hipLaunchKernelGGL(k_edge_count<false>, grid, dim3(256), 0, st, z, ld, D, node_off, n_nodes,
-                               max_nodes_per_graph, L.W, threshold, self_loops, inv_sqrt_d, bitmap, rowcnt);
+            hipLaunchKernelGGL((k_edge_count<false, Dist>), grid, dim3(256), 0, st, z, ld, D, node_off, n_nodes,
+                               max_nodes_per_graph, L.W, threshold, self_loops, dist, bitmap, rowcnt);
         GNF_LAUNCH_CHECK("k_edge_count");
     }
     hipLaunchKernelGGL(k_edge_scan, dim3(1), dim3(256), 0, st, rowcnt, n_graphs > 0 ? n_nodes : 0, node_off, n_graphs, rowptr,
                        n_edge, total);
     GNF_LAUNCH_CHECK("k_edge_scan");
     return GNF_OK;
+}
+
+}  // namespace gnf
+
+using namespace gnf;
+
+extern "C" {
+
+size_t gnf_adj_edges_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph) {
+    if (n_graphs < 0 || n_nodes < 0 || max_nodes_per_graph < 0) return 0;
+    return edge_ws(n_graphs, n_nodes, max_nodes_per_graph).total;
+}
+
+int gnf_adj_edges_count_f32(const float* z, int64_t ld, int32_t D, const int32_t* n_node, int64_t n_graphs, int64_t n_nodes,
+                            int32_t max_nodes_per_graph, float threshold, int32_t self_loops, int32_t* rowptr,
+                            int32_t* n_edge, int64_t* total, void* ws, size_t ws_bytes, gnf_stream_t stream) {
+    return edges_count("gnf_adj_edges_count_f32", DistScaledHacky{D >= 1 ? 1.f / sqrtf((float)D) : 0.f}, z, ld, D, n_node,
+                       n_graphs, n_nodes, max_nodes_per_graph, threshold, self_loops, rowptr, n_edge, total, ws, ws_bytes,
+                       stream);
+}
+
+int gnf_adj_edges_count_dist_f32(const GnfDistance* dist, const float* z, int64_t ld, int32_t D, const int32_t* n_node,
+                                 int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph, float threshold,
+                                 int32_t self_loops, int32_t* rowptr, int32_t* n_edge, int64_t* total, void* ws, size_t ws_bytes,
+                                 gnf_stream_t stream) {
+    if (!dist) {
+        set_error("gnf_adj_edges_count_dist_f32: null dist");
+        return GNF_EINVAL;
+    }
+    return edges_count("gnf_adj_edges_count_dist_f32", dist_sigmoid(*dist, D >= 1 ? D : 1), z, ld, D, n_node, n_graphs,
+                       n_nodes, max_nodes_per_graph, threshold, self_loops, rowptr, n_edge, total, ws, ws_bytes, stream);
 }
 
 int gnf_adj_edges_fill(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph, const int32_t* rowptr,

@@ -4,7 +4,8 @@ train.EncoderTrainer (gnn.TimestepGNN.forward_train / backward), whose result sa
 
   evaluate                 run_gnn.py:441-465: encoder -> adj_loss.binary_loss and its counts
   write_embedding_chunks   generate_grevnet_training_data.py:78-120: encoder outputs cut into chunk files
-  save_encoder / load_encoder   an encoder's hyper-parameters and TimestepGNN.get_params() in one .npz
+  save_encoder / load_encoder   an encoder's hyper-parameters and TimestepGNN.get_params() in one .npz, with the distance
+                           function it was trained against (distance_of)
 """
 import json
 import os
@@ -103,8 +104,42 @@ def _flatten(params):
     return flat
 
 
-def save_encoder(path, hp, encoder):
-    """hp (make_encoder's) and encoder.get_params() as one .npz"""
+_DISTANCE_KINDS = ("scaled_hacky_sigmoid_l2", "hacky_sigmoid_l2", "sigmoid_l2")
+
+
+def distance_entry(distance_fn):
+    """{"kind", "temp", "shift"} of a distance token: what save_encoder stores.  A TunedSigmoidL2's values are read back from
+    the device here, once; it is stored as the sigmoid_l2 it has become (with "scale_by_sqrt_dim": false if it is unscaled)."""
+    if isinstance(distance_fn, adj_loss.TunedSigmoidL2):
+        temp, shift = distance_fn.values()
+        entry = {"kind": "sigmoid_l2", "temp": temp, "shift": shift}
+        if not distance_fn.scale_by_sqrt_dim:
+            entry["scale_by_sqrt_dim"] = False
+        return entry
+    temp, shift, by_sqrt = adj_loss._distance_params(distance_fn)
+    kind = "sigmoid_l2" if isinstance(distance_fn, adj_loss.sigmoid_l2) else _DISTANCE_KINDS[0 if by_sqrt else 1]
+    return {"kind": kind, "temp": temp, "shift": shift}
+
+
+def distance_of(hp):
+    """The distance token of a loaded encoder's hyper-parameters: what to hand pred_adj, decode_graphs, generate_graphs and
+    evaluate.  Files written without a "distance" entry give the default, scaled_hacky_sigmoid_l2."""
+    entry = hp.get("distance")
+    if entry is None or entry["kind"] == "scaled_hacky_sigmoid_l2":
+        return scaled_hacky_sigmoid_l2
+    if entry["kind"] == "hacky_sigmoid_l2":
+        return adj_loss.hacky_sigmoid_l2
+    if entry["kind"] == "sigmoid_l2":
+        if not entry.get("scale_by_sqrt_dim", True):
+            return adj_loss.TunedSigmoidL2(entry["temp"], entry["shift"], scale_by_sqrt_dim=False)
+        return adj_loss.sigmoid_l2(entry["temp"], entry["shift"])
+    raise ValueError(f"distance kind {entry['kind']!r}: one of {_DISTANCE_KINDS}")
+
+
+def save_encoder(path, hp, encoder, distance_fn=None):
+    """hp (make_encoder's) and encoder.get_params() as one .npz; with distance_fn, hp gains "distance" (distance_entry)"""
+    if distance_fn is not None:
+        hp = dict(hp, distance=distance_entry(distance_fn))
     np.savez(path, hp_json=np.array(json.dumps(hp)), **_flatten(encoder.get_params()))
 
 

@@ -135,9 +135,13 @@ def pred_adj(gnn_output, distance_fn=scaled_hacky_sigmoid_l2, max_nodes_per_grap
     sigmoid(10 * (1 - ||z_i - z_j||^2 / sqrt(D))) between the nodes of each graph, zero diagonal.  The
     reference returns a dense block-diagonal-masked [N, N] matrix; this returns the list of per-graph
     [n_g, n_g] blocks (views of one device buffer), which is what its consumer slices out
-    (train_grevnet_with_data.py:538-540).  `adjacency = block > 0.5` gives the sampled graphs."""
-    if distance_fn is not scaled_hacky_sigmoid_l2:
-        raise NotImplementedError("pred_adj supports distance_fn=scaled_hacky_sigmoid_l2 (loss.py:45-53)")
+    (train_grevnet_with_data.py:538-540).  `adjacency = block > 0.5` gives the sampled graphs.
+    distance_fn: the default, or one of adj_loss' tokens - hacky_sigmoid_l2, sigmoid_l2(temp, shift), TunedSigmoidL2 - whose
+    probabilities have the bits binary_loss scores (gnf_pred_adj_dist_f32); the default keeps gnf_pred_adj_f32."""
+    default = distance_fn is scaled_hacky_sigmoid_l2
+    if not default:
+        from .adj_loss import check_token, distance_desc
+        check_token(distance_fn, "pred_adj")   # (anything else raises before the device is looked at)
     lib = _abi.lib()
     z = gnn_output.nodes
     if z.device.type != "cuda":
@@ -159,9 +163,15 @@ def pred_adj(gnn_output, distance_fn=scaled_hacky_sigmoid_l2, max_nodes_per_grap
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
     nn = gnn_output.n_node.to(torch.int32).contiguous()
     with torch.cuda.device(dev):
-        _abi.check(lib.gnf_pred_adj_f32(_abi.ptr(z), z.stride(0), z.shape[1], _abi.ptr(nn), b, cap, _abi.ptr(out),
-                                        _abi.ptr(off), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                   "gnf_pred_adj_f32")
+        if default:
+            _abi.check(lib.gnf_pred_adj_f32(_abi.ptr(z), z.stride(0), z.shape[1], _abi.ptr(nn), b, cap, _abi.ptr(out),
+                                            _abi.ptr(off), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                       "gnf_pred_adj_f32")
+        else:
+            dist = distance_desc(distance_fn, dev, "pred_adj")
+            _abi.check(lib.gnf_pred_adj_dist_f32(C.byref(dist), _abi.ptr(z), z.stride(0), z.shape[1], _abi.ptr(nn), b, cap,
+                                                 _abi.ptr(out), _abi.ptr(off), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                       "gnf_pred_adj_dist_f32")
     blocks, o = [], 0
     for n in n_node_host:
         blocks.append(out[o:o + n * n].view(n, n))
@@ -190,9 +200,12 @@ def decode_graphs(gnn_output, threshold=0.5, self_loops=False, edge_capacity=Non
     the host and nothing synchronises, so the call can be captured into a hipGraph.  The edge tensors (and "graph".edges)
     then have edge_capacity entries of which only the first min(total_edges, edge_capacity) are valid - the rest is
     unspecified - and rowptr / n_edge / "csr" describe the untruncated edge list: check total_edges <= edge_capacity before
-    using them.  The CSR cache is not seeded in this mode."""
-    if distance_fn is not scaled_hacky_sigmoid_l2:
-        raise NotImplementedError("decode_graphs supports distance_fn=scaled_hacky_sigmoid_l2 (loss.py:45-53)")
+    using them.  The CSR cache is not seeded in this mode.
+    distance_fn: as for pred_adj (gnf_adj_edges_count_dist_f32; the default keeps gnf_adj_edges_count_f32)."""
+    default = distance_fn is scaled_hacky_sigmoid_l2
+    if not default:
+        from .adj_loss import check_token, distance_desc
+        check_token(distance_fn, "decode_graphs")   # (anything else raises before the device is looked at)
     from .graphs import Csr, GraphsTuple, seed_csr_cache
     lib = _abi.lib()
     z = gnn_output.nodes
@@ -224,9 +237,16 @@ def decode_graphs(gnn_output, threshold=0.5, self_loops=False, edge_capacity=Non
     ws_bytes = lib.gnf_adj_edges_workspace_bytes(b, n, cap)
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _abi.check(lib.gnf_adj_edges_count_f32(_abi.ptr(z), ld, d, _abi.ptr(nn), b, n, cap, float(threshold),
-                                               int(bool(self_loops)), _abi.ptr(rowptr), _abi.ptr(n_edge), _abi.ptr(total),
-                                               _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_edges_count_f32")
+        if default:
+            _abi.check(lib.gnf_adj_edges_count_f32(_abi.ptr(z), ld, d, _abi.ptr(nn), b, n, cap, float(threshold),
+                                                   int(bool(self_loops)), _abi.ptr(rowptr), _abi.ptr(n_edge), _abi.ptr(total),
+                                                   _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_edges_count_f32")
+        else:
+            dist = distance_desc(distance_fn, dev, "decode_graphs")
+            _abi.check(lib.gnf_adj_edges_count_dist_f32(C.byref(dist), _abi.ptr(z), ld, d, _abi.ptr(nn), b, n, cap,
+                                                        float(threshold), int(bool(self_loops)), _abi.ptr(rowptr),
+                                                        _abi.ptr(n_edge), _abi.ptr(total), _abi.ptr(ws), ws_bytes,
+                                                        _abi.stream_ptr(dev)), "gnf_adj_edges_count_dist_f32")
         exact = edge_capacity is None
         e = int(total.item()) if exact else int(edge_capacity)
         senders = torch.empty(e, dtype=torch.int32, device=dev)
@@ -243,14 +263,16 @@ def decode_graphs(gnn_output, threshold=0.5, self_loops=False, edge_capacity=Non
     return {"graph": graph, "csr": csr, "total_edges": total[0]}
 
 
-def generate_graphs(grevnet, shell_graph, generator=None, threshold=0.5, self_loops=False):
+def generate_graphs(grevnet, shell_graph, generator=None, threshold=0.5, self_loops=False,
+                    distance_fn=scaled_hacky_sigmoid_l2):
     """generate_graphs.py:57-84 / train_grevnet_with_data.py:526-540 in one call: sample z ~ N(0, I) on shell_graph's
     topology, run the flow in reverse, decode the embeddings to graphs (decode_graphs, exact-size mode).  Returns what
     decode_graphs returns, what sample returns, and "sample_log_prob_per_graph": the mean of sample_log_prob over each
-    graph's nodes (generate_graphs.py:76; device fp64 [B], 0 for a graph without nodes)."""
+    graph's nodes (generate_graphs.py:76; device fp64 [B], 0 for a graph without nodes).  distance_fn: the function the
+    encoder whose embeddings the flow models was trained against (decode_graphs' argument)."""
     out = sample(grevnet, shell_graph, generator=generator)
     top = out["grevnet_top"]
-    res = decode_graphs(top, threshold=threshold, self_loops=self_loops)
+    res = decode_graphs(top, threshold=threshold, self_loops=self_loops, distance_fn=distance_fn)
     dev = top.nodes.device
     nn = shell_graph.n_node.to(device=dev, dtype=torch.int64)
     b = int(nn.shape[0])

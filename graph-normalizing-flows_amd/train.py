@@ -474,16 +474,28 @@ class EncoderTrainer:
     are run_gnn.py's flags (lr 1e-4, beta1 0.9, beta2 0.999, epsilon 1e-8, lr_type polynomial_decay over num_train_iters
     200000); lr_type "schedule" is not built.  No clipping: run_gnn.py has none.  With max_nodes_per_graph given,
     loss_and_grads neither copies to the host nor synchronises and can be captured; apply_gradients is one more launch whose
-    step size is a host scalar that changes every step (it is passed by value, so it stays outside a captured region)."""
+    step size is a host scalar that changes every step (it is passed by value, so it stays outside a captured region).
+    tune_sigmoid (run_gnn.py:146-165): temp and shift of sigmoid_l2 are trained as well.  distance_fn is then a sigmoid_l2 or
+    adj_loss.TunedSigmoidL2 token (its values are where training starts); the two floats are the LAST two entries of theta,
+    self.distance_fn is a TunedSigmoidL2 whose .params is a view of them, binary_loss writes their gradient into the last two
+    entries of grad (gnf_adj_loss_dist_f32) and the one Adam launch moves them with everything else.  The kernels read them
+    from the device at run time, so a captured loss_and_grads replayed after a step computes what the eager call computes."""
 
     LR_TYPES = ("constant", "fixed_decay", "polynomial_decay")
 
     def __init__(self, encoder, lr=1e-4, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, lr_type="polynomial_decay",
                  num_train_iters=200000, lr_fixed_decay_steps=1000, lr_fixed_decay_rate=0.99, lr_fixed_decay_staircase=False,
-                 distance_fn=None, use_soft_labels=False, max_nodes_per_graph=None):
+                 distance_fn=None, use_soft_labels=False, max_nodes_per_graph=None, tune_sigmoid=False):
+        from .adj_loss import TunedSigmoidL2, sigmoid_l2
         from .flow import scaled_hacky_sigmoid_l2
         if lr_type not in self.LR_TYPES:
             raise ValueError(f"lr_type={lr_type!r}: one of {self.LR_TYPES} ('schedule' is not built)")
+        self.tune_sigmoid = bool(tune_sigmoid)
+        if self.tune_sigmoid:
+            if isinstance(distance_fn, sigmoid_l2):
+                distance_fn = TunedSigmoidL2(distance_fn.temp, distance_fn.shift)
+            elif not isinstance(distance_fn, TunedSigmoidL2):   # run_gnn.py:148-153
+                raise ValueError("tune_sigmoid needs distance_fn = sigmoid_l2(temp, shift) or TunedSigmoidL2(temp, shift)")
         self.net = encoder
         self.lr, self.beta1, self.beta2, self.epsilon = float(lr), float(adam_beta1), float(adam_beta2), float(adam_epsilon)
         self.lr_type, self.num_train_iters = lr_type, int(num_train_iters)
@@ -524,6 +536,9 @@ class EncoderTrainer:
         old_m, old_v = self.m, self.v
         tensors = [self._get(v) for v in variables]
         total = sum(t.numel() for t in tensors)
+        if self.tune_sigmoid:                     # temp, shift: the last two entries
+            sigmoid = self.distance_fn.values()   # (a host read, when the arena is laid out only)
+            total += 2
         theta = torch.empty(total, dtype=torch.float32, device=device)
         grad = torch.zeros_like(theta)
         views, gviews, off = [], [], 0
@@ -546,6 +561,9 @@ class EncoderTrainer:
                 for o in objs:
                     o.gamma, o.beta = next(it), next(it)
                     grads[key].append({"gamma": next(git), "beta": next(git)})
+        if self.tune_sigmoid:
+            theta[-2:].copy_(torch.tensor(sigmoid, dtype=torch.float32))
+            self.distance_fn.bind(theta[-2:])
         keep = old_m is not None and old_m.numel() == total and old_m.device == device
         self.theta, self.grad, self._grads = theta, grad, grads
         self.m = old_m if keep else torch.zeros_like(theta)
@@ -574,7 +592,8 @@ class EncoderTrainer:
         out, stash = self.net.forward_train(graph)
         res = adj_loss.binary_loss(out, graph if true_graph is None else true_graph, distance_fn=self.distance_fn,
                                    use_soft_labels=self.use_soft_labels, grad="sum",
-                                   max_nodes_per_graph=self.max_nodes_per_graph)
+                                   max_nodes_per_graph=self.max_nodes_per_graph,
+                                   grad_params=self.grad[-2:] if self.tune_sigmoid else False)
         self.net.backward(graph, stash, res["grad_nodes"], self._grads)
         res["gnn_output"], res["total_loss"] = out, res["sum_loss"]
         return res

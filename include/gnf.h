@@ -510,6 +510,9 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 /* Added within ABI v10: the adjacency reconstruction loss of embeddings against a true batch, its edge-error counts and its
  * gradient (gnf_adj_loss.h) - likewise part of this interface, in a header of its own. */
 #include "gnf_adj_loss.h"
+/* Added within ABI v10: one distance-function description, with parameters that may live on the device, for the loss and the
+ * two decoders, and the loss's gradient with respect to those parameters (gnf_distance.h) - likewise. */
+#include "gnf_distance.h"
 /* Added within ABI v10: the encoder's forward pass, TimestepGNN with its batch / layer norms (gnf_timestep_gnn.h) - likewise. */
 #include "gnf_timestep_gnn.h"
 /* Added within ABI v10: the encoder's training forward (with a stash) and its backward pass (gnf_timestep_gnn_train.h) - likewise. */

@@ -14,6 +14,9 @@ on
                8 .. 19 nodes, D = 200, against symmetric G(n, 0.3) graphs with a self loop per node - both routes are
                launch-bound here
 Embeddings: N(0, 1) * 0.5 * D^-1/4 with one row in eight stretched by 4 (the tests' distribution: every branch sees pairs).
+Beside the device route, the same call through gnf_adj_loss_dist_f32 (adj_loss.TunedSigmoidL2(10, 1): temp and shift read
+from device memory) without a gradient, with dL/dnodes, and with dL/dnodes and dL/d(temp, shift) - its outputs are asserted
+bit-equal to the device route's first, so the three timings price the run-time parameter load and the two extra fp64 sums.
 Both routes run on one machine, after a warm-up, as repeated timed regions (20 calls each) that end in a device synchronise;
 the routes are alternated inside every repeat and median, min and max over the repeats go out as one JSON line per workload,
 with dense_over_device for the call without and with the gradient.  Before anything is timed the two routes are compared
@@ -51,7 +54,7 @@ def timed(fns, repeats, sync):
 
 def main():
     import torch
-    from gnf_amd.adj_loss import binary_loss
+    from gnf_amd.adj_loss import TunedSigmoidL2, binary_loss
     import numpy as np
     from gnf_amd.datasets import GraphDataset
     from gnf_amd.flow import pred_adj
@@ -118,8 +121,17 @@ def main():
         assert row["count_mismatches_vs_pred_adj"] == 0, row     # the same arithmetic as pred_adj: equal
         assert abs(row["sum_loss_device"] - row["sum_loss_dense_fp32"]) <= 1e-3 * abs(row["sum_loss_device"]), row
         assert row["grad_max_abs_diff_vs_autograd"] <= 1e-2 * gmax, row
+        tuned = TunedSigmoidL2(10.0, 1.0)
+        via_dist = binary_loss(emb, true, tuned, grad="sum", grad_params=True, n_node_host=sizes)
+        for k in ("sum_loss", "loss_per_graph", "false_positive_pairs", "false_negative_pairs", "grad_nodes"):
+            assert torch.equal(via_dist[k], out[k]), k           # the same arithmetic: equal
+        row["grad_params"] = [float(v) for v in via_dist["grad_params"].cpu()]
         row.update(timed({"device": (lambda: binary_loss(emb, true, n_node_host=sizes), 20),
                           "device_grad": (lambda: binary_loss(emb, true, grad="sum", n_node_host=sizes), 20),
+                          "dist": (lambda: binary_loss(emb, true, tuned, n_node_host=sizes), 20),
+                          "dist_grad": (lambda: binary_loss(emb, true, tuned, grad="sum", n_node_host=sizes), 20),
+                          "dist_grad_params": (lambda: binary_loss(emb, true, tuned, grad="sum", grad_params=True,
+                                                                   n_node_host=sizes), 20),
                           "dense": (lambda: dense(False), 20), "dense_grad": (lambda: dense(True), 20)}, repeats, sync))
         row["dense_over_device"] = round(row["dense_ms"]["median"] / row["device_ms"]["median"], 2)
         row["dense_over_device_grad"] = round(row["dense_grad_ms"]["median"] / row["device_grad_ms"]["median"], 2)
