@@ -87,6 +87,11 @@ def set_random_seed(seed):
     _GEN.manual_seed(int(seed))
 
 
+def _as_param(v):
+    """numpy or torch -> a contiguous fp32 torch tensor (the caller's own tensor where it already is one)"""
+    return torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(torch.float32).contiguous()
+
+
 # ----------------------------------------------------------------------------------------------
 # MLP  (gnn.py:159-180: snt.nets.MLP([latent]*(K-1)+[out], activate_final=False))
 # ----------------------------------------------------------------------------------------------
@@ -138,8 +143,7 @@ class MLP:
             raise ValueError(f"{self.name}: expected {len(self.layer_sizes)} layers, got {len(layers)}")
         params, fan_in = [], None
         for j, (w, b) in enumerate(layers):
-            w = torch.as_tensor(np.asarray(w) if not isinstance(w, torch.Tensor) else w).to(torch.float32).contiguous()
-            b = torch.as_tensor(np.asarray(b) if not isinstance(b, torch.Tensor) else b).to(torch.float32).contiguous()
+            w, b = _as_param(w), _as_param(b)
             if w.ndim != 2 or b.ndim != 1 or w.shape[1] != self.layer_sizes[j] or b.shape[0] != self.layer_sizes[j]:
                 raise ValueError(f"{self.name}: layer {j} has W{tuple(w.shape)} b{tuple(b.shape)}, "
                                  f"expected out width {self.layer_sizes[j]}")
@@ -300,8 +304,7 @@ class _AttentionParams:
         other keys are ignored."""
         p = {}
         for key in self.attn_keys():
-            w = attn[key]
-            w = torch.as_tensor(np.asarray(w) if not isinstance(w, torch.Tensor) else w).to(torch.float32).contiguous()
+            w = _as_param(attn[key])
             if w.ndim != (1 if key.startswith("ln_") else 2):
                 raise ValueError(f"{self.name}: {key} must be " + ("1-D [out]" if key.startswith("ln_") else "2-D [in, out]"))
             p[key] = w
@@ -320,7 +323,7 @@ def _xavier_uniform(fi, fo):
     return torch.empty(fi, fo).uniform_(-a, a, generator=_GEN)
 
 
-class DMSelfAttentionMLP(_NodeBlock):
+class DMSelfAttentionMLP(_AttentionParams, _NodeBlock):
     """gnn.py:480-553 (with DMSelfAttention, gnn.py:385-477, fused in): edge-list multi-head
     self-attention over the incoming edges of every node, heads concatenated and projected to
     `concat_heads_output_dim`, optionally concatenated with the node's own features, then the MLP.
@@ -356,9 +359,6 @@ class DMSelfAttentionMLP(_NodeBlock):
         return (type(self).__name__, self.num_heads, self.kq_dim, self.v_dim, self.concat_heads_output_dim,
                 self.concat, self.residual, self.layer_norm, self.kq_dim_division, self._mlp.act_code, self._mlp.alpha)
 
-    def attn_version(self):
-        return self._attn_version
-
     def _shapes(self, h):
         nq = self.num_heads * self.kq_dim
         shapes = {"wq": (h, nq), "wk": (h, nq), "wv": (h, self.v_dim),
@@ -368,54 +368,11 @@ class DMSelfAttentionMLP(_NodeBlock):
             shapes.update(ln_gamma=(w_out,), ln_beta=(w_out,))
         return shapes
 
-    def attn_keys(self):
-        return ("wq", "wk", "wv", "wo") + (("ln_gamma", "ln_beta") if self.layer_norm else ())
-
-    def ensure_attn_built(self, h, device):
-        if self.attn_params is None:
-            p = {}
-            for key, shp in self._shapes(h).items():
-                if len(shp) == 1:               # snt.LayerNorm: gamma = 1, beta = 0
-                    p[key] = torch.ones(shp) if key == "ln_gamma" else torch.zeros(shp)
-                    continue
-                fi, fo = shp
-                w = torch.empty(fi, fo)
-                if key == "wo":
-                    std = 1.0 / math.sqrt(fi)
-                    torch.nn.init.trunc_normal_(w, 0.0, std, -2 * std, 2 * std, generator=_GEN)
-                else:
-                    a = math.sqrt(6.0 / (fi + fo))
-                    w.uniform_(-a, a, generator=_GEN)
-                p[key] = w
-            self.attn_params = p
-            self._attn_version += 1
-            _touch()
-        for key, shp in self._shapes(h).items():
-            if tuple(self.attn_params[key].shape) != shp:
-                raise ValueError(f"{self.name}: {key} has shape {tuple(self.attn_params[key].shape)}, expected {shp}")
-        if self.attn_params["wq"].device != torch.device(device):
-            self.attn_params = {k: v.to(device) for k, v in self.attn_params.items()}
-            self._attn_version += 1
-            _touch()
-        return self
-
-    def set_attn_params(self, attn):
-        """attn: dict with wq, wk, wv, wo (numpy or torch, [in, out]) and, for a layer_norm block, ln_gamma, ln_beta
-        [MLP output width]; other keys are ignored."""
-        p = {}
-        for key in self.attn_keys():
-            w = attn[key]
-            w = torch.as_tensor(np.asarray(w) if not isinstance(w, torch.Tensor) else w).to(torch.float32).contiguous()
-            if w.ndim != (1 if key.startswith("ln_") else 2):
-                raise ValueError(f"{self.name}: {key} must be " + ("1-D [out]" if key.startswith("ln_") else "2-D [in, out]"))
-            p[key] = w
-        self.attn_params = p
-        self._attn_version += 1
-        _touch()
-        return self
-
-    def get_attn_params(self):
-        return None if self.attn_params is None else {k: v.detach().cpu().numpy().copy() for k, v in self.attn_params.items()}
+    def _init_weight(self, key, fi, fo):
+        if key != "wo":
+            return _xavier_uniform(fi, fo)
+        w, std = torch.empty(fi, fo), 1.0 / math.sqrt(fi)
+        return torch.nn.init.trunc_normal_(w, 0.0, std, -2 * std, 2 * std, generator=_GEN)
 
     def attn_desc(self, h, device):
         self.ensure_attn_built(h, device)
@@ -571,7 +528,57 @@ def get_gnns(num_timesteps, make_gnn_fn):            # gnn.py:266-267
 # ----------------------------------------------------------------------------------------------
 # make_batch_norm (gnn.py:260-263)
 # ----------------------------------------------------------------------------------------------
-class BatchNormBijector:
+class _NormParams:
+    """Variables of one normalisation, created at first connection: gamma, moving_variance = ones, beta, moving_mean = zeros
+    (KEYS says which), as fp32 tensors on the device; the containers that take batch moments (BATCH_VARIANCE: the initial
+    batch_variance) also own batch_mean / batch_variance of the last call.  Every re-binding bumps `version` and the epoch."""
+    KEYS = ("gamma", "beta", "moving_mean", "moving_variance")
+    WHAT = "batch norm"
+    BATCH_VARIANCE = None    # None: the container keeps no batch moments
+    OWN_COPY = True          # set_params: 1-D tensors only, cloned (False: the caller's tensors as they are)
+
+    def __init__(self):
+        self.gamma = self.beta = self.moving_mean = self.moving_variance = None
+        self.batch_mean = self.batch_variance = None
+        self.version = 0
+
+    def _rebound(self):
+        self.version += 1
+        _touch()
+
+    def ensure_built(self, width, device):
+        if self.gamma is None:
+            for k in self.KEYS:
+                setattr(self, k, torch.ones(width) if k in ("gamma", "moving_variance") else torch.zeros(width))
+            self._rebound()
+        if self.gamma.shape[0] != width:
+            raise ValueError(f"{self.WHAT} built for width {self.gamma.shape[0]}, connected to {width}")
+        moments = self.BATCH_VARIANCE is not None
+        if self.gamma.device != torch.device(device) or (moments and self.batch_mean is None):
+            for k in self.KEYS:
+                setattr(self, k, getattr(self, k).to(device=device, dtype=torch.float32).contiguous())
+            if moments:
+                self.batch_mean = torch.zeros(width, dtype=torch.float32, device=device)
+                self.batch_variance = torch.full((width,), self.BATCH_VARIANCE, dtype=torch.float32, device=device)
+            self._rebound()
+        return self
+
+    def set_params(self, d):
+        for k in self.KEYS:
+            v = _as_param(d[k])
+            if self.OWN_COPY:
+                v = v.clone()
+                if v.ndim != 1:
+                    raise ValueError(f"{self.WHAT} {k} must be 1-D [D]")
+            setattr(self, k, v)
+        self.batch_mean = None
+        self._rebound()
+
+    def get_params(self):
+        return {k: getattr(self, k).detach().cpu().numpy().copy() for k in self.KEYS}
+
+
+class BatchNormBijector(_NormParams):
     """tfb.BatchNormalization(batchnorm_layer=tf.layers.BatchNormalization(axis=-1,
     gamma_constraint=lambda x: relu(x) + 1e-6), training=True): variables gamma (ones), beta (zeros),
     moving_mean (zeros), moving_variance (ones), epsilon 1e-3, momentum 0.99 (tf.layers defaults), created at
@@ -580,43 +587,8 @@ class BatchNormBijector:
     applies (UPDATE_OPS + the optimizer's constraint projection)."""
     epsilon = 1e-3
     momentum = 0.99
-
-    def __init__(self):
-        self.gamma = self.beta = self.moving_mean = self.moving_variance = None
-        self.batch_mean = self.batch_variance = None
-        self.version = 0
-
-    def ensure_built(self, hdim, device):
-        if self.gamma is None:
-            self.gamma = torch.ones(hdim)
-            self.beta = torch.zeros(hdim)
-            self.moving_mean = torch.zeros(hdim)
-            self.moving_variance = torch.ones(hdim)
-            self.version += 1
-            _touch()
-        if self.gamma.shape[0] != hdim:
-            raise ValueError(f"batch norm built for width {self.gamma.shape[0]}, connected to {hdim}")
-        if self.gamma.device != torch.device(device) or self.batch_mean is None:
-            for k in ("gamma", "beta", "moving_mean", "moving_variance"):
-                setattr(self, k, getattr(self, k).to(device=device, dtype=torch.float32).contiguous())
-            self.batch_mean = torch.zeros(hdim, dtype=torch.float32, device=device)
-            self.batch_variance = torch.ones(hdim, dtype=torch.float32, device=device)
-            self.version += 1
-            _touch()
-        return self
-
-    def set_params(self, d):
-        for k in ("gamma", "beta", "moving_mean", "moving_variance"):
-            v = d[k]
-            v = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(torch.float32).contiguous()
-            setattr(self, k, v)
-        self.batch_mean = None
-        self.version += 1
-        _touch()
-
-    def get_params(self):
-        return {k: getattr(self, k).detach().cpu().numpy().copy()
-                for k in ("gamma", "beta", "moving_mean", "moving_variance")}
+    BATCH_VARIANCE = 1.0
+    OWN_COPY = False
 
     def fill_desc(self, desc):
         desc.gamma, desc.beta = self.gamma.data_ptr(), self.beta.data_ptr()
@@ -637,6 +609,20 @@ class BatchNormBijector:
 
 def make_batch_norm():                                # gnn.py:260-263
     return BatchNormBijector()
+
+
+def _set_net(block, net):
+    """one net of a parameter container into its block: [(W, b), ...] or, for an attention block,
+    {"attn": {wq, wk, wv, wo, ...}, "mlp": [(W, b), ...]}"""
+    if isinstance(net, dict):
+        block.set_attn_params(net["attn"])
+        net = net["mlp"]
+    block._mlp.set_params(net)
+
+
+def _get_net(block):
+    mlp = block._mlp.get_params()
+    return {"attn": block.get_attn_params(), "mlp": mlp} if hasattr(block, "get_attn_params") else mlp
 
 
 # ----------------------------------------------------------------------------------------------
@@ -700,11 +686,7 @@ class GRevNet:
         for kind in ("s", "t"):
             flat = list(params[kind]) if self.weight_sharing else list(params[kind][0]) + list(params[kind][1])
             for blk, net in zip(self.blocks(kind), flat):
-                if isinstance(net, dict):       # attention net: {"attn": {wq, wk, wv, wo, ...}, "mlp": [...]}
-                    blk.set_attn_params(net["attn"])
-                    blk._mlp.set_params(net["mlp"])
-                else:
-                    blk._mlp.set_params(net)
+                _set_net(blk, net)
         if "bn" in params and params["bn"] is not None:   # [[{gamma, beta, moving_mean, moving_variance}]*T]*2
             for half in range(2):
                 for i in range(self.num_timesteps):
@@ -715,8 +697,7 @@ class GRevNet:
     def get_params(self):
         out = {}
         for kind in ("s", "t"):
-            flat = [({"attn": b.get_attn_params(), "mlp": b._mlp.get_params()} if hasattr(b, "get_attn_params")
-                     else b._mlp.get_params()) for b in self.blocks(kind)]
+            flat = [_get_net(b) for b in self.blocks(kind)]
             t = self.num_timesteps
             out[kind] = flat if self.weight_sharing else [flat[:t], flat[t:]]
         if self.use_batch_norm and self.bns[0] and self.bns[0][0].gamma is not None:
@@ -940,75 +921,23 @@ class GRevNet:
 # ----------------------------------------------------------------------------------------------
 # TimestepGNN (gnn.py:183-235): the encoder of the graph auto-encoder (run_gnn.py:230-239)
 # ----------------------------------------------------------------------------------------------
-class SntBatchNorm:
+class SntBatchNorm(_NormParams):
     """snt.BatchNorm(scale=True) of one encoder timestep (gnn.py:210-213): gamma (ones), beta (zeros), moving_mean (zeros),
     moving_variance (ones), created at first connection; eps 1e-3 and decay_rate 0.999 are Sonnet-1's constructor defaults
     (third party, absent: UNPINNED - include/gnf_timestep_gnn.h lists what is restated).  The arithmetic AND the
     moving-average update of a training call run inside gnf_timestep_gnn_f32; this object owns the variables and the batch
     moments of the last call that took them."""
-    KEYS = ("gamma", "beta", "moving_mean", "moving_variance")
-
-    def __init__(self):
-        self.gamma = self.beta = self.moving_mean = self.moving_variance = None
-        self.batch_mean = self.batch_variance = None
-
-    def ensure_built(self, width, device):
-        if self.gamma is None:
-            self.gamma, self.beta = torch.ones(width), torch.zeros(width)
-            self.moving_mean, self.moving_variance = torch.zeros(width), torch.ones(width)
-        if self.gamma.shape[0] != width:
-            raise ValueError(f"batch norm built for width {self.gamma.shape[0]}, connected to {width}")
-        if self.gamma.device != torch.device(device) or self.batch_mean is None:
-            for k in self.KEYS:
-                setattr(self, k, getattr(self, k).to(device=device, dtype=torch.float32).contiguous())
-            self.batch_mean = torch.zeros(width, dtype=torch.float32, device=device)
-            self.batch_variance = torch.zeros(width, dtype=torch.float32, device=device)
-        return self
-
-    def set_params(self, d):
-        for k in self.KEYS:
-            v = d[k]
-            v = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(torch.float32).contiguous().clone()
-            if v.ndim != 1:
-                raise ValueError(f"batch norm {k} must be 1-D [D]")
-            setattr(self, k, v)
-        self.batch_mean = None
-
-    def get_params(self):
-        return {k: getattr(self, k).detach().cpu().numpy().copy() for k in self.KEYS}
+    BATCH_VARIANCE = 0.0
 
     def fill_desc(self, desc):
         for k in self.KEYS + ("batch_mean", "batch_variance"):
             setattr(desc, k, getattr(self, k).data_ptr())
 
 
-class RowLayerNorm:
+class RowLayerNorm(_NormParams):
     """snt.LayerNorm() of one encoder timestep (gnn.py:214-215): gamma (ones), beta (zeros) of the node width."""
     KEYS = ("gamma", "beta")
-
-    def __init__(self):
-        self.gamma = self.beta = None
-
-    def ensure_built(self, width, device):
-        if self.gamma is None:
-            self.gamma, self.beta = torch.ones(width), torch.zeros(width)
-        if self.gamma.shape[0] != width:
-            raise ValueError(f"layer norm built for width {self.gamma.shape[0]}, connected to {width}")
-        if self.gamma.device != torch.device(device):
-            for k in self.KEYS:
-                setattr(self, k, getattr(self, k).to(device=device, dtype=torch.float32).contiguous())
-        return self
-
-    def set_params(self, d):
-        for k in self.KEYS:
-            v = d[k]
-            v = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).to(torch.float32).contiguous().clone()
-            if v.ndim != 1:
-                raise ValueError(f"layer norm {k} must be 1-D [D]")
-            setattr(self, k, v)
-
-    def get_params(self):
-        return {k: getattr(self, k).detach().cpu().numpy().copy() for k in self.KEYS}
+    WHAT = "layer norm"
 
 
 class TimestepGNN:
@@ -1052,11 +981,7 @@ class TimestepGNN:
         if len(nets) != len(self.gnns):
             raise ValueError(f"{self.name}: expected {len(self.gnns)} nets, got {len(nets)}")
         for blk, net in zip(self.blocks(), nets):
-            if isinstance(net, dict):
-                blk.set_attn_params(net["attn"])
-                blk._mlp.set_params(net["mlp"])
-            else:
-                blk._mlp.set_params(net)
+            _set_net(blk, net)
         for key, objs in (("bn", self.bns), ("ln", self.lns)):
             if objs and params.get(key) is not None:
                 if len(params[key]) != len(objs):
@@ -1066,8 +991,7 @@ class TimestepGNN:
         return self
 
     def get_params(self):
-        out = {"nets": [({"attn": b.get_attn_params(), "mlp": b._mlp.get_params()} if hasattr(b, "get_attn_params")
-                         else b._mlp.get_params()) for b in self.blocks()]}
+        out = {"nets": [_get_net(b) for b in self.blocks()]}
         if self.bns and self.bns[0].gamma is not None:
             out["bn"] = [b.get_params() for b in self.bns]
         if self.lns and self.lns[0].gamma is not None:
@@ -1112,15 +1036,7 @@ class TimestepGNN:
 
     def _build(self, graph, is_training):
         lib = _abi.lib()
-        x = graph.nodes
-        if x.device.type != "cuda":
-            raise _abi.GnfError("TimestepGNN runs on a HIP device only (no CPU path)")
-        if x.ndim != 2 or x.shape[1] < 1:
-            raise ValueError(f"nodes must be [N, D] with D >= 1; got {tuple(x.shape)}")
-        x = x.to(torch.float32)
-        n, d = x.shape
-        if n > 0 and (x.stride(1) != 1 or x.stride(0) < d):
-            x = x.contiguous()
+        x, n, d, ldx = self._prepare(graph)
         dev = x.device
         desc, keep = self._desc(d, dev, is_training)
         csr = csr_desc(graph, csr_of(graph), self.blocks()[0].graph_scope)
@@ -1128,9 +1044,8 @@ class TimestepGNN:
         with torch.cuda.device(dev):
             ws_bytes = lib.gnf_timestep_gnn_workspace_bytes(n, d, C.byref(desc))
             ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-            _abi.check(lib.gnf_timestep_gnn_f32(C.byref(csr), C.byref(desc), _abi.ptr(x), x.stride(0) if n > 1 else max(int(x.stride(0)), d),
-                                                _abi.ptr(out), d, d, _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                       "gnf_timestep_gnn_f32")
+            _abi.check(lib.gnf_timestep_gnn_f32(C.byref(csr), C.byref(desc), _abi.ptr(x), ldx, _abi.ptr(out), d, d,
+                                                _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_timestep_gnn_f32")
         del keep
         took = self.bns and n > 0 and (bool(is_training) or self.test_local_stats)
         self.last_batch_moments = [(b.batch_mean, b.batch_variance) for b in self.bns] if took else None

@@ -24,9 +24,34 @@ import math
 import torch
 
 from . import _abi
-from .gnn import _touch as _gnn_touch
+from .gnn import _EPOCH, _touch as _gnn_touch
 from .flow import LN_2PI
 from .graphs import csr_desc, csr_of
+from .params import ParamArena
+
+
+def _adopt(trainer, arena):
+    """the trainer's public theta / grad / m / v are the arena's"""
+    trainer.theta, trainer.grad, trainer.m, trainer.v = arena.theta, arena.grad, arena.m, arena.v
+
+
+def _host_copy(tree):
+    """a container of device tensors as the same container of numpy arrays"""
+    if isinstance(tree, dict):
+        return {k: _host_copy(v) for k, v in tree.items()}
+    if isinstance(tree, (list, tuple)):
+        return type(tree)(_host_copy(v) for v in tree)
+    return tree.detach().cpu().numpy().copy()
+
+
+def _adam_step(tr, learning_rate, stream):
+    """tf.train.AdamOptimizer(lr, beta1, beta2, epsilon).apply_gradients over the whole arena: the bias-corrected step size
+    of step global_step + 1 on the host, one gnf_adam_f32 launch (the caller has made theta's device current)."""
+    t = tr.global_step + 1
+    lr_t = learning_rate * math.sqrt(1.0 - tr.beta2 ** t) / (1.0 - tr.beta1 ** t)
+    _abi.check(_abi.lib().gnf_adam_f32(_abi.ptr(tr.theta), _abi.ptr(tr.grad), _abi.ptr(tr.m), _abi.ptr(tr.v), tr.theta.numel(),
+                                       lr_t, tr.beta1, tr.beta2, tr.epsilon, stream), "gnf_adam_f32")
+    tr.global_step = t
 
 
 class _StepTerms(dict):
@@ -79,19 +104,18 @@ class GRevNetTrainer:
         self.clip_by_norm, self.clip_norm = bool(clip_gradient_by_norm), float(clip_gradient_norm)
         self.global_step = 0
         self.theta = self.grad = self.m = self.v = None
+        self._arena = ParamArena()
+        self._grads = None       # views of self.grad in get_params()'s layout (named_gradients)
         self._grad_flow = None
         self._keep = None
         self._offsets = None
         self._ws = None
         self._bns = []
-        self._attn_blocks = []
         self._clip_ws = None     # scratch of the two-pass clip_by_norm
         self._stash = None       # attention front-end stash (uint8 device buffer), see loss_and_grads
         self.stash_attention = True          # False: recompute the attention front-end in the backward walk
         self.stash_mlp_rows = True           # False: recompute the MLP rows too (the fully reversible walk)
         self._mlp_stash = None
-        self._arena_versions = None   # version counters of every parameter container when the arena was (re)built
-        self._arena_epoch = -1
         self._aux = None         # second HIP stream: the weight-gradient GEMMs overlap the backward walk
         self.overlap_weight_grads = True     # False: no auxiliary stream for the weight-gradient GEMMs
         # the MLP-row stash is memory for time (wide nets: 2T slots of every hidden activation - about 20 GB for 30 k nodes
@@ -103,174 +127,75 @@ class GRevNetTrainer:
 
     # ---- parameter arena ---------------------------------------------------------------------
     def _ensure_arena(self, hdim, device):
-        net = self.net
+        """theta / grad / m / v over every variable of the flow, in ONE order: the MLPs of s then t ((W, b) per layer), the
+        attention blocks of s then t (attn_keys()), the bijectors' gamma, beta (index half*T + i; their moving statistics are
+        not trained).  Re-seated when somebody called set_params / set_attn_params (or moved the net) since: their tensors
+        live OUTSIDE theta, so Adam would go on updating a vector nothing reads."""
+        net, arena = self.net, self._arena
         net._flow(hdim, device)                      # builds lazily-initialised MLPs (Sonnet-style first connect)
-        from .gnn import _EPOCH
-        if self.theta is not None and self.theta.device == torch.device(device) and self._arena_epoch == _EPOCH[0]:
-            return                                   # no parameter container anywhere was touched since the arena was built
+        if arena.is_seated(device, _EPOCH[0]):
+            return
         mlps = net.mlps("s") + net.mlps("t")
-        blocks = net.blocks("s") + net.blocks("t")
-        attn_blocks = [b for b in blocks if getattr(b, "attn_params", None) is not None]
-        bns = [b for half in net.bns for b in half] if net.use_batch_norm else []   # index half*T + i
-
-        def versions():
-            return (tuple(m.version for m in mlps), tuple(b.attn_version() for b in blocks), tuple(b.version for b in bns))
-        if self.theta is not None and self.theta.device == torch.device(device):
-            # the parameter containers were last (re)bound by this trainer: nothing to do.  Otherwise somebody called
-            # set_params / set_attn_params (or moved the net) since: their tensors live OUTSIDE theta, so Adam would go on
-            # updating a vector nothing reads - re-seat the arena on the new values (Adam moments kept when the
-            # model size is unchanged)
-            if self._arena_versions == versions():
-                self._arena_epoch = _EPOCH[0]
-                return
-        old_m, old_v = self.m, self.v
-        sizes = []
-        for m in mlps:
-            for (w, b) in m.params:
-                sizes += [w.numel(), b.numel()]
-        for blk in attn_blocks:                       # attention front-end: wq, wk, wv, wo (+ ln_gamma, ln_beta)
-            sizes += [blk.attn_params[k].numel() for k in blk.attn_keys()]
-        for b in bns:                                 # trainable: gamma, beta (the moving statistics are not)
-            sizes += [b.gamma.numel(), b.beta.numel()]
-        total = sum(sizes)
-        theta = torch.empty(total, dtype=torch.float32, device=device)
-        off, bounds = 0, [0]
-        for m in mlps:
-            views = []
-            for (w, b) in m.params:
-                wv = theta[off:off + w.numel()].view_as(w)
-                wv.copy_(w)
-                off += w.numel()
-                bounds.append(off)
-                bv = theta[off:off + b.numel()].view_as(b)
-                bv.copy_(b)
-                off += b.numel()
-                bounds.append(off)
-                views.append((wv, bv))
-            m.params = views                          # the MLP now reads / is updated through the arena
-            m.version += 1
+        blocks = [b for b in net.blocks("s") + net.blocks("t") if getattr(b, "attn_params", None) is not None]
+        bns = [b for half in net.bns for b in half] if net.use_batch_norm else []
+        slots = [(m, "params", j, h) for m in mlps for j in range(len(m.params)) for h in (0, 1)]
+        slots += [(b, "attn_params", k) for b in blocks for k in b.attn_keys()]
+        slots += [(b, k) for b in bns for k in ("gamma", "beta")]
+        _adopt(self, arena.seat(slots, device))
+        for c in mlps + bns:                          # the containers now read / are updated through the arena
+            c.version += 1
             _gnn_touch()
-        self._attn_off = off
-        for blk in attn_blocks:
-            views = {}
-            for k in blk.attn_keys():
-                old = blk.attn_params[k]
-                view = theta[off:off + old.numel()].view_as(old)
-                view.copy_(old)
-                views[k] = view
-                off += old.numel()
-                bounds.append(off)
-            blk.attn_params = views
-            blk._attn_version += 1
-            _gnn_touch()
-        self._bn_off = off
-        for b in bns:
-            for name in ("gamma", "beta"):
-                old = getattr(b, name)
-                view = theta[off:off + old.numel()]
-                view.copy_(old)
-                setattr(b, name, view)
-                off += old.numel()
-                bounds.append(off)
-            b.version += 1
+        for b in blocks:
+            b._attn_version += 1
             _gnn_touch()
         net._cache = None
-        self.theta = theta
-        self.grad = torch.zeros_like(theta)
-        keep = old_m is not None and old_m.numel() == total and old_m.device == theta.device
-        self.m = old_m if keep else torch.zeros_like(theta)
-        self.v = old_v if keep else torch.zeros_like(theta)
-        self._offsets = torch.tensor(bounds, dtype=torch.int64, device=device)
-        # gradient flow descriptor: same shapes, W / b pointing into self.grad
-        n = len(net.mlps("s"))
-        gs, gt = (_abi.GnfMlp * n)(), (_abi.GnfMlp * n)()
-        off = 0
-        for arr, ms in ((gs, net.mlps("s")), (gt, net.mlps("t"))):
-            for q, m in enumerate(ms):
-                arr[q].num_layers = len(m.layer_sizes)
-                for j, d in enumerate(m.dims()):
-                    arr[q].dims[j] = d
-                for j, (w, b) in enumerate(m.params):
-                    arr[q].W[j] = self.grad.data_ptr() + 4 * off
-                    off += w.numel()
-                    arr[q].b[j] = self.grad.data_ptr() + 4 * off
-                    off += b.numel()
-        gattn = None
-        if attn_blocks:                               # gradient GnfAttn per net, hung off the gradient GnfMlp
-            gattn = (_abi.GnfAttn * len(attn_blocks))()
-            for q, blk in enumerate(attn_blocks):     # order: s nets then t nets, like `blocks`
-                ga = gattn[q]
-                ga.num_heads, ga.kq_dim, ga.v_dim, ga.out_dim = blk.num_heads, blk.kq_dim, blk.v_dim, blk.concat_heads_output_dim
-                ga.layer_norm = int(blk.layer_norm)
-                ga.scope = _abi.GNF_ATTN_GRAPH if blk.graph_scope else _abi.GNF_ATTN_EDGES
-                ptrs = {}
-                for k in blk.attn_keys():
-                    ptrs[k] = self.grad.data_ptr() + 4 * off
-                    off += blk.attn_params[k].numel()
-                ga.Wq, ga.Wk, ga.Wv, ga.Wo = ptrs["wq"], ptrs["wk"], ptrs["wv"], ptrs.get("wo", 0)   # (SelfAttention: no wo)
-                if blk.layer_norm:
-                    ga.ln_gamma, ga.ln_beta = ptrs["ln_gamma"], ptrs["ln_beta"]
-                arr = gs if q < n else gt
-                arr[q % n].attn = C.cast(C.byref(gattn, q * C.sizeof(_abi.GnfAttn)), C.POINTER(_abi.GnfAttn))
-        spec = net.blocks("s")[0].spec()
-        gbn = None
+        arena.epoch = _EPOCH[0]
+        self._offsets, self._bns = arena.offsets, bns
+        # the gradient in the parameter container's layout (named_gradients) and as a flow descriptor: same shapes, every
+        # pointer a view of self.grad
+        g = iter(arena.grad_views)
+        g_mlps = [[(next(g), next(g)) for _ in m.params] for m in mlps]
+        g_attn = [{k: next(g) for k in b.attn_keys()} for b in blocks]
+        g_bns = [{"gamma": next(g), "beta": next(g)} for _ in bns]
+        n, t = len(mlps) // 2, net.num_timesteps
+        nets = [{"attn": a, "mlp": m} for a, m in zip(g_attn, g_mlps)] if blocks else g_mlps
+        halves = lambda flat: flat if net.weight_sharing else [flat[:t], flat[t:]]
+        self._grads = {"s": halves(nets[:n]), "t": halves(nets[n:])}
         if bns:
-            gbn = (_abi.GnfBatchNorm * len(bns))()
-            for q, b in enumerate(bns):
-                gbn[q].gamma = self.grad.data_ptr() + 4 * off
-                off += b.gamma.numel()
-                gbn[q].beta = self.grad.data_ptr() + 4 * off
-                off += b.beta.numel()
+            self._grads["bn"] = [g_bns[:t], g_bns[t:]]
+        gs, gt = (_abi.GnfMlp * n)(), (_abi.GnfMlp * n)()
+        for q, (m, layers) in enumerate(zip(mlps, g_mlps)):
+            desc = (gs if q < n else gt)[q % n]
+            desc.num_layers = len(m.layer_sizes)
+            for j, d in enumerate(m.dims()):
+                desc.dims[j] = d
+            for j, (gw, gb) in enumerate(layers):
+                desc.W[j], desc.b[j] = gw.data_ptr(), gb.data_ptr()
+        gattn = (_abi.GnfAttn * len(blocks))() if blocks else None   # gradient GnfAttn per net, hung off the gradient GnfMlp
+        for q, (blk, ptrs) in enumerate(zip(blocks, g_attn)):       # order: s nets then t nets
+            ga = gattn[q]
+            ga.num_heads, ga.kq_dim, ga.v_dim, ga.out_dim = blk.num_heads, blk.kq_dim, blk.v_dim, blk.concat_heads_output_dim
+            ga.layer_norm = int(blk.layer_norm)
+            ga.scope = _abi.GNF_ATTN_GRAPH if blk.graph_scope else _abi.GNF_ATTN_EDGES
+            ga.Wq, ga.Wk, ga.Wv = ptrs["wq"].data_ptr(), ptrs["wk"].data_ptr(), ptrs["wv"].data_ptr()
+            ga.Wo = ptrs["wo"].data_ptr() if "wo" in ptrs else 0      # (SelfAttention: no wo)
+            if blk.layer_norm:
+                ga.ln_gamma, ga.ln_beta = ptrs["ln_gamma"].data_ptr(), ptrs["ln_beta"].data_ptr()
+            (gs if q < n else gt)[q % n].attn = C.cast(C.byref(gattn, q * C.sizeof(_abi.GnfAttn)), C.POINTER(_abi.GnfAttn))
+        gbn = (_abi.GnfBatchNorm * len(bns))() if bns else None
+        for q, gd in enumerate(g_bns):
+            gbn[q].gamma, gbn[q].beta = gd["gamma"].data_ptr(), gd["beta"].data_ptr()
         self._grad_flow = _abi.GnfFlow(net.num_timesteps, int(net.weight_sharing),
-                                       C.cast(gs, C.POINTER(_abi.GnfMlp)), C.cast(gt, C.POINTER(_abi.GnfMlp)), spec,
+                                       C.cast(gs, C.POINTER(_abi.GnfMlp)), C.cast(gt, C.POINTER(_abi.GnfMlp)),
+                                       net.blocks("s")[0].spec(),
                                        C.cast(gbn, C.POINTER(_abi.GnfBatchNorm)) if gbn is not None else None)
         self._keep = (gs, gt, gbn, gattn)
-        self._bns = bns
-        self._attn_blocks = attn_blocks
-        self._arena_versions = versions()            # as left by the re-binding above
-        self._arena_epoch = _EPOCH[0]
 
     def named_gradients(self):
-        """Gradients in the oracle / fixture container layout ({"s": [[mlp]*T, [mlp]*T], "t": ...}; mlp =
-        [(dW, db), ...]) as numpy arrays (host copy; for tests and summaries)."""
-        net, out, off = self.net, {}, 0
-        g = self.grad.detach().cpu().numpy()
-        for kind in ("s", "t"):
-            flat = []
-            for m in net.mlps(kind):
-                layers = []
-                for (w, b) in m.params:
-                    dw = g[off:off + w.numel()].reshape(tuple(w.shape)).copy()
-                    off += w.numel()
-                    db = g[off:off + b.numel()].copy()
-                    off += b.numel()
-                    layers.append((dw, db))
-                flat.append(layers)
-            t = net.num_timesteps
-            out[kind] = flat if net.weight_sharing else [flat[:t], flat[t:]]
-        if self._attn_blocks:      # attention nets: {"attn": {wq, wk, wv, wo}, "mlp": [...]} like the parameter container
-            per_block = []
-            for blk in self._attn_blocks:
-                d = {}
-                for k in blk.attn_keys():
-                    w = blk.attn_params[k]
-                    d[k] = g[off:off + w.numel()].reshape(tuple(w.shape)).copy()
-                    off += w.numel()
-                per_block.append(d)
-            nb = len(net.mlps("s"))
-            for ki, kind in enumerate(("s", "t")):
-                flat = out[kind] if net.weight_sharing else out[kind][0] + out[kind][1]
-                wrapped = [{"attn": per_block[ki * nb + q], "mlp": mlp} for q, mlp in enumerate(flat)]
-                t = net.num_timesteps
-                out[kind] = wrapped if net.weight_sharing else [wrapped[:t], wrapped[t:]]
-        if self._bns:
-            t, h = net.num_timesteps, self._bns[0].gamma.numel()
-            flat = []
-            for _ in self._bns:
-                flat.append({"gamma": g[off:off + h].copy(), "beta": g[off + h:off + 2 * h].copy()})
-                off += 2 * h
-            out["bn"] = [flat[:t], flat[t:]]
-        return out
+        """Gradients in the oracle / fixture container layout ({"s": [[mlp]*T, [mlp]*T], "t": ...}; mlp = [(dW, db), ...],
+        attention nets {"attn": {...}, "mlp": mlp}; "bn": [[{gamma, beta}]*T]*2) as numpy arrays (host copy; for tests and
+        summaries)."""
+        return _host_copy(self._grads)
 
     # ---- compute_gradients ---------------------------------------------------------------------
     def loss_and_grads(self, graph):
@@ -362,8 +287,6 @@ class GRevNetTrainer:
         lib = _abi.lib()
         dev = self.theta.device
         lr = self.current_learning_rate() if learning_rate is None else float(learning_rate)
-        t = self.global_step + 1
-        lr_t = lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
         n = self.theta.numel()
         with torch.cuda.device(dev):
             st = _abi.stream_ptr(dev)
@@ -377,15 +300,13 @@ class GRevNetTrainer:
                     self._clip_ws = torch.empty(max(cb, 8), dtype=torch.uint8, device=dev)
                 _abi.check(lib.gnf_clip_by_norm_f32(_abi.ptr(self.grad), _abi.ptr(self._offsets), nt, self.clip_norm,
                                                     _abi.ptr(self._clip_ws), cb, st), "gnf_clip_by_norm_f32")
-            _abi.check(lib.gnf_adam_f32(_abi.ptr(self.theta), _abi.ptr(self.grad), _abi.ptr(self.m), _abi.ptr(self.v),
-                                        n, lr_t, self.beta1, self.beta2, self.epsilon, st), "gnf_adam_f32")
+            _adam_step(self, lr, st)
             h = self.net.mlps("s")[0].layer_sizes[-1]
             flow = self.net._flow(h, dev)
             if self.net.fused:
                 _abi.check(lib.gnf_pack_flow(C.byref(flow), st), "gnf_pack_flow")
             if self._bns:          # gamma_constraint projection (gnn.py:261-262) + UPDATE_OPS (run_grevnet.py:360), one launch
                 _abi.check(lib.gnf_bn_post_step_f32(C.byref(flow), h, self._bns[0].momentum, st), "gnf_bn_post_step_f32")
-        self.global_step = t
 
     def all_reduce_gradients(self, group=None):
         """Data parallelism: total_loss is a SUM over nodes (run_grevnet.py:295), so the gradient of the global
@@ -422,28 +343,36 @@ def mlp_stash_within_budget(stash_bytes, free_bytes, max_bytes=None, free_fracti
 
 
 # ---- the trainer's state: what the drivers checkpoint through tf.train.Saver (run_grevnet.py:379, 449-453) --------------
-def trainer_state(tr):
-    """Everything a resumed run needs: parameters, Adam moments, step counter, batch-norm moving statistics (host copies)."""
+def _state(tr, bns):
     if tr.theta is None:
         raise RuntimeError("run a step (or loss_and_grads) first so that the variables exist")
     return {"theta": tr.theta.detach().cpu(), "m": tr.m.detach().cpu(), "v": tr.v.detach().cpu(),
             "global_step": tr.global_step,
-            "bn_moving": [(b.moving_mean.detach().cpu(), b.moving_variance.detach().cpu()) for b in tr._bns]}
+            "bn_moving": [(b.moving_mean.detach().cpu(), b.moving_variance.detach().cpu()) for b in bns]}
 
 
-def load_trainer_state(tr, state):
-    """Restore `trainer_state`'s dict into a connected trainer; the matrix-core weight copies follow (gnf_pack_flow)."""
+def _load_state(tr, bns, state, what):
     if tr.theta is None:
         raise RuntimeError("connect the trainer first (run loss_and_grads on a batch)")
     if state["theta"].numel() != tr.theta.numel():
-        raise ValueError(f"checkpoint has {state['theta'].numel()} parameters, the flow has {tr.theta.numel()}")
+        raise ValueError(f"checkpoint has {state['theta'].numel()} parameters, the {what} has {tr.theta.numel()}")
     tr.theta.copy_(state["theta"])
     tr.m.copy_(state["m"])
     tr.v.copy_(state["v"])
     tr.global_step = int(state["global_step"])
-    for b, (mm, mv) in zip(tr._bns, state["bn_moving"]):
+    for b, (mm, mv) in zip(bns, state["bn_moving"]):
         b.moving_mean.copy_(mm)
         b.moving_variance.copy_(mv)
+
+
+def trainer_state(tr):
+    """Everything a resumed run needs: parameters, Adam moments, step counter, batch-norm moving statistics (host copies)."""
+    return _state(tr, tr._bns)
+
+
+def load_trainer_state(tr, state):
+    """Restore `trainer_state`'s dict into a connected trainer; the matrix-core weight copies follow (gnf_pack_flow)."""
+    _load_state(tr, tr._bns, state, "flow")
     dev = tr.theta.device
     with torch.cuda.device(dev):
         flow = tr.net._flow(tr.net.mlps("s")[0].layer_sizes[-1], dev)
@@ -506,78 +435,39 @@ class EncoderTrainer:
         self.max_nodes_per_graph = max_nodes_per_graph
         self.global_step = 0
         self.theta = self.grad = self.m = self.v = None
+        self._arena = ParamArena()
         self._grads = None     # views of self.grad in TimestepGNN.make_grads' layout
-        self._bound = None     # [(owner description, data_ptr)] of every view handed out: detects a set_params since
 
     # ---- parameter arena ---------------------------------------------------------------------
-    def _variables(self):
-        """[(get, set, tensor)] in arena order: nets (W, b per layer), then bn gamma / beta per timestep, then ln"""
-        out = []
-        for m in (b._mlp for b in self.net.blocks()):
-            for j in range(len(m.params)):
-                out.append((m, j, 0)), out.append((m, j, 1))
-        for o in list(self.net.bns) + list(self.net.lns):
-            out.append((o, "gamma", None)), out.append((o, "beta", None))
-        return out
-
-    @staticmethod
-    def _get(var):
-        o, k, h = var
-        return o.params[k][h] if h is not None else getattr(o, k)
-
     def _ensure_arena(self, d, device):
-        net = self.net
-        device = torch.device(device)
-        net._desc(d, device, True)               # creates the variables at first connection (Sonnet style)
-        variables = self._variables()
-        if self.theta is not None and self.theta.device == device and \
-                [self._get(v).data_ptr() for v in variables] == self._bound:
+        """theta / grad / m / v in ONE order: the nets' (W, b) per layer, the batch norms' gamma, beta per timestep, the
+        layer norms', then (tune_sigmoid) temp, shift.  Re-seated when somebody called set_params (or moved the encoder)."""
+        net, arena = self.net, self._arena
+        if arena.is_seated(device, _EPOCH[0]):
             return
-        old_m, old_v = self.m, self.v
-        tensors = [self._get(v) for v in variables]
-        total = sum(t.numel() for t in tensors)
+        net._desc(d, torch.device(device), True)  # creates the variables at first connection (Sonnet style)
+        mlps, norms = [b._mlp for b in net.blocks()], list(net.bns) + list(net.lns)
+        slots = [(m, "params", j, h) for m in mlps for j in range(len(m.params)) for h in (0, 1)]
+        slots += [(o, k) for o in norms for k in ("gamma", "beta")]
         if self.tune_sigmoid:                     # temp, shift: the last two entries
             sigmoid = self.distance_fn.values()   # (a host read, when the arena is laid out only)
-            total += 2
-        theta = torch.empty(total, dtype=torch.float32, device=device)
-        grad = torch.zeros_like(theta)
-        views, gviews, off = [], [], 0
-        for t in tensors:
-            view = theta[off:off + t.numel()].view(t.shape)
-            view.copy_(t)
-            views.append(view)
-            gviews.append(grad[off:off + t.numel()].view(t.shape))
-            off += t.numel()
-        it, git = iter(views), iter(gviews)
-        grads = {"nets": []}
-        for m in (b._mlp for b in net.blocks()):
-            m.params = [(next(it), next(it)) for _ in m.params]
-            m.version += 1
+        _adopt(self, arena.seat(slots, device, trailing=2 if self.tune_sigmoid else 0))
+        for c in mlps + norms:                    # the containers now read / are updated through the arena
+            c.version += 1
             _gnn_touch()
-            grads["nets"].append([(next(git), next(git)) for _ in m.params])
+        arena.epoch = _EPOCH[0]
+        g = iter(arena.grad_views)
+        self._grads = {"nets": [[(next(g), next(g)) for _ in m.params] for m in mlps]}
         for key, objs in (("bn", net.bns), ("ln", net.lns)):
             if objs:
-                grads[key] = []
-                for o in objs:
-                    o.gamma, o.beta = next(it), next(it)
-                    grads[key].append({"gamma": next(git), "beta": next(git)})
+                self._grads[key] = [{"gamma": next(g), "beta": next(g)} for _ in objs]
         if self.tune_sigmoid:
-            theta[-2:].copy_(torch.tensor(sigmoid, dtype=torch.float32))
-            self.distance_fn.bind(theta[-2:])
-        keep = old_m is not None and old_m.numel() == total and old_m.device == device
-        self.theta, self.grad, self._grads = theta, grad, grads
-        self.m = old_m if keep else torch.zeros_like(theta)
-        self.v = old_v if keep else torch.zeros_like(theta)
-        self._bound = [self._get(v).data_ptr() for v in variables]
+            arena.tail.copy_(torch.tensor(sigmoid, dtype=torch.float32))
+            self.distance_fn.bind(arena.tail)
 
     def named_gradients(self):
         """The gradients in TimestepGNN.get_params()'s layout (without the moving statistics) as numpy arrays (host copy)."""
-        cp = lambda t: t.detach().cpu().numpy().copy()
-        out = {"nets": [[(cp(w), cp(b)) for (w, b) in net] for net in self._grads["nets"]]}
-        for key in ("bn", "ln"):
-            if key in self._grads:
-                out[key] = [{k: cp(v) for k, v in d.items()} for d in self._grads[key]]
-        return out
+        return _host_copy(self._grads)
 
     # ---- compute_gradients -----------------------------------------------------------------------
     def loss_and_grads(self, graph, true_graph=None):
@@ -607,16 +497,10 @@ class EncoderTrainer:
 
     def apply_gradients(self, learning_rate=None):
         """tf.train.AdamOptimizer(lr, beta1, beta2, epsilon).apply_gradients: one gnf_adam_f32 over the arena"""
-        lib = _abi.lib()
         dev = self.theta.device
         lr = self.current_learning_rate() if learning_rate is None else float(learning_rate)
-        t = self.global_step + 1
-        lr_t = lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
         with torch.cuda.device(dev):
-            _abi.check(lib.gnf_adam_f32(_abi.ptr(self.theta), _abi.ptr(self.grad), _abi.ptr(self.m), _abi.ptr(self.v),
-                                        self.theta.numel(), lr_t, self.beta1, self.beta2, self.epsilon, _abi.stream_ptr(dev)),
-                       "gnf_adam_f32")
-        self.global_step = t
+            _adam_step(self, lr, _abi.stream_ptr(dev))
 
     def step(self, graph, true_graph=None, learning_rate=None):
         """One iteration of run_gnn.py's loop: returns loss_and_grads' dict."""
@@ -641,22 +525,9 @@ def encoder_learning_rate(lr_type, lr, global_step, num_train_iters=200000, deca
 
 def encoder_trainer_state(tr):
     """What a resumed encoder run needs: parameters, Adam moments, step counter, the batch norms' moving statistics."""
-    if tr.theta is None:
-        raise RuntimeError("run a step (or loss_and_grads) first so that the variables exist")
-    return {"theta": tr.theta.detach().cpu(), "m": tr.m.detach().cpu(), "v": tr.v.detach().cpu(), "global_step": tr.global_step,
-            "bn_moving": [(b.moving_mean.detach().cpu(), b.moving_variance.detach().cpu()) for b in tr.net.bns]}
+    return _state(tr, tr.net.bns)
 
 
 def load_encoder_trainer_state(tr, state):
     """Restore encoder_trainer_state's dict into a connected trainer."""
-    if tr.theta is None:
-        raise RuntimeError("connect the trainer first (run loss_and_grads on a batch)")
-    if state["theta"].numel() != tr.theta.numel():
-        raise ValueError(f"checkpoint has {state['theta'].numel()} parameters, the encoder has {tr.theta.numel()}")
-    tr.theta.copy_(state["theta"])
-    tr.m.copy_(state["m"])
-    tr.v.copy_(state["v"])
-    tr.global_step = int(state["global_step"])
-    for b, (mm, mv) in zip(tr.net.bns, state["bn_moving"]):
-        b.moving_mean.copy_(mm)
-        b.moving_variance.copy_(mv)
+    _load_state(tr, tr.net.bns, state, "encoder")
