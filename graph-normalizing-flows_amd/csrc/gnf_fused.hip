@@ -123,6 +123,7 @@ namespace gnf {
 // wave's stage-0 weights), 5 + 2 j behind layer j's barrier, kTraceCoupled behind the coupling store, kTraceEnd kernel end.
 #ifdef GNF_TRACE
 static constexpr int kTraceSlots = 32, kTraceCoupled = kTraceSlots - 2, kTraceEnd = kTraceSlots - 1;
+static constexpr int kTracePhFlushed = 20;  // PHASES instance: the last pending store issued; + 1, + 2: behind the two closing barriers
 __shared__ unsigned long long s_trace[kFusedThreads / 64][kTraceSlots];
 static unsigned long long* g_trace_buf = nullptr;
 static int g_trace_cap = 0, g_trace_next = 0;
@@ -677,6 +678,9 @@ struct GeoLayout {  // the packed layout (launch_pack_mlp) of this geometry, in 
     static_assert(woff(1) == 16 * IN0G * 16 * LG && kBias == 16 * IN0G * 16 * LG + (K - 2) * 256 * LG * LG + 16 * LG * 16 * HG,
                   "sum of Ip x Op over the layers");
     static_assert(kLds <= (size_t)kLdsLimit, "activation buffers in LDS");
+    // the PHASES instance: all 8 waves on one net's layer at a time, tile stride kPhaseTs
+    static_assert(LG == 2 * kPhaseTs && kPhaseTs == kFusedThreads / 64, "a wave owns exactly two column tiles of a hidden layer of EACH net: one mlp_phase per net and layer");
+    static_assert(2 * HG <= kWpn, "the output layer's 2 HG accumulator chains go to waves 0 .. 2 HG - 1: one per SIMD");
 };
 
 // Memory order of the prologue: what has a known address goes out first - the rowptr slice, then this thread's own
@@ -688,7 +692,28 @@ struct GeoLayout {  // the packed layout (launch_pack_mlp) of this geometry, in 
 // measured slower.)  The weights still have the gather's two round trips to land in, and do: a layer's first operands are
 // there 128 cycles behind its barrier.  Only the order of requests and waits differs from the generic instance; every
 // product and sum is its own.
-template <int IN0G, int LG, int K, int HG>
+//
+// PHASES instance (what automatic dispatch runs; force_shape = kForceGeoParent keeps the one above): both nets in every wave.
+// Wave w owns column tiles {w, w + 8} of each hidden layer of the s-net and {w', w' + 8}, w' = (w + 6) % 8, of the t-net,
+// and runs the phases S0 T0 S1 T1 .. S(K-2) T(K-2) (mlp_phase, gnf_fused_dev.h; Sj / Tj = layer j of the s- / t-net), then
+// the output layer's thin chunks on waves 0 .. HG - 1 (s) and HG .. 2 HG - 1 (t): four chains on four SIMDs, as above.
+// A phase leaves its result in registers; the NEXT phase - the other net's, whose operands have been ready for a whole
+// phase - applies the activation and stores it in the shadow of its first stage's MFMAs, and the one workgroup barrier of
+// that phase follows right there (phase_barrier: LDS traffic only, the weight ring stays in flight), MFMAs on both sides.
+// Why one barrier per phase orders everything (each net has its own ping-pong pair; B(P) = the barrier inside phase P):
+//   read after write: layer j + 1 of a net reads what the phase behind layer j's flushed in front of ITS barrier; the reads
+//     are requested in that phase's last stages at the earliest (Sj's output: flushed in Tj, B(Tj), read from the end of
+//     Tj on; Tj's output: flushed in S(j+1), B(S(j+1)), read from the end of S(j+1) on).
+//   write after read: the buffer a flush writes is the one the same net's layer j - 1 wrote and layer j read.  Layer j's
+//     reads all returned before its wave issued that phase's last MFMAs, hence before the wave arrived at the NEXT
+//     barrier; the flush of layer j's output stands behind that barrier's release in every wave's program order (Sj reads
+//     until its end, every wave passes B(Tj) behind its own Sj, and the flush of S(j+1) into that buffer sits in T(j+1),
+//     behind B(S(j+1)): two barriers later).
+//   The output layer: S(K-1) reads what T(K-2)'s phase flushed and fenced; every wave flushes T(K-2) behind its last MFMA,
+//     one phase_barrier, then both thin chunks run side by side; they write the buffers layer K - 2 READ, whose reads ended
+//     in front of that barrier.  The closing __syncthreads() and couple_tile are the instance's above.
+// Every barrier is reached by all 8 waves in straight-line code; there is no other synchronisation.
+template <int IN0G, int LG, int K, int HG, bool PHASES = false>
 __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using G = GeoLayout<IN0G, LG, K, HG>;
@@ -712,7 +737,12 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
     // s_load can sink below this point (left alone, an argument is read where it is first used: a scalar round trip behind
     // a barrier or in the epilogue).  The values stay the compiler's - a pointer is still known to be a global one.  The
     // tile comes from n_tiles (= gridDim.x, launch_geo): the grid size sits in the hidden arguments, a round trip of its own.
-    const float* wnet = a.wp[nl];
+    const float* wnet = a.wp[PHASES ? 0 : nl];
+    // PHASES: both nets in every wave - s-net tiles {wave, wave + 8}; the t-net's rotated so that its output-layer tiles land
+    // on the two SIMDs the s-net's do not use (waves HG .. 2 HG - 1)
+    [[maybe_unused]] const float* wnet1 = a.wp[1];
+    [[maybe_unused]] const int wt_own = (wave + kPhaseTs - HG) % kPhaseTs;
+    if constexpr (PHASES) asm volatile("" ::"s"(wnet1));
 #ifdef GNF_TRACE
     asm volatile("" ::"s"(a.trace));
 #endif
@@ -770,14 +800,41 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
     if (staged && tid < seg_len) col_reg = a.col[seg_beg + tid];
     __builtin_amdgcn_sched_barrier(0);
     f32x4 b_pre[kPF][4];
+    // PHASES: the first stages of S0 (two tiles), and a lane's biases as the four consecutive columns its accumulators
+    // hold (mlp_phase): [net][layer][tile] f32x4, + the output layer's one float for the waves that run a thin chunk
+    [[maybe_unused]] f32x4 ph_b_pre[kPhasePF][2];
+    [[maybe_unused]] auto ph_pf = [](int j) constexpr { return G::ipg(j) < kPhasePF ? G::ipg(j) : kPhasePF; };  // stages a phase of layer j gets handed
+    [[maybe_unused]] f32x4 ph_bias[2][K - 1][2];
+    [[maybe_unused]] const int thin_net = wave >= HG && wave < 2 * HG;                    // (wave-uniform)
+    [[maybe_unused]] const bool thin_mine = wave < 2 * HG;
+    [[maybe_unused]] const int thin_tile = thin_mine ? (thin_net ? wt_own : wave) : 0;      // (a wave without one reads tile 0's: in bounds)
+    BiasRegs<4> bias_h[K - 1];
+    BiasRegs<1> bias_o;
+    if constexpr (PHASES) {
+        const __amdgpu_buffer_rsrc_t rs0 =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wnet), 0, G::ipg(0) * G::ont(0) * 1024, 0x00020000);
+#pragma unroll
+        for (int u = 0; u < ph_pf(0); ++u)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) ph_b_pre[u][b] = GNF_LOAD_B(rs0, voff, (u * G::ont(0) + wave + kPhaseTs * b) * 1024);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const float* bq = (q ? wnet1 : wnet) + G::kBias + 16 * (q ? wt_own : wave) + 4 * (lane >> 4);
+#pragma unroll
+            for (int j = 0; j < K - 1; ++j)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) ph_bias[q][j][b] = *reinterpret_cast<const f32x4*>(bq + G::boff(j) + 16 * kPhaseTs * b);
+        }
+        bias_o.v[0] = (thin_net ? wnet1 : wnet)[G::kBias + G::boff(K - 1) + 16 * thin_tile + (lane & 15)];
+    } else {
     prefetch_chunk(chunk(std::integral_constant<int, 0>{}), WPN, voff, b_pre, true);
     const float* bnet = wnet + G::kBias + 16 * wl + (lane & 15);
-    BiasRegs<4> bias_h[K - 1];
 #pragma unroll
     for (int j = 0; j < K - 1; ++j)
 #pragma unroll
         for (int b = 0; b < 4; ++b) bias_h[j].v[b] = bnet[G::boff(j) + 16 * WPN * b];
-    const BiasRegs<1> bias_o{{bnet[G::boff(K - 1) - (last_mine ? 0 : 16 * wl)]}};  // (a wave without a tile reads tile 0's: in bounds)
+    bias_o.v[0] = bnet[G::boff(K - 1) - (last_mine ? 0 : 16 * wl)];  // (a wave without a tile reads tile 0's: in bounds)
+    }
     __builtin_amdgcn_sched_barrier(0);
     if (staged) {
         if (tid < seg_len) s_col[tid] = col_reg;
@@ -792,6 +849,46 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
 
     // ---- B: the K layers, unrolled; the chunk after a wave's last one is that chunk again (harmless re-load) ----
     const float slope_h = a.act == GNF_ACT_RELU ? 0.f : a.alpha;
+    if constexpr (PHASES) {
+        // trace slots: 4 + 2 p the first MFMA of phase p (S0 T0 S1 ..: p = 2 j + net), 5 + 2 p behind its barrier (p >= 1),
+        // kTracePhFlushed the last pending store issued, + 1 behind the barrier in front of the thin chunks, + 2 behind the closing one
+        const int lrow = lane & 15, lgrp = lane >> 4;
+        const int lane_at = lrow * LS + 4 * lgrp;  // this lane's A row / its four accumulator columns inside a tile
+        f32x4 acc_s[2], acc_t[2], a_pre[kPhasePF];
+#pragma unroll
+        for (int u = 0; u < ph_pf(0); ++u) a_pre[u] = *reinterpret_cast<const f32x4*>(buf(0, 0) + lane_at + 16 * u);
+        WChunk thin;
+        thin.wbase = (thin_net ? wnet1 : wnet) + G::woff(K - 1);
+        thin.wbytes = (unsigned)G::ipg(K - 1) * (unsigned)G::ont(K - 1) * 1024u;
+        thin.ipg = G::ipg(K - 1), thin.ont = G::ont(K - 1), thin.boff = G::boff(K - 1), thin.nt0 = thin_tile, thin.nv = 1, thin.layer = K - 1;
+        epi_static_for<K - 1>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int pj = j & 1;
+            // Sj: flushes T(j-1) into the t-net's buffer layer j reads; next: Tj
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc_s[b] = ph_bias[0][j][b];
+            GNF_STAMP(4 + 4 * j);
+            mlp_phase<G::ipg(j), G::ont(j), ph_pf(j), (j > 0), PH_NEXT_HIDDEN, G::ipg(j), G::ont(j), ph_pf(j)>(
+                buf(0, pj) + lane_at, wnet + G::woff(j), wave, acc_s, a_pre, ph_b_pre, acc_t, buf(1, pj) + lane_at + 16 * wt_own, slope_h,
+                buf(1, pj) + lane_at, wnet1 + G::woff(j), wt_own, thin, b_pre, voff, [&] { GNF_STAMP(5 + 4 * j); });
+            // Tj: flushes Sj; next: S(j+1), or the thin chunk's weights
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc_t[b] = ph_bias[1][j][b];
+            GNF_STAMP(6 + 4 * j);
+            constexpr int jn = j + 1 < K - 1 ? j + 1 : j;
+            mlp_phase<G::ipg(j), G::ont(j), ph_pf(j), true, (j + 1 < K - 1 ? PH_NEXT_HIDDEN : PH_NEXT_THIN), G::ipg(jn), G::ont(jn), ph_pf(jn)>(
+                buf(1, pj) + lane_at, wnet1 + G::woff(j), wt_own, acc_t, a_pre, ph_b_pre, acc_s, buf(0, pj ^ 1) + lane_at + 16 * wave, slope_h,
+                buf(0, pj ^ 1) + lane_at, wnet + G::woff(jn), wave, thin, b_pre, voff, [&] { GNF_STAMP(7 + 4 * j); });
+        });
+        constexpr int po = (K - 1) & 1;  // the output layer reads buf(net, po)
+        phase_flush(acc_t, buf(1, po) + lane_at + 16 * wt_own, slope_h);
+        GNF_STAMP(kTracePhFlushed);
+        phase_barrier();
+        GNF_STAMP(kTracePhFlushed + 1);
+        if (thin_mine) mlp_chunk_thin(buf(thin_net, po), LS, thin, thin, kPhaseTs, bias_o, buf(thin_net, po ^ 1), 1.f, lane, b_pre);
+        __syncthreads();
+        GNF_STAMP(kTracePhFlushed + 2);
+    } else
     epi_static_for<K>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         const float* in_lds = buf(nl, j & 1);
@@ -815,7 +912,7 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
     couple_tile<TM, false, false, false, true>(a, 0, 0, H, LS, buf(0, pp), buf(1, pp), buf(0, pp ^ 1), nullptr, red, tile, row0, tid, wave, lane, own);
     GNF_STAMP(kTraceEnd);
 #ifdef GNF_TRACE
-    static_assert(4 + 2 * K <= kTraceCoupled, "stamp slots");
+    static_assert(4 + 2 * K <= kTraceCoupled && 4 + 4 * (K - 1) <= kTracePhFlushed, "stamp slots");
     if (a.trace && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2) && lane < kTraceSlots)
         a.trace[((blockIdx.x != 0) * (kFusedThreads / 64) + wave) * kTraceSlots + lane] = s_trace[wave][lane];
 #endif
@@ -868,7 +965,9 @@ bool fused_supports_oop(const HalfStep& hs) {
 // (MT, NETS) choice, from measurements on MI355X at L=256, K=5 (profiles/):
 //   (1,2) 16 nodes x both nets : 37.5 us per launch, any tile count <= 256 (one tile per CU); 35.1 us since round 6, and
 //                                30.3 us in its compile-time-geometry instance (k_half_fused_geo: in0 = H = 32, L = 256,
-//                                K = 5, combine = agg - geo_matches below; any forced shape keeps the generic instance)
+//                                K = 5, combine = agg - geo_matches below; any forced shape keeps the generic instance);
+//                                29.9 us as step / 16 since the memory-order change, 29.4 us in the PHASES instance (both
+//                                nets per wave, the barrier inside a phase; force_shape = 13 keeps the one before it)
 //   (2,2) 32 nodes x both nets : 64 us per launch = 32 us per 16 nodes -> wins once there is more than
 //                                one 16-node tile per CU
 //   (*,1) one net per workgroup + k_coupling: never faster at these widths, but its LDS footprint is
@@ -1043,7 +1142,9 @@ bool fused_stash_shape(const GnfMlp* s, const GnfMlp* t, int64_t n) {
 
 // The compile-time-geometry instance (k_half_fused_geo<IN0G, LG, K, HG>) takes a launch only when ALL of this holds; the
 // callers have already settled the rest of the rule (the (1,2) shape, not the large-batch form, no attention front-end):
-//   - no forced shape of any kind: gnf_set_option("force_shape", 12) is how tests and A/B runs reach the generic instance;
+//   - no forced shape: gnf_set_option("force_shape", 12) is how tests and A/B runs reach the generic instance - except
+//     force_shape = 13 (kForceGeoParent; no shape of its own, so choose_shape and choose_big decide as if nothing were
+//     forced), which selects this kernel's one-net-per-wave instance instead of the PHASES one automatic dispatch runs;
 //   - message-passing GNN with combine = agg, no MLP-row stash, no per-row log-det, no batch-norm moments;
 //   - the MLP is exactly in0 = 16 IN0G -> (K - 1) x 16 LG -> H = 16 HG, and its packed copy has the layout the kernel's
 //     constants (GeoLayout) were derived from.
@@ -1052,7 +1153,8 @@ template <int IN0G, int LG, int K, int HG>
 static bool geo_matches(const HalfStep& hs, const FusedArgs& a) {
     using G = GeoLayout<IN0G, LG, K, HG>;
     const GnfMlp* s = hs.s_net;
-    if (opt(OPT_FORCE_SHAPE) || s->attn || hs.mlp_stash || hs.row_logdet || a.bn_part || a.concat || a.h0[0]) return false;
+    const int64_t force = opt(OPT_FORCE_SHAPE);
+    if ((force && force != kForceGeoParent) || s->attn || hs.mlp_stash || hs.row_logdet || a.bn_part || a.concat || a.h0[0]) return false;
     if (a.K != K || a.H != 16 * HG || a.in0 != 16 * IN0G || s->dims[K] != 16 * HG) return false;
     for (int j = 0; j < K; ++j) {
         if (s->dims[j] != 16 * G::ipg(j) || a.ipg[j] != G::ipg(j) || a.ont[j] != G::ont(j) || a.boff[j] != G::boff(j)) return false;
@@ -1061,14 +1163,14 @@ static bool geo_matches(const HalfStep& hs, const FusedArgs& a) {
     return a.bias[0] == a.wp[0][0] + G::kBias && a.bias[1] == a.wp[1][0] + G::kBias && a.LS == G::kLS;
 }
 
-template <int IN0G, int LG, int K, int HG>
+template <int IN0G, int LG, int K, int HG, bool PHASES>
 static int launch_geo(const FusedArgs& a, unsigned tiles, hipStream_t st) {
 #ifdef GNF_TRACE
     constexpr int lds_limit = kLdsLimit - (int)sizeof(unsigned long long) * (kFusedThreads / 64) * kTraceSlots;  // (s_trace is static LDS)
 #else
     constexpr int lds_limit = kLdsLimit;
 #endif
-    GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_fused_geo<IN0G, LG, K, HG>),
+    GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_fused_geo<IN0G, LG, K, HG, PHASES>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit)));
     GeoArgs g{a.rowptr, a.col, a.x_cond, a.x_upd, a.x_upd_src, a.cond_copy, a.partials, a.sq_partials, {a.wp[0][0], a.wp[1][0]},
               a.ld, a.n_nodes, a.n_tiles, a.eps, a.alpha, a.mean, a.act, a.inverse};
@@ -1077,7 +1179,7 @@ static int launch_geo(const FusedArgs& a, unsigned tiles, hipStream_t st) {
     g.trace = g_trace_buf && g_trace_cap > 0 ? g_trace_buf + (size_t)(g_trace_next++ % g_trace_cap) * per_launch : nullptr;
 #endif
     constexpr size_t lds = GeoLayout<IN0G, LG, K, HG>::kLds;
-    hipLaunchKernelGGL((k_half_fused_geo<IN0G, LG, K, HG>), dim3(tiles), dim3(kFusedThreads), lds, st, g);
+    hipLaunchKernelGGL((k_half_fused_geo<IN0G, LG, K, HG, PHASES>), dim3(tiles), dim3(kFusedThreads), lds, st, g);
     GNF_LAUNCH_CHECK("k_half_fused_geo");
     return GNF_OK;
 }
@@ -1244,7 +1346,9 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
                       : launch_shape<1, 2, true>(a, (unsigned)tiles, lds + (size_t)L.mask_words * sizeof(unsigned long long), st);
         } else if (MT == 1 && !fold && geo_matches<2, 16, 5, 2>(hs, a)) {
             // the reference's default MLP (in0 = H = 32, L = 256, K = 5): what a plain benchmark run is sixteen launches of
-            rc = launch_geo<2, 16, 5, 2>(a, (unsigned)tiles, st);
+            // (both nets per wave, a barrier inside each phase; force_shape = kForceGeoParent: a net per wave, a barrier per layer)
+            rc = opt(OPT_FORCE_SHAPE) == kForceGeoParent ? launch_geo<2, 16, 5, 2, false>(a, (unsigned)tiles, st)
+                                                         : launch_geo<2, 16, 5, 2, true>(a, (unsigned)tiles, st);
         } else {
             rc = rowld ? launch_nets2<true>(a, MT, fold, fa, &rla, (unsigned)tiles, lds, front_lds, st)
                        : launch_nets2<false>(a, MT, fold, fa, nullptr, (unsigned)tiles, lds, front_lds, st);

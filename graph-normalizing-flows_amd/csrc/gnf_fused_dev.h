@@ -381,6 +381,150 @@ __device__ __forceinline__ void mlp_chunk(const float* __restrict__ in_lds, int 
 }
 
 
+// ---- phased form of the 16-row chunk (k_half_fused_geo's PHASES instance, gnf_fused.hip) ------------------------------
+// A PHASE is the k-loop of ONE net's layer for the wave's two column tiles {nt0, nt0 + kPhaseTs} - mlp_chunk<1, 2>'s
+// stages, ring and interleave - with three differences:
+//   - the result is not written: it stays in `acc`, and the NEXT phase (the other net's) gets it as `pend` and does the
+//     activation and the LDS store in the shadow of its own first stage's MFMAs, then waits for ITS LDS traffic only
+//     (lgkmcnt, never the weight ring's vmcnt) and meets the other waves in a bare s_barrier - phase_barrier();
+//   - the MFMAs take the WEIGHT fragment as their first operand and the activation fragment as the second (as
+//     k_half_big does): the same products in the same k order, but a lane's four accumulator values are four consecutive
+//     COLUMNS of row lane & 15, so the bias comes as an f32x4 and a tile's store is one ds_write_b128;
+//   - the stages that mlp_chunk's tail spends re-reading its last stage request the next phase's first kPF stages (a_pre /
+//     b_pre hand them over), or the thin chunk's weights: a phase ends without a barrier and without a wait.
+// The next phase's A fragments are requested behind this phase's barrier only (its input is what this phase flushes).
+static constexpr int kPhaseTs = 8;  // tile stride: all 8 waves on one net's layer
+// weight stages in flight ahead of the one being multiplied: a stage is 8 MFMAs here, half of mlp_chunk<1, 4>'s, so twice
+// kPF stages are the same bytes and the same cycles of cover (with kPF = 2 a phase took 9.4 k cycles against 8.2 k of MFMAs)
+static constexpr int kPhasePF = 2 * kPF, kPhaseR = kPhasePF + 1;
+enum { PH_NEXT_HIDDEN = 0, PH_NEXT_THIN = 1 };
+
+__device__ __forceinline__ void phase_barrier() {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// activation + store of a finished phase's two tiles: dst = this lane's four columns of row lane & 15 in the first tile
+__device__ __forceinline__ void phase_flush(const f32x4 (&pend)[2], float* __restrict__ dst, float slope) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float v = pend[b][r];
+            o[r] = fmaxf(v, slope * v);
+        }
+        *reinterpret_cast<f32x4*>(dst + 16 * kPhaseTs * b) = o;
+    }
+}
+
+// PFI stages of this phase arrive in a_pre / b_pre (ring slots 0 .. PFI - 1; stage k lives in slot k % kPhaseR); the first PFO
+// stages of the next phase leave in them (ring slots (IPG + n) % kPhaseR).  Stage kg requests this phase's stage kg + PFI, and
+// next-phase stage n goes out at stage IPG - PFO + n (PFO > IPG - the two-stage layer-0 phase in front of a 16-stage one -
+// spreads them evenly); its A read never in front of the barrier.
+template <int IPG, int ONT, int PFI, bool FLUSH, int NXKIND, int NX_IPG, int NX_ONT, int PFO, class Behind>
+__device__ __forceinline__ void mlp_phase(const float* __restrict__ arow, const float* wbase, int nt0, f32x4 (&acc)[2],
+                                          f32x4 (&a_pre)[kPhasePF], f32x4 (&b_pre)[kPhasePF][2], const f32x4 (&pend)[2],
+                                          float* __restrict__ pend_dst, float slope, const float* __restrict__ nx_arow,
+                                          const float* nx_wbase, int nx_nt0, const WChunk& nx_thin, f32x4 (&b_thin)[kPF][4],
+                                          int voff, Behind&& behind_barrier) {
+    constexpr int R = kPhaseR;
+    static_assert(PFI <= IPG && PFI <= kPhasePF && PFO <= NX_IPG && PFO <= kPhasePF && IPG >= 2, "whole stages, inside the ring");
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), 0, IPG * ONT * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t nrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(nx_wbase), 0, NX_IPG * NX_ONT * 1024, 0x00020000);
+    const int wt[2] = {nt0 * 1024, (nt0 + kPhaseTs) * 1024};
+    const int nwt[2] = {nx_nt0 * 1024, (nx_nt0 + kPhaseTs) * 1024};
+    f32x4 a_ring[R], b_ring[R][2];
+#pragma unroll
+    for (int u = 0; u < PFI; ++u) {
+        a_ring[u] = a_pre[u];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) b_ring[u][b] = b_pre[u][b];
+    }
+    // the first stage behind the barrier: the earliest one that may read the next phase's input
+    constexpr int kFirstNxA = FLUSH ? 1 : 0;
+#pragma unroll
+    for (int kg = 0; kg < IPG; ++kg) {
+        if (kg + PFI < IPG) {
+            const int kn = kg + PFI;
+            a_ring[kn % R] = *reinterpret_cast<const f32x4*>(arow + 16 * kn);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) b_ring[kn % R][b] = GNF_LOAD_B(rsrc, voff, wt[b] + kn * ONT * 1024);
+        }
+        if constexpr (NXKIND == PH_NEXT_HIDDEN) {
+#pragma unroll
+            for (int n = 0; n < PFO; ++n) {
+                const int at = PFO <= IPG ? IPG - PFO + n : n * IPG / PFO;
+                const int at_a = at > kFirstNxA ? at : kFirstNxA;
+                if (at == kg) {
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) b_ring[(IPG + n) % R][b] = GNF_LOAD_B(nrsrc, voff, nwt[b] + n * NX_ONT * 1024);
+                }
+                if (at_a == kg) a_ring[(IPG + n) % R] = *reinterpret_cast<const f32x4*>(nx_arow + 16 * n);
+            }
+        } else {
+            if (kg == IPG - kPF) {  // (where mlp_chunk requests them: one of its rounds in front of the end)
+                prefetch_chunk(nx_thin, kPhaseTs, voff, b_thin, true);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (FLUSH && kg == 0) phase_flush(pend, pend_dst, slope);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+                acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(b_ring[kg % R][b][q], a_ring[kg % R][q], acc[b], 0, 0, 0);
+        // (a group whose instructions this stage does not have stays empty)
+        if (FLUSH && kg == 0) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // this phase's next A fragment
+            __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);  // tile 0: 4 x (mul, canonicalize, max)
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // ds_write_b128
+            __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);  // tile 1
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // (one by one: a group of two comes out in reverse order, so the two accumulator
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  //  chains met back to back; alternating measured the same, and reads as written)
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // (one by one: a group of two comes out in reverse order, so the two accumulator
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  //  chains met back to back; alternating measured the same, and reads as written)
+            __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+        } else {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, kPhasePF, 0);  // the A reads this stage requests
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // (one by one: a group of two comes out in reverse order, so the two accumulator
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  //  chains met back to back; alternating measured the same, and reads as written)
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // (one by one: a group of two comes out in reverse order, so the two accumulator
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  //  chains met back to back; alternating measured the same, and reads as written)
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // (one by one: a group of two comes out in reverse order, so the two accumulator
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  //  chains met back to back; alternating measured the same, and reads as written)
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (FLUSH && kg == 0) {
+            phase_barrier();
+            behind_barrier();
+        }
+    }
+    if constexpr (NXKIND == PH_NEXT_HIDDEN) {
+#pragma unroll
+        for (int n = 0; n < PFO; ++n) {
+            a_pre[n] = a_ring[(IPG + n) % R];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) b_pre[n][b] = b_ring[(IPG + n) % R][b];
+        }
+    }
+}
+
 
 // A tile's rows of one LDS activation buffer ([TM][LS], first `width` columns) to global memory [n_nodes, dld]: coalesced
 // 16-byte-per-lane copy where the widths allow (element-wise stores from the accumulator layout, 64-byte segments, made

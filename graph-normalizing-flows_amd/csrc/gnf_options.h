@@ -16,7 +16,8 @@ namespace gnf {
 enum OptionId {
     OPT_FORCE_SHAPE = 0,     // fused forward workgroup shape <MT><NETS>, e.g. 21; 40 / 30 / 20 / 10: the large-batch kernel with that many
                              // row tiles per workgroup at most; 49: that kernel (cap 4) with the split tiles' hand-over flag withheld -
-                             // fault injection, every split tile takes the lost-partner branch (NaN rows, NaN partial sums); 0 = by batch size
+                             // fault injection, every split tile takes the lost-partner branch (NaN rows, NaN partial sums); 13: as 0, with the
+                             // compile-time-geometry kernel in its one-net-per-wave instance (kForceGeoParent); 0 = by batch size
     OPT_ATTN_KERNEL,         // attention forward: 1 always the rows kernel, 2 always the edge-tiled kernel, 3 always the matrix-core
                              // attention core (each keeps the front-end out of the fused kernel's prologue); 0 = by batch / geometry
     OPT_ATTN_BWD_ROWS,       // attention rows kernels: 64 / 32 (backward also 16 and 3264) rows per workgroup; 0 = by batch size / mean degree
@@ -28,6 +29,9 @@ enum OptionId {
 };
 
 static constexpr int64_t kForceBigLostPartner = 49;
+// force_shape = 13: every choice as with 0, but where the compile-time-geometry half-step kernel takes the launch it is the
+// instance with one net per wave and a barrier per layer (A/B runs and tests against the phased instance, gnf_fused.hip)
+static constexpr int64_t kForceGeoParent = 13;
 extern std::atomic<int64_t> g_options[OPT_COUNT];
 inline int64_t opt(OptionId id) { return g_options[id].load(std::memory_order_relaxed); }
 

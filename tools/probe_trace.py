@@ -5,6 +5,7 @@ directory - the shipped libgnf_hip.so has none of it):
 
     python tools/probe_trace.py --build            # compile build/gnf_trace/libgnf_hip_trace.so (no GPU needed)
     python tools/probe_trace.py [--reps 20]        # run on the GPU box: forward steps of config 2, the table on stdout
+    python tools/probe_trace.py --parent           # the same for the one-net-per-wave instance (force_shape = 13)
     python tools/probe_trace.py --build --src-root <another checkout> --out <dir>, then --lib <dir>/libgnf_hip_trace.so
                                                    # the same table for another state of the sources
 
@@ -12,7 +13,12 @@ With GNF_TRACE every wave of the kernel stamps s_memtime (shader cycles) at: ker
 barrier, behind the gather barrier, when the operands of each layer's first MFMA have landed, behind each layer barrier,
 behind the coupling store and at the kernel's end; the 8 waves of workgroup 0 and of the mid-grid workgroup copy their stamps
 to a buffer of their own.  A phase's figure is the mean over the 8 waves of a workgroup, then the median over launches and
-repetitions.  Stamps cost 7 - 11 % of the kernel: compare stamped runs with stamped runs only."""
+repetitions.  Stamps cost 7 - 11 % of the kernel: compare stamped runs with stamped runs only.
+
+The phased instance (automatic dispatch; phases S0 T0 S1 T1 ..: both nets in every wave) stamps each phase's first MFMA, behind
+each phase's barrier, where the last pending tile's store has been issued, and behind the two closing barriers: phases_phased().
+"Stage 0 + flush -> behind its barrier" includes the time a wave waits for the wave it shares its SIMD with, which is still
+in the previous phase: it is a wave's time, not the matrix pipe's."""
 import argparse
 import ctypes as C
 import glob
@@ -23,6 +29,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SLOTS, WAVES, COUPLED, END = 32, 8, 30, 31
+PH_FLUSHED = 20        # phased instance (kTracePhFlushed, gnf_fused.hip)
+FORCE_GEO_PARENT = 13  # gnf_set_option("force_shape", 13): the one-net-per-wave instance (kForceGeoParent, gnf_options.h)
 
 
 def build(src_root, out):
@@ -55,6 +63,24 @@ def phases(k):
     return names
 
 
+def phases_phased(k):
+    """The phased instance (automatic dispatch): phase p = 2 j + net of S0 T0 S1 T1 ..; slot 4 + 2 p its first MFMA, 5 + 2 p
+    behind its barrier (none in S0), PH_FLUSHED the last pending store issued, then the two closing barriers."""
+    names = [(0, 1, "entry -> barrier 1 (rowptr in LDS)"), (1, 2, "-> col barrier"), (2, 3, "-> gather barrier")]
+    prev = 3
+    for p in range(2 * (k - 1)):
+        tag = f"{'ST'[p & 1]}{p >> 1}"
+        names.append((prev, 4 + 2 * p, f"-> {tag} first MFMA"))
+        prev = 4 + 2 * p
+        if p:
+            names.append((prev, 5 + 2 * p, f"{tag}: stage 0 + flush -> behind its barrier"))
+            prev = 5 + 2 * p
+    names += [(prev, PH_FLUSHED, f"-> T{k - 2} done, its flush issued"), (PH_FLUSHED, PH_FLUSHED + 1, "-> behind the flush barrier"),
+              (PH_FLUSHED + 1, PH_FLUSHED + 2, "thin chunks -> closing barrier"), (PH_FLUSHED + 2, COUPLED, "-> coupling store"),
+              (COUPLED, END, "-> kernel end (reduction)"), (3, PH_FLUSHED + 2, "MLP: gather barrier -> closing barrier"), (0, END, "entry -> kernel end")]
+    return names
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--build", action="store_true")
@@ -63,6 +89,7 @@ def main():
     ap.add_argument("--lib", default=None)
     ap.add_argument("--workload", default="config2")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--parent", action="store_true", help="the one-net-per-wave instance (force_shape = 13) and its table")
     args = ap.parse_args()
     if args.build:
         build(os.path.abspath(args.src_root), os.path.abspath(args.out))
@@ -94,7 +121,10 @@ def main():
     for _ in range(5):   # warm-up, not recorded
         forward_shard_sums(net, graph)
     torch.cuda.synchronize()
-    table = phases(k)
+    _abi.set_option("force_shape", FORCE_GEO_PARENT if args.parent else 0)
+    table = phases(k) if args.parent else phases_phased(k)
+    if args.parent:
+        table.insert(-1, (3, 5 + 2 * (k - 1), "MLP: gather barrier -> last layer barrier"))
     got = {(wg, name): [] for wg in (0, 1) for _, _, name in table}
     for _ in range(args.reps):
         buf.zero_()
@@ -109,6 +139,7 @@ def main():
                 d = (t[:, wg, :, b] - t[:, wg, :, a]).double().mean(dim=1)   # per launch: mean over the 8 waves
                 got[(wg, name)] += d.tolist()
     lib.gnf_trace_set_buffer(None, 0)
+    print(f"# instance: {'one net per wave, a barrier per layer (force_shape = 13)' if args.parent else 'both nets per wave, a barrier inside each phase (automatic dispatch)'}")
     print(f"# k_half_fused_geo phase table, workload {args.workload}: {n_global} nodes, {launches} launches per step, {args.reps} steps; shader cycles")
     print("# (mean over the 8 waves of a workgroup, median / min / max over launches and steps; stamped build)")
     print(f"# {'phase':46s} {'workgroup 0':>26s} {'mid-grid workgroup':>26s}")
