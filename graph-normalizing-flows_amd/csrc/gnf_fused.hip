@@ -118,7 +118,7 @@ namespace gnf {
 
 // Diagnostic build only (-DGNF_TRACE, tools/probe_trace.py; never the shipped library): every wave of the instance stamps
 // the cycle counter (s_memtime) at the phase boundaries into LDS, and the waves of workgroup 0 and of the mid-grid workgroup
-// copy their stamps to a buffer nothing else reads.  Slots: 0 entry, 1 behind barrier 1 (rowptr in LDS), 2 behind the col
+// copy their stamps to a buffer nothing else reads.  Slots: 0 entry, 1 the rowptr slice has landed (the col segment's bounds read out of it; a barrier stood here once), 2 behind the col
 // barrier, 3 behind the gather barrier, 4 + 2 j the operands of layer j's first MFMA have landed (the stamp waits for this
 // wave's stage-0 weights), 5 + 2 j behind layer j's barrier, kTraceCoupled behind the coupling store, kTraceEnd kernel end.
 #ifdef GNF_TRACE
@@ -153,6 +153,26 @@ __device__ __forceinline__ void geo_stamp_after(int slot, float landed) {
 // compile-time-geometry instance (k_half_fused_geo), whose arguments carry no residual, batch-norm or stash fields; it
 // hands in what the epilogue reads (CoupleOwn: TM * H = kFusedThreads there, so one element per thread; no global load and
 // no kernel-argument read here) and has sum(s) and sum(x_new^2) reduced in one pass (red: 16 doubles), same adds, same order.
+// Lane 0's value of the tree  v[i] += v[i + off], off = 32, 16, 8, 4, 2, 1  (the __shfl_down loop: the same pairs added in
+// the same order on every path that reaches lane 0; the other lanes' values are not the loop's) without an LDS round trip
+// per step: the halves of the wave and the rows of a half change places in v_permlane32_swap / v_permlane16_swap (both
+// operands the value itself: the second result holds lanes i + 32 / i + 16 in lanes i < 32 / i < 16), the steps inside a
+// 16-lane row are DPP row shifts of the two 32-bit halves (row_shl:n: lane i reads lane i + n of its row).
+template <class Mv>
+__device__ __forceinline__ double add_moved(double v, Mv&& mv) {
+    const int lo = mv(__double2loint(v)), hi = mv(__double2hiint(v));
+    return v + __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_sum_lane0(double v) {
+    v = add_moved(v, [](int x) { return (int)__builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false)[1]; });
+    v = add_moved(v, [](int x) { return (int)__builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false)[1]; });
+    v = add_moved(v, [](int x) { return __builtin_amdgcn_update_dpp(0, x, 0x108, 0xf, 0xf, true); });
+    v = add_moved(v, [](int x) { return __builtin_amdgcn_update_dpp(0, x, 0x104, 0xf, 0xf, true); });
+    v = add_moved(v, [](int x) { return __builtin_amdgcn_update_dpp(0, x, 0x102, 0xf, 0xf, true); });
+    v = add_moved(v, [](int x) { return __builtin_amdgcn_update_dpp(0, x, 0x101, 0xf, 0xf, true); });
+    return v;
+}
+
 struct CoupleOwn {  // held in vector registers since kernel entry
     float xu = 0.f;              // the old x_upd_src[r, f]
     float* dst = nullptr;        // &x_upd[r, f]; NULL: the row is past n_nodes
@@ -208,29 +228,29 @@ __device__ __forceinline__ void couple_tile(const Args& a, const FArgs& fa, cons
         }
     }
     if constexpr (PLAIN) GNF_STAMP(kTraceCoupled);
-    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
     if constexpr (PLAIN) {  // both sums behind ONE barrier: red[0 .. 7] sum(s), red[8 .. 15] sum(x_new^2), each summed in wave order
         constexpr int NW = kFusedThreads / 64;
         const bool sq = own.sq_part != nullptr;
-        if (sq)
-            for (int off = 32; off > 0; off >>= 1) local2 += __shfl_down(local2, off, 64);
+        local = wave_sum_lane0(local);  // (lane 0's value is the one the __shfl_down loop below leaves there)
+        if (sq) local2 = wave_sum_lane0(local2);
         if (lane == 0) {
             red[wave] = local;
             if (sq) red[NW + wave] = local2;
         }
         __syncthreads();
-        if (tid == 0) {
-            double tot = 0.0;
-            for (int w = 0; w < NW; ++w) tot += red[w];
+        if (tid == 0) {  // (its own wave's sums are still in its registers)
+            double tot = 0.0 + local;
+            for (int w = 1; w < NW; ++w) tot += red[w];
             *own.part = tot;
             if (sq) {
-                double tot2 = 0.0;
-                for (int w = 0; w < NW; ++w) tot2 += red[NW + w];
+                double tot2 = 0.0 + local2;
+                for (int w = 1; w < NW; ++w) tot2 += red[NW + w];
                 *own.sq_part = tot2;
             }
         }
         return;
     }
+    for (int off = 32; off > 0; off >>= 1) local += __shfl_down(local, off, 64);
     if (lane == 0) red[wave] = local;
     __syncthreads();
     if (tid == 0) {
@@ -674,7 +694,17 @@ struct GeoLayout {  // the packed layout (launch_pack_mlp) of this geometry, in 
     static constexpr int kBias = woff(K);                                 // bias block behind the weights
     static constexpr int kLS = 16 * (LG > IN0G ? LG : IN0G) + 4;          // LDS row stride: widest layer + 4 floats
     static constexpr int kRed = 2 * (kFusedThreads / 64);                 // reduction scratch: sum(s) and sum(x_new^2) of every wave
-    static constexpr size_t kLds = (size_t)2 * 2 * 16 * kLS * sizeof(float) + kRed * sizeof(double) + (kRowptrPad + kColCap) * sizeof(int);
+    // the PHASES instance's bias block, behind the col slice: both nets' packed bias blocks as they lie in memory.  With it
+    // kLds is above half of the CU's 160 KB, so a second workgroup can never share the CU, whatever the register count
+    // becomes (at 8 waves of ~148 registers it could not before either) - keep it that way: the prologue counts on the
+    // LDS pipe and the vector-memory queue of the CU being its own.
+    static constexpr int kBiasBlock = boff(K);                            // floats of one net's bias block
+    static constexpr size_t kBiasAt = (size_t)2 * 2 * 16 * kLS * sizeof(float) + kRed * sizeof(double) + (kRowptrPad + kColCap) * sizeof(int);
+    static constexpr size_t kLds = kBiasAt + (size_t)2 * kBiasBlock * sizeof(float);
+    static_assert(kBiasAt % 16 == 0 && kBiasBlock % 4 == 0, "the bias block is written and read in 16-byte pieces");
+    static_assert(2 * (kBiasBlock / 4) <= 2 * kFusedThreads && 2 * (kBiasBlock / 4) - kFusedThreads <= 16,
+                  "one 16-byte piece per thread, and a second one for at most 16 threads");
+    static_assert(kLds > (size_t)kLdsLimit / 2, "one workgroup per CU");
     static_assert(woff(1) == 16 * IN0G * 16 * LG && kBias == 16 * IN0G * 16 * LG + (K - 2) * 256 * LG * LG + 16 * LG * 16 * HG,
                   "sum of Ip x Op over the layers");
     static_assert(kLds <= (size_t)kLdsLimit, "activation buffers in LDS");
@@ -685,13 +715,28 @@ struct GeoLayout {  // the packed layout (launch_pack_mlp) of this geometry, in 
 
 // Memory order of the prologue: what has a known address goes out first - the rowptr slice, then this thread's own
 // x_cond[r, f] and old x_upd_src[r, f] (TM * H = kFusedThreads: one element per thread, held in two registers through the
-// MLP) - and every kernel argument is read once at entry.  Behind barrier 1 the col segment's first kFusedThreads entries are
-// requested BEFORE the layer-0 weights and the biases: vmcnt retires in issue order, so a col entry requested behind them
-// would wait for the launch's first (cold) touch of the weights.  (Its LDS write still comes behind the ISSUE of those 25
-// loads, which holds the wave for ~1.4 k cycles - profiles/r8a_trace_geo.txt; requesting them in front of barrier 1 instead
-// measured slower.)  The weights still have the gather's two round trips to land in, and do: a layer's first operands are
-// there 128 cycles behind its barrier.  Only the order of requests and waits differs from the generic instance; every
-// product and sum is its own.
+// MLP) - and every kernel argument is read once at entry.  EVERY wave loads the rowptr slice and reads the col segment's
+// bounds out of its own registers (v_readlane of lanes 0 and TM: wave-uniform), so no barrier and no LDS hop stand in front
+// of the second dependent round trip; wave 0 still writes s_rowptr[0 .. TM] for tile_gather, which reads it behind the col
+// barrier.  The col segment's first kFusedThreads entries are requested BEFORE the layer-0 weights (and, one net per wave,
+// the biases): vmcnt retires in issue order, so a col entry requested behind them would wait for the launch's first (cold)
+// touch of the weights.  (One net per wave, its LDS write still comes behind the ISSUE of those 25 loads, which holds the
+// wave for ~1.4 k cycles - profiles/r8a_trace_geo.txt; requesting them at entry instead measured slower.)  The weights still
+// have the gather's two round trips to land in, and do: a layer's first operands are there 128 cycles behind its barrier.
+// Only the order of requests and waits differs from the generic instance; every product and sum is its own.
+// Synchronisation of the prologue: the col barrier orders s_rowptr, s_col and (PHASES) the bias block, all written in front
+// of it by the threads that loaded them, against tile_gather's and the bias reads behind it; the gather barrier orders the
+// layer-0 input.  Nothing in LDS is read in front of the col barrier any more.
+//
+// PHASES, the biases: the two nets' bias blocks (2 x 1 056 floats, 8.4 KB) are requested at entry, one 16-byte piece per
+// thread, written to the LDS block behind the col slice in front of the col barrier, and read from there - ph_bias and
+// bias_o, the same four columns per lane as from memory - right behind that barrier, in front of the gather.
+// 10 vector-memory instructions per wave between entry and the col barrier instead of 25 (136 of a workgroup's were bias
+// loads of four distinct addresses each), and the col entry's LDS write no longer stands behind their issue.
+// tile_gather's round loop still opens with s_waitcnt vmcnt(1): the waits of its global-col path (segments above kColCap)
+// are merged into the head of the LDS-col loop, because the path is chosen by a value read from LDS, which the compiler
+// cannot know to be uniform.  On first entry that waits for three of the four weight loads above.  Removing it needs
+// tile_gather's text changed (a uniform `staged`), for every caller; it stays.
 //
 // PHASES instance (what automatic dispatch runs; force_shape = kForceGeoParent keeps the one above): both nets in every wave.
 // Wave w owns column tiles {w, w + 8} of each hidden layer of the s-net and {w', w' + 8}, w' = (w + 6) % 8, of the t-net,
@@ -720,11 +765,12 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
     constexpr int TM = 16, WPN = G::kWpn, LS = G::kLS, H = 16 * HG, IN0 = 16 * IN0G;
     static_assert(TM * H == kFusedThreads && IN0 == H, "one own-row element per thread, the same one in the gather and in the coupling");
     GNF_STAMP(0);
-    // [net][pingpong][TM][LS] | reduction scratch | rowptr slice | col slice
+    // [net][pingpong][TM][LS] | reduction scratch | rowptr slice | col slice | [net] bias block (PHASES)
     auto buf = [&](int net_, int pp_) -> float* { return smem + (2 * net_ + pp_) * TM * LS; };
     double* red = reinterpret_cast<double*>(smem + 2 * 2 * TM * LS);
     int* s_rowptr = reinterpret_cast<int*>(red + G::kRed);
     int* s_col = s_rowptr + kRowptrPad;
+    [[maybe_unused]] float* s_bias = smem + G::kBiasAt / sizeof(float);
 
     const int tid = threadIdx.x;
     // (wave ids, the second net's rotated column-tile ownership: as in k_half_fused)
@@ -752,9 +798,10 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
     const int tile = nets2_tile(blockIdx.x, a.n_tiles);
     const int row0 = tile * TM;
 
-    // ---- loads with known addresses: the rowptr slice first (barrier 1 waits for it alone), then the thread's own row ----
-    // (unconditional, clamped addresses: a load inside a branch made the wait in front of barrier 1 a vmcnt(0))
-    const int rp_row = row0 + (tid < TM ? tid : TM);
+    // ---- loads with known addresses: the rowptr slice first (the col request waits for it alone), then the thread's own row ----
+    // (unconditional, clamped addresses: a load inside a branch made the wait for the rowptr slice a vmcnt(0))
+    // EVERY wave loads the slice (lane l: rowptr[row0 + min(l, TM)]), so each has the segment's bounds in its own registers
+    const int rp_row = row0 + (lane < TM ? lane : TM);
     const int rp_reg = a.rowptr[rp_row < a.n_nodes ? rp_row : a.n_nodes];
     CoupleOwn own;
     float xc_own;
@@ -768,6 +815,17 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
         own.part = hold_v(a.partials + tile);
         own.sq_part = hold_v(a.sq_partials ? a.sq_partials + tile : nullptr);
         own.inverse = hold_v(a.inverse);
+    }
+    // PHASES: the two nets' bias blocks (2 x G::kBiasBlock floats, addresses known from the arguments) go through LDS: one
+    // 16-byte piece per thread, 2 * NPC of them, and the 2 * NPC - kFusedThreads left over once more in every wave (the
+    // same 16 addresses in each - unconditional, as the loads above; the first wave's lanes 0 .. 15 write them)
+    [[maybe_unused]] constexpr int NPC = G::kBiasBlock / 4;
+    [[maybe_unused]] f32x4 bias_pc, bias_pc2;
+    [[maybe_unused]] const int bias_at2 = kFusedThreads + (lane & 15);
+    static_assert(kFusedThreads >= NPC && kFusedThreads + 15 < 2 * NPC, "pieces past kFusedThreads are the second net's");
+    if constexpr (PHASES) {
+        bias_pc = *reinterpret_cast<const f32x4*>((tid < NPC ? wnet : wnet1) + G::kBias + 4 * (tid < NPC ? tid : tid - NPC));
+        bias_pc2 = *reinterpret_cast<const f32x4*>(wnet1 + G::kBias + 4 * (bias_at2 - NPC));
     }
     __builtin_amdgcn_sched_barrier(0);
 
@@ -787,14 +845,16 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
     };
     const bool last_mine = wl < HG;  // (wave-uniform) the output layer has HG tiles for WPN waves
 
+    // ---- the segment's bounds from this wave's own registers (lanes 0 and TM: wave-uniform values in scalar registers), no
+    // barrier and no LDS hop in front of the col request; s_rowptr is for tile_gather, and the col barrier publishes it ----
     if (tid <= TM) s_rowptr[tid] = rp_reg;
-    __syncthreads();  // barrier 1
+    const int seg_beg = __builtin_amdgcn_readlane(rp_reg, 0);
+    const int seg_len = __builtin_amdgcn_readlane(rp_reg, TM) - seg_beg;
     GNF_STAMP(1);
 
-    // ---- the col segment's first kFusedThreads entries into a register, THEN the first chunk's weights and this wave's
-    // biases (one float per lane and column tile, K - 1 layers x 4 tiles + the output layer's), then the LDS write ----
-    const int seg_beg = s_rowptr[0];
-    const int seg_len = s_rowptr[TM] - seg_beg;
+    // ---- the col segment's first kFusedThreads entries into a register, THEN the first chunk's weights (one net per wave:
+    // and this wave's biases, one float per lane and column tile, K - 1 layers x 4 tiles + the output layer's), then the
+    // LDS writes: the bias piece (PHASES; requested at entry, long landed) and the col entry ----
     const bool staged = seg_len <= kColCap;  // workgroup-uniform (tile_gather has the same rule)
     int col_reg = 0;
     if (staged && tid < seg_len) col_reg = a.col[seg_beg + tid];
@@ -817,15 +877,6 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
         for (int u = 0; u < ph_pf(0); ++u)
 #pragma unroll
             for (int b = 0; b < 2; ++b) ph_b_pre[u][b] = GNF_LOAD_B(rs0, voff, (u * G::ont(0) + wave + kPhaseTs * b) * 1024);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const float* bq = (q ? wnet1 : wnet) + G::kBias + 16 * (q ? wt_own : wave) + 4 * (lane >> 4);
-#pragma unroll
-            for (int j = 0; j < K - 1; ++j)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) ph_bias[q][j][b] = *reinterpret_cast<const f32x4*>(bq + G::boff(j) + 16 * kPhaseTs * b);
-        }
-        bias_o.v[0] = (thin_net ? wnet1 : wnet)[G::kBias + G::boff(K - 1) + 16 * thin_tile + (lane & 15)];
     } else {
     prefetch_chunk(chunk(std::integral_constant<int, 0>{}), WPN, voff, b_pre, true);
     const float* bnet = wnet + G::kBias + 16 * wl + (lane & 15);
@@ -836,12 +887,31 @@ __global__ __launch_bounds__(kFusedThreads) void k_half_fused_geo(const GeoArgs 
     bias_o.v[0] = bnet[G::boff(K - 1) - (last_mine ? 0 : 16 * wl)];  // (a wave without a tile reads tile 0's: in bounds)
     }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PHASES) {
+        *reinterpret_cast<f32x4*>(s_bias + 4 * tid) = bias_pc;
+        if (tid < 2 * NPC - kFusedThreads) *reinterpret_cast<f32x4*>(s_bias + 4 * bias_at2) = bias_pc2;
+    }
     if (staged) {
         if (tid < seg_len) s_col[tid] = col_reg;
         for (int i = tid + kFusedThreads; i < seg_len; i += kFusedThreads) s_col[i] = a.col[seg_beg + i];
     }
     __syncthreads();
     GNF_STAMP(2);
+    // PHASES: the biases out of the LDS block, IN FRONT of the gather: its round loop opens with a wait for the weight loads
+    // (header comment), and the 17 reads return in that wait's shadow.  Behind the gather's last request, in front of the
+    // gather barrier, they stood on the critical path: 4.5 us a step slower (profiles/prologue_ab.txt).
+    if constexpr (PHASES) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const float* bq = s_bias + q * G::kBiasBlock + 16 * (q ? wt_own : wave) + 4 * (lane >> 4);
+#pragma unroll
+            for (int j = 0; j < K - 1; ++j)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) ph_bias[q][j][b] = *reinterpret_cast<const f32x4*>(bq + G::boff(j) + 16 * kPhaseTs * b);
+        }
+        bias_o.v[0] = s_bias[thin_net * G::kBiasBlock + G::boff(K - 1) + 16 * thin_tile + (lane & 15)];
+    }
     const TileAgg ta{a.col, a.x_cond, a.ld, a.n_nodes, row0, H, IN0, IN0, a.mean, 0, a.eps, a.cond_copy};
     tile_gather<TM, kFusedThreads, kColCap>(ta, s_rowptr, s_col, buf(0, 0), buf(1, 0), LS, nullptr, tid, OwnRow{xc_own});
     __syncthreads();
@@ -967,7 +1037,8 @@ bool fused_supports_oop(const HalfStep& hs) {
 //                                30.3 us in its compile-time-geometry instance (k_half_fused_geo: in0 = H = 32, L = 256,
 //                                K = 5, combine = agg - geo_matches below; any forced shape keeps the generic instance);
 //                                29.9 us as step / 16 since the memory-order change, 29.4 us in the PHASES instance (both
-//                                nets per wave, the barrier inside a phase; force_shape = 13 keeps the one before it)
+//                                nets per wave, the barrier inside a phase; force_shape = 13 keeps the one before it),
+//                                28.6 us with its biases through LDS, no rowptr barrier and the register-level sums
 //   (2,2) 32 nodes x both nets : 64 us per launch = 32 us per 16 nodes -> wins once there is more than
 //                                one 16-node tile per CU
 //   (*,1) one net per workgroup + k_coupling: never faster at these widths, but its LDS footprint is
