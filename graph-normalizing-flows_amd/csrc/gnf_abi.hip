@@ -204,7 +204,7 @@ int validate_flow_call(const GnfCsr* csr, const GnfFlow* flow, int64_t ld, int32
     }
     const int H = D / 2;
     const int T = flow->num_timesteps;
-    const int n_nets = flow->weight_sharing ? 2 : 2 * T;
+    const int n_nets = flow_net_count(flow);
     for (int q = 0; q < n_nets; ++q) {
         rc = validate_pair(&flow->s_nets[q], &flow->t_nets[q], &flow->gnn, H);
         if (rc) return rc;
@@ -427,7 +427,7 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
     }
     const int H = D / 2;
     const int T = flow->num_timesteps;
-    const int n_nets = flow->weight_sharing ? 2 : 2 * T;
+    const int n_nets = flow_net_count(flow);
     if (direction == GNF_FORWARD && !sums) {
         set_error("gnf_grevnet_f32: FORWARD needs a device sums[2] buffer");
         return GNF_EINVAL;

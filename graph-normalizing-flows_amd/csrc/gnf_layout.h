@@ -21,6 +21,8 @@ inline int hidden_max(const GnfMlp* s, const GnfMlp* t) { return hidden_max(s) >
 inline const GnfMlp* flow_net(const GnfFlow* f, const GnfMlp* nets, int half, int i) {
     return f->weight_sharing ? &nets[half] : &nets[half * f->num_timesteps + i];
 }
+// nets in each of GnfFlow.s_nets / t_nets
+inline int flow_net_count(const GnfFlow* f) { return f->weight_sharing ? 2 : 2 * f->num_timesteps; }
 
 // ---- half-step float scratch -------------------------------------------------------------------------------------
 // h0 [n, in0] | per net: A [n, lmax] | B [n, lmax] (ping-pong activations of the layered path, two nets side by side for

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void k_pack_multi(const PackBatch pb) {
 static inline int pad16i(int v) { return (v + 15) & ~15; }
 
 static int pack_flow(const GnfFlow* flow, hipStream_t st) {
-    const int n_nets = flow->weight_sharing ? 2 : 2 * flow->num_timesteps;
+    const int n_nets = flow_net_count(flow);
     PackBatch pb;
     int cnt = 0;
     int64_t maxtot = 0;
@@ -261,7 +261,7 @@ int gnf_pack_flow(const GnfFlow* flow, gnf_stream_t stream) {
         set_error("gnf_pack_flow: null flow / nets");
         return GNF_EINVAL;
     }
-    const int n_nets = flow->weight_sharing ? 2 : 2 * flow->num_timesteps;
+    const int n_nets = flow_net_count(flow);
     for (int q = 0; q < n_nets; ++q) {
         int rc = validate_mlp(&flow->s_nets[q], "gnf_pack_flow s_net");
         if (rc) return rc;

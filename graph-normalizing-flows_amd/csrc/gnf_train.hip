@@ -1720,7 +1720,7 @@ static int launch_half_bwd_dw(const BwdArgs* bwd, int64_t bwd_tiles, size_t bwd_
 static bool merged_walk_ok(const GnfFlow* flow, int64_t n, int64_t* tiles_out, size_t* lds_out) {
     if (opt(OPT_BWD_GENERIC) || opt(OPT_DW_GROUPED)) return false;
     if (flow->s_nets[0].attn && 2 * (flow->s_nets[0].num_layers + 4) > kMergedGroup) return false;
-    const int n_nets = flow->weight_sharing ? 2 : 2 * flow->num_timesteps;
+    const int n_nets = flow_net_count(flow);
     for (int q = 0; q < n_nets; ++q)
         if (!fused_bwd_supported(&flow->s_nets[q], &flow->t_nets[q])) return false;
     int64_t tiles;
@@ -1739,7 +1739,7 @@ static bool merged_walk_ok(const GnfFlow* flow, int64_t n, int64_t* tiles_out, s
 // (1.8 GB for the data driver's defaults on a 2 718-node batch), bounded at 48 GB.
 bool layered_stash_mode(const GnfFlow* flow, int64_t n, int32_t H) {
     if (n <= 0 || !flow->s_nets || !flow->t_nets || flow->num_timesteps < 1) return false;
-    const int n_nets = flow->weight_sharing ? 2 : 2 * flow->num_timesteps;
+    const int n_nets = flow_net_count(flow);
     for (int q = 0; q < n_nets; ++q) {
         const GnfMlp *s = &flow->s_nets[q], *t = &flow->t_nets[q];
         if (s->num_layers != t->num_layers || s->num_layers < 2) return false;
@@ -1755,7 +1755,7 @@ bool layered_stash_mode(const GnfFlow* flow, int64_t n, int32_t H) {
 bool mlp_stash_supported(const GnfFlow* flow, int64_t n, int32_t H) {
     if (layered_stash_mode(flow, n, H)) return true;
     if (opt(OPT_BWD_GENERIC) || n <= 0 || !flow->s_nets || !flow->t_nets) return false;
-    const int n_nets = flow->weight_sharing ? 2 : 2 * flow->num_timesteps;
+    const int n_nets = flow_net_count(flow);
     for (int q = 0; q < n_nets; ++q)
         if (!fused_stash_shape(&flow->s_nets[q], &flow->t_nets[q], n) || !fused_bwd_supported(&flow->s_nets[q], &flow->t_nets[q]))
             return false;
@@ -2059,16 +2059,10 @@ int launch_weight_grad_one(const float* h, int64_t ldh, const float* dy, int64_t
 
 using namespace gnf;
 
-extern "C" {
+// ---- the backward walk ------------------------------------------------------------------------------
 
-size_t gnf_backward_workspace_bytes(int64_t n_nodes, int32_t D, const GnfFlow* flow) {
-    if (n_nodes < 0 || D < 2 || (D & 1) || !flow || !flow->s_nets) return 0;
-    return plan_backward(n_nodes, D, &flow->s_nets[0], kBwdSetsDefault, flow->weight_sharing ? 2 : 2 * flow->num_timesteps).total * sizeof(float);
-}
-
-int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFlow* flow, const GnfFlow* grad,
-                             float* z, int64_t ld, int32_t D, void* ws, size_t ws_bytes, gnf_stream_t stream,
-                             gnf_stream_t aux_stream) {
+static int validate_backward_call(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFlow* flow, const GnfFlow* grad, int64_t ld,
+                                  int32_t D) {
     int rc = validate_flow_call(csr, flow, ld, D, "gnf_grevnet_backward_f32");
     if (rc) return rc;
     if (!csr_t || csr_t->n_nodes != csr->n_nodes || csr_t->n_edges != csr->n_edges ||
@@ -2082,7 +2076,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
         return GNF_EINVAL;
     }
     const int T = flow->num_timesteps;
-    const int n_nets = flow->weight_sharing ? 2 : 2 * T;
+    const int n_nets = flow_net_count(flow);
     for (int q = 0; q < n_nets; ++q) {
         const GnfMlp* pairs[2][2] = {{&flow->s_nets[q], &grad->s_nets[q]}, {&flow->t_nets[q], &grad->t_nets[q]}};
         for (auto& pr : pairs) {
@@ -2122,17 +2116,113 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
             }
         }
     }
+    return GNF_OK;
+}
+
+// an empty batch has zero gradient
+static int zero_gradients(const GnfFlow* flow, const GnfFlow* grad, int H, hipStream_t st) {
+    const int n_nets = flow_net_count(flow);
+    for (int q = 0; q < n_nets; ++q)
+        for (int kind = 0; kind < 2; ++kind) {
+            const GnfMlp* gm = kind ? &grad->t_nets[q] : &grad->s_nets[q];
+            for (int j = 0; j < gm->num_layers; ++j) {
+                GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->W[j]), 0, sizeof(float) * gm->dims[j] * gm->dims[j + 1], st));
+                GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->b[j]), 0, sizeof(float) * gm->dims[j + 1], st));
+            }
+            if (gm->attn) {
+                const GnfAttn* fa = (kind ? &flow->t_nets[q] : &flow->s_nets[q])->attn;
+                const size_t nq = (size_t)fa->num_heads * fa->kq_dim;
+                GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wq), 0, sizeof(float) * H * nq, st));
+                GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wk), 0, sizeof(float) * H * nq, st));
+                const size_t wv_cols = (size_t)(attn_is_graph(fa) ? fa->num_heads : 1) * fa->v_dim;   // (graph scope: per head)
+                GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wv), 0, sizeof(float) * H * wv_cols, st));
+                if (fa->Wo)   // (a graph-scope block may have no output projection)
+                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wo), 0,
+                                               sizeof(float) * fa->num_heads * fa->v_dim * fa->out_dim, st));
+                if (fa->layer_norm) {
+                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->ln_gamma), 0, sizeof(float) * H, st));
+                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->ln_beta), 0, sizeof(float) * H, st));
+                }
+            }
+        }
+    if (flow->bns)
+        for (int q = 0; q < 2 * flow->num_timesteps; ++q) {
+            GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(grad->bns[q].gamma), 0, sizeof(float) * H, st));
+            GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(grad->bns[q].beta), 0, sizeof(float) * H, st));
+        }
+    return GNF_OK;
+}
+
+// The fork / join events of the weight-gradient stream live in a per-host-thread, per-device cache (created at a thread's
+// first call on a device, released when the thread ends): no create / destroy per training step, nothing shared between
+// threads or devices, and no event destroyed while work recorded on it is still pending or being captured.
+struct EventCache {
+    hipEvent_t ev[64][kBwdMaxSets + 2] = {};
+    ~EventCache() {
+        for (auto& dev_ev : ev)
+            for (hipEvent_t e : dev_ev)
+                if (e) (void)hipEventDestroy(e);
+    }
+};
+// whatever path leaves the entry after the auxiliary stream was given work, the caller's stream is ordered
+// behind it (an early error return used to leave the fork unjoined: fatal inside a stream capture)
+struct AuxJoin {
+    hipStream_t aux, st;
+    hipEvent_t ev;
+    bool armed = false;
+    ~AuxJoin() {
+        if (armed && aux && ev && hipEventRecord(ev, aux) == hipSuccess) (void)hipStreamWaitEvent(st, ev, 0);
+    }
+};
+
+// Everything one half-step (timestep i, half) reads, decided once (resolve_half): the routes consume it and write none of it.
+struct HalfOps {
+    int step, set;    // position in the walk, operand set
+    int co, uo;       // column of the conditioning half / of the half this half-step updates
+    bool last, acc, attn, fused, front_stashed;
+    const GnfMlp *nets[2], *grads[2];
+    float* x_cond;    // z + co
+    BwdOperands o;    // the set's buffers, with the forward's stash slots in place of what they make unnecessary
+    const float* st_in[2] = {nullptr, nullptr};         // s, t and the act' ballots of the MLP-row stash
+    const unsigned long long* mask_in = nullptr;
+    const float* wot[2] = {nullptr, nullptr};           // the nets' Wo^T / [Wq | Wk | Wv]^T (k_pack_wot)
+    const float* wct[2] = {nullptr, nullptr};
+    const GnfBatchNorm *bn = nullptr, *gbn = nullptr;   // the bijector in front of this half-step (gnn.py:310-313, 325-328)
+};
+
+struct TileLaunch {   // build_bwd_args' results
+    BwdArgs ba;
+    int mt;
+    int64_t tiles;
+    size_t lds;
+    bool have_dagg = false;
+};
+
+extern "C" {
+
+size_t gnf_backward_workspace_bytes(int64_t n_nodes, int32_t D, const GnfFlow* flow) {
+    if (n_nodes < 0 || D < 2 || (D & 1) || !flow || !flow->s_nets) return 0;
+    return plan_backward(n_nodes, D, &flow->s_nets[0], kBwdSetsDefault, flow_net_count(flow)).total * sizeof(float);
+}
+
+// Validate, plan, then 2 T half-steps in reverse: resolve_half decides what the half-step reads, half_merged or
+// half_streams (one route per call) issues its launches.  The routes are local functions over this call's plan.
+int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFlow* flow, const GnfFlow* grad,
+                             float* z, int64_t ld, int32_t D, void* ws, size_t ws_bytes, gnf_stream_t stream,
+                             gnf_stream_t aux_stream) {
+    int rc = validate_backward_call(csr, csr_t, flow, grad, ld, D);
+    if (rc) return rc;
+    const int T = flow->num_timesteps, H = D / 2;
+    const int n_nets = flow_net_count(flow);
     const int64_t n = csr->n_nodes;
     hipStream_t st = (hipStream_t)stream;
     if (n_nets == 0) return GNF_OK;
-    const int n_nets_each = flow->weight_sharing ? 2 : 2 * flow->num_timesteps;
-    const BwdPlan p = plan_backward(n, D, &flow->s_nets[0], kBwdSetsDefault, n_nets_each);
+    const BwdPlan p = plan_backward(n, D, &flow->s_nets[0], kBwdSetsDefault, n_nets);
     if (n > 0 && (!z || !ws || ws_bytes < p.total * sizeof(float))) {
         set_error("gnf_grevnet_backward_f32: workspace %zu < %zu bytes (or null z/ws)", ws_bytes,
                   p.total * sizeof(float));
         return GNF_EWORKSPACE;
     }
-    const int H = D / 2;
     const size_t stash_slot = attn_stash_slot_floats(flow, n);
     const AttnRegion R = attn_region(flow->s_nets[0].attn, n, p.in0);   // (a slot's layout, as the plan: net 0's)
     if (flow->attn_stash && stash_slot > 0 && flow->attn_stash_bytes < (size_t)2 * T * stash_slot * sizeof(float)) {
@@ -2140,37 +2230,7 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
                   (size_t)2 * T * stash_slot * sizeof(float));
         return GNF_EWORKSPACE;
     }
-    if (n == 0) {  // an empty batch has zero gradient
-        for (int q = 0; q < n_nets; ++q)
-            for (int kind = 0; kind < 2; ++kind) {
-                const GnfMlp* gm = kind ? &grad->t_nets[q] : &grad->s_nets[q];
-                for (int j = 0; j < gm->num_layers; ++j) {
-                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->W[j]), 0, sizeof(float) * gm->dims[j] * gm->dims[j + 1], st));
-                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->b[j]), 0, sizeof(float) * gm->dims[j + 1], st));
-                }
-                if (gm->attn) {
-                    const GnfAttn* fa = (kind ? &flow->t_nets[q] : &flow->s_nets[q])->attn;
-                    const size_t nq = (size_t)fa->num_heads * fa->kq_dim;
-                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wq), 0, sizeof(float) * H * nq, st));
-                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wk), 0, sizeof(float) * H * nq, st));
-                    const size_t wv_cols = (size_t)(attn_is_graph(fa) ? fa->num_heads : 1) * fa->v_dim;   // (graph scope: per head)
-                    GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wv), 0, sizeof(float) * H * wv_cols, st));
-                    if (fa->Wo)   // (a graph-scope block may have no output projection)
-                        GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->Wo), 0,
-                                                   sizeof(float) * fa->num_heads * fa->v_dim * fa->out_dim, st));
-                    if (fa->layer_norm) {
-                        GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->ln_gamma), 0, sizeof(float) * H, st));
-                        GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(gm->attn->ln_beta), 0, sizeof(float) * H, st));
-                    }
-                }
-            }
-        if (flow->bns)
-            for (int q = 0; q < 2 * T; ++q) {
-                GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(grad->bns[q].gamma), 0, sizeof(float) * H, st));
-                GNF_HIP_TRY(hipMemsetAsync(const_cast<float*>(grad->bns[q].beta), 0, sizeof(float) * H, st));
-            }
-        return GNF_OK;
-    }
+    if (n == 0) return zero_gradients(flow, grad, H, st);
     float* wsf = (float*)ws;
     float* g = wsf + p.g;
     {
@@ -2181,68 +2241,49 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
                            mean ? csr->rowptr : nullptr, mean ? wsf + p.invdeg : nullptr);
         GNF_LAUNCH_CHECK("k_copy_rows");
     }
-    // fork / join events of the weight-gradient stream: flag-only events owned by THIS call (created on the current
-    // device, destroyed when the call returns - hipEventDestroy defers the release until the recorded work has
-    // completed), so concurrent callers, other devices and stream capture never share one.  ev[0]: "this half-step's
-    // operands are ready" (recorded on the main stream, waited for by the auxiliary one); ev[1 + set]: "the dW launch
-    // that read operand set `set` is done" - needed before a set is refilled (flows with more half-steps than sets) and,
-    // for the last launch, as the final join.
-    hipStream_t aux = (hipStream_t)aux_stream;
-    if (aux == st) aux = nullptr;
     // small message-passing batches: one launch per half-step carries the backward kernel, the previous half-step's dW
     // GEMMs and the reduce of the one before (k_half_bwd_dw) - no second stream
-    bool merged = false;
-    int64_t m_tiles = 0;
     size_t m_lds = 0;
-    if (p.slab_sets == 2) merged = merged_walk_ok(flow, n, &m_tiles, &m_lds);
+    const bool merged = p.slab_sets == 2 && merged_walk_ok(flow, n, nullptr, &m_lds);
     // the training forward left every half-step's MLP rows in GnfFlow.mlp_stash: no recompute (ABI v8)
-    const bool mstashed = flow->mlp_stash != nullptr && mlp_stash_supported(flow, n, D / 2);
-    const MlpStashLayout msl = mstashed ? mlp_stash_layout(&flow->s_nets[0], n, D / 2) : MlpStashLayout{};
-    const bool layered = mstashed && layered_stash_mode(flow, n, D / 2);
+    const bool mstashed = flow->mlp_stash != nullptr && mlp_stash_supported(flow, n, H);
+    const MlpStashLayout msl = mstashed ? mlp_stash_layout(&flow->s_nets[0], n, H) : MlpStashLayout{};
+    const bool layered = mstashed && layered_stash_mode(flow, n, H);
     if (mstashed && flow->mlp_stash_bytes < (size_t)2 * T * msl.slot * sizeof(float)) {
         set_error("gnf_grevnet_backward_f32: mlp_stash %zu < %zu bytes", flow->mlp_stash_bytes,
                   (size_t)2 * T * msl.slot * sizeof(float));
         return GNF_EWORKSPACE;
     }
-    if (merged) aux = nullptr;
+    const hipStream_t aux = (hipStream_t)aux_stream == st || merged ? nullptr : (hipStream_t)aux_stream;
     // attention nets: Wo of every net as transposed fragments, once per call (k_pack_wot) - the tile
     // kernel then forms dagg = dnew Wo^T itself (its last table row) and the GEMM launch in front of the edge kernels
     // goes (7.7 us per half-step on the config-2 batch).
-    bool wot_packed = false;
-    if (flow->s_nets[0].attn && !attn_is_graph(flow->s_nets[0].attn)) {   // (edge scope only: the graph scope's dagg is a GEMM)
-        for (int k0 = 0; k0 < n_nets_each; k0 += 32) {  // (64 pointers per array in the kernel's arguments: 32 nets of each kind a launch)
-            const int cnt = n_nets_each - k0 < 32 ? n_nets_each - k0 : 32;
-            PackWot pw;
-            memset(&pw, 0, sizeof(pw));
-            for (int k = 0; k < cnt; ++k) {
-                for (int q = 0; q < 2; ++q) {
-                    const GnfAttn* at = q ? flow->t_nets[k0 + k].attn : flow->s_nets[k0 + k].attn;
-                    const int slot = q * cnt + k, ix = q * n_nets_each + k0 + k;
-                    pw.wo[slot] = at->Wo, pw.wq[slot] = at->Wq, pw.wk[slot] = at->Wk, pw.wv[slot] = at->Wv;
-                    pw.out[slot] = wsf + p.wot + (size_t)ix * p.wot_each;
-                    pw.out_ct[slot] = wsf + p.wct + (size_t)ix * p.wct_each;
-                }
+    const bool wot_packed = flow->s_nets[0].attn && !attn_is_graph(flow->s_nets[0].attn);   // (edge scope only: the graph scope's dagg is a GEMM)
+    for (int k0 = 0; wot_packed && k0 < n_nets; k0 += 32) {  // (64 pointers per array in the kernel's arguments: 32 nets of each kind a launch)
+        const int cnt = n_nets - k0 < 32 ? n_nets - k0 : 32;
+        PackWot pw;
+        memset(&pw, 0, sizeof(pw));
+        for (int k = 0; k < cnt; ++k) {
+            for (int q = 0; q < 2; ++q) {
+                const GnfAttn* at = q ? flow->t_nets[k0 + k].attn : flow->s_nets[k0 + k].attn;
+                const int slot = q * cnt + k, ix = q * n_nets + k0 + k;
+                pw.wo[slot] = at->Wo, pw.wq[slot] = at->Wq, pw.wk[slot] = at->Wk, pw.wv[slot] = at->Wv;
+                pw.out[slot] = wsf + p.wot + (size_t)ix * p.wot_each;
+                pw.out_ct[slot] = wsf + p.wct + (size_t)ix * p.wct_each;
             }
-            pw.NV = p.NV, pw.C = p.C, pw.NVp = (p.NV + 15) & ~15, pw.Cp = (p.C + 15) & ~15;
-            pw.H = p.H, pw.nq = p.nh * p.kq, pw.vd = p.vd, pw.Pp = (p.P + 15) & ~15, pw.Hp = (p.H + 15) & ~15;
-            const int pack_elems = pw.NVp * pw.Cp > pw.Pp * pw.Hp ? pw.NVp * pw.Cp : pw.Pp * pw.Hp;
-            hipLaunchKernelGGL(k_pack_wot, dim3((unsigned)((pack_elems + 255) / 256), (unsigned)(2 * cnt)), dim3(256), 0, st, pw);
-            GNF_LAUNCH_CHECK("k_pack_wot");
         }
-        wot_packed = true;
+        pw.NV = p.NV, pw.C = p.C, pw.NVp = (p.NV + 15) & ~15, pw.Cp = (p.C + 15) & ~15;
+        pw.H = p.H, pw.nq = p.nh * p.kq, pw.vd = p.vd, pw.Pp = (p.P + 15) & ~15, pw.Hp = (p.H + 15) & ~15;
+        const int pack_elems = pw.NVp * pw.Cp > pw.Pp * pw.Hp ? pw.NVp * pw.Cp : pw.Pp * pw.Hp;
+        hipLaunchKernelGGL(k_pack_wot, dim3((unsigned)((pack_elems + 255) / 256), (unsigned)(2 * cnt)), dim3(256), 0, st, pw);
+        GNF_LAUNCH_CHECK("k_pack_wot");
     }
     const bool reuse_sets = 2 * T > p.n_sets;
-    // The events live in a per-host-thread, per-device cache (created at a thread's first call on a device, released
-    // when the thread ends): no create / destroy per training step, nothing shared between threads or devices, and no
-    // event destroyed while work recorded on it is still pending or being captured.
-    struct EventCache {
-        hipEvent_t ev[64][kBwdMaxSets + 2] = {};
-        ~EventCache() {
-            for (auto& dev_ev : ev)
-                for (hipEvent_t e : dev_ev)
-                    if (e) (void)hipEventDestroy(e);
-        }
-    };
+    // fork / join events of the weight-gradient stream: flag-only, this thread's on the current device, so concurrent
+    // callers, other devices and stream capture never share one.  ev[0]: "this half-step's
+    // operands are ready" (recorded on the main stream, waited for by the auxiliary one); ev[1 + set]: "the dW launch
+    // that read operand set `set` is done" - needed before a set is refilled (flows with more half-steps than sets) and,
+    // for the last launch, as the final join.
     static thread_local EventCache tl_events;
     int cur_dev = 0;
     (void)hipGetDevice(&cur_dev);
@@ -2250,31 +2291,109 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
     if (aux)
         for (int q = 0; q < kBwdMaxSets + 2; ++q)
             if (!call_ev[q]) GNF_HIP_TRY(hipEventCreateWithFlags(&call_ev[q], hipEventDisableTiming));
-    // whatever path leaves this function after the auxiliary stream was given work, the caller's stream is ordered
-    // behind it (an early error return used to leave the fork unjoined: fatal inside a stream capture)
-    struct AuxJoin {
-        hipStream_t aux, st;
-        hipEvent_t ev;
-        bool armed = false;
-        ~AuxJoin() {
-            if (armed && aux && ev && hipEventRecord(ev, aux) == hipSuccess) (void)hipStreamWaitEvent(st, ev, 0);
-        }
-    } aux_join{aux, st, aux ? call_ev[kBwdMaxSets + 1] : nullptr};
+    AuxJoin aux_join{aux, st, aux ? call_ev[kBwdMaxSets + 1] : nullptr};
     const hipEvent_t ev_ready = call_ev[0];
     hipEvent_t ev_done[kBwdMaxSets] = {};
     hipEvent_t ev_last = nullptr;
-    int step = 0;
-    bool used[2] = {false, false};  // weight sharing: the T uses of a net accumulate
+
+    auto resolve_half = [&](int i, int half, int step) {
+        HalfOps h;
+        h.step = step, h.set = step % p.n_sets, h.last = step == 2 * T - 1;
+        h.co = half == 0 ? 0 : H, h.uo = half == 0 ? H : 0;
+        h.nets[0] = flow_net(flow, flow->s_nets, half, i), h.nets[1] = flow_net(flow, flow->t_nets, half, i);
+        h.grads[0] = flow_net(grad, grad->s_nets, half, i), h.grads[1] = flow_net(grad, grad->t_nets, half, i);
+        h.acc = flow->weight_sharing && i < T - 1;  // weight sharing: the T uses of a net accumulate
+        h.attn = h.nets[0]->attn != nullptr;
+        h.fused = !opt(OPT_BWD_GENERIC) && fused_bwd_supported(h.nets[0], h.nets[1]);  // (the option: shape forcing for the parity tests)
+        h.x_cond = z + h.co;
+        BwdOperands& o = h.o = bwd_operands(p, wsf, h.set, h.attn);
+        const size_t k = (size_t)(2 * i + half);   // the half-step's slot in either stash
+        // attention front-end left behind by the forward pass (GnfFlow.attn_stash): q | k | v and the layer-0
+        // inputs of both nets are read from the half-step's slot instead of being recomputed
+        h.front_stashed = h.attn && stash_slot > 0 && flow->attn_stash != nullptr;
+        if (h.front_stashed) {
+            float* slot = flow->attn_stash + k * stash_slot;
+            for (int q = 0; q < 2; ++q) {
+                o.qkv[q] = slot + R.qkv[q];
+                o.h0[q] = slot + R.h0[q];
+                o.hin[q * p.K] = o.h0[q];
+                // attended values (A operand of dWo) and softmax statistics of the forward pass
+                o.agg[q] = slot + R.agg[q];
+                o.stats[q] = slot + R.stats[q];
+            }
+        }
+        // layer inputs of both nets, s, t and the act' ballots come from the half-step's slot of the MLP-row stash.  (stb:
+        // read by the generic path alone, mlp_backward_generic; the tile kernels take s, t as st_in and the ballots, which
+        // the layered mode does not write, as mask_in)
+        if (mstashed) {
+            float* slot = flow->mlp_stash + k * msl.slot;
+            for (int q = 0; q < 2; ++q) {
+                if (!h.attn) {  // (attention nets: the layer-0 inputs are the front-end's, stashed or recomputed)
+                    o.h0[q] = slot + msl.h0;
+                    o.hin[q * p.K] = o.h0[q];
+                }
+                for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act_of(q, j);
+                h.st_in[q] = o.stb[q] = slot + msl.st_of(q);
+            }
+            h.mask_in = reinterpret_cast<const unsigned long long*>(slot + msl.mask);
+        }
+        if (h.attn && wot_packed) {
+            const int ni = flow->weight_sharing ? half : half * T + i;
+            for (int q = 0; q < 2; ++q) {   // (s-nets first, then t-nets: BwdPlan.wot)
+                h.wot[q] = wsf + p.wot + (size_t)(q * n_nets + ni) * p.wot_each;
+                h.wct[q] = wsf + p.wct + (size_t)(q * n_nets + ni) * p.wct_each;
+            }
+        }
+        if (flow->bns) h.bn = &flow->bns[half * T + i], h.gbn = &grad->bns[half * T + i];
+        return h;
+    };
+    // ---- layer-0 inputs, where no stash supplies them ---------------------------------------------------------
+    auto layer0_inputs = [&](const HalfOps& h) -> int {
+        const BwdOperands& o = h.o;
+        if (h.attn) {   // recompute the attention front-end of both nets (q | k | v kept for the way back)
+            const GnfAttn* at[2] = {h.nets[0]->attn, h.nets[1]->attn};
+            if (h.front_stashed) return GNF_OK;
+            // (the conditioning half as the dW GEMMs of Wq / Wk / Wv read it, o.xc, is copied by the attention
+            // backward's last kernel: launch_attn_backward)
+            return attn_is_graph(at[0])
+                       ? launch_attn_graph_front(at, 2, n, h.x_cond, ld, H, p.in0, csr->node_offsets, csr->n_graphs, o.qkv[0], o.h0,
+                                                 st, o.agg, o.stats)
+                       : launch_attn_front(csr->rowptr, csr->col, n, h.x_cond, ld, H, at, 2, p.in0, o.qkv[0], o.h0, st,
+                                           csr->n_edges, true, nullptr, o.agg, o.stats);
+        }
+        // (the fused kernels aggregate themselves; layered stash: the forward's layer-0 rows are in the slot - so o.h0[0]
+        // is the workspace's whenever this launch runs)
+        if (h.fused || layered) return GNF_OK;
+        return launch_aggregate(csr->rowptr, csr->col, n, h.x_cond, ld, H, flow->gnn.agg == GNF_AGG_MEAN,
+                                flow->gnn.combine == GNF_COMBINE_CONCAT ? 1 : 0, flow->gnn.epsilon, o.h0[0], p.in0, st);
+    };
+    // the tile kernel's launch for one half-step: its operands, the stash rows where the forward left them, and, where
+    // Wo^T is packed, dagg = dnew Wo^T as the kernel's last table row instead of a GEMM launch (have_dagg)
+    auto tile_launch = [&](const HalfOps& h, const BwdFold* fold, TileLaunch* t) -> int {
+        const BwdOperands& o = h.o;
+        const int rc_ = build_bwd_args(csr->rowptr, csr->col, n, flow->gnn, h.nets[0], h.nets[1], h.x_cond, z + h.uo, ld, g + h.uo,
+                                       D, H, o.h0[0], h.attn ? o.h0 : nullptr, o.hin, p.lmax, o.dPs, p.lmax, o.gst, o.dh0, &t->ba,
+                                       &t->mt, &t->tiles, &t->lds, fold);
+        if (rc_) return rc_;
+        t->have_dagg = h.wot[0] && bwd_args_add_dagg_row(&t->ba, h.wot, o.dagg, p.C, p.NV, h.nets[0]->attn->concat ? H : 0);
+        if (mstashed) t->ba.st_in[0] = h.st_in[0], t->ba.st_in[1] = h.st_in[1], t->ba.mask_in = h.mask_in;
+        return GNF_OK;
+    };
     // the attention front-end backwards: dagg = dnew Wo^T ([nodes, C] x [C, heads*v]; Wo is [heads*v, C]: rows = output
-    // columns), then the edge kernels; dL/dx_cond accumulates into g_cond
-    auto attention_backward = [&](const GnfMlp* const* nets_, const BwdOperands& o_, float* g_cond, const AttnBnFold* bnf,
-                                  const float* x_cond_, bool have_dagg = false, const float* const* wct_ = nullptr) -> int {
-        const GnfAttn* at[2] = {nets_[0]->attn, nets_[1]->attn};
-        const int off = at[0]->concat ? D / 2 : 0;
+    // columns), then the edge kernels; dL/dx_cond accumulates into the conditioning half of g.  *bn_pre: batch-norm
+    // backward moments left by the attention backward's last kernel for the bijector in front of the half-step (partial rows)
+    auto attention_backward = [&](const HalfOps& h, bool have_dagg, int32_t* bn_pre) -> int {
+        const BwdOperands& o = h.o;
+        const AttnBnFold bnf{z + h.co, ld, h.bn ? h.bn->gamma : nullptr, h.bn ? h.bn->beta : nullptr,
+                             reinterpret_cast<double*>(wsf + p.bnpart), bn_pre};
+        *bn_pre = 0;
+        float* const g_cond = g + h.co;
+        const GnfAttn* at[2] = {h.nets[0]->attn, h.nets[1]->attn};
+        const int off = at[0]->concat ? H : 0;
         const bool graph = attn_is_graph(at[0]);
         if (!have_dagg && (!graph || at[0]->Wo)) {  // (else: the backward tile kernel's last table row has written it)
             GemmJob jobs[2];
-            for (int q = 0; q < 2; ++q) jobs[q] = GemmJob{o_.dh0[q] + off, at[q]->Wo, o_.dagg[q], nullptr, nullptr};
+            for (int q = 0; q < 2; ++q) jobs[q] = GemmJob{o.dh0[q] + off, at[q]->Wo, o.dagg[q], nullptr, nullptr};
             GemmShape sh;
             memset(&sh, 0, sizeof(sh));
             sh.lda = p.in0, sh.ldb = p.C, sh.ldc = p.NV;
@@ -2284,291 +2403,166 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
         }
         if (graph) {   // the graph scope's two passes + dL/dx_cond (gnf_attn_graph_bwd.hip); no batch-norm moments left behind
             const bool proj = at[0]->Wo != nullptr;   // (without Wo the attended values and their gradient live in h0 / dh0[:, H:))
-            const float* dg[2] = {proj ? o_.dagg[0] : o_.dh0[0] + off, proj ? o_.dagg[1] : o_.dh0[1] + off};
-            const float* ag[2] = {proj ? o_.agg[0] : o_.h0[0] + off, proj ? o_.agg[1] : o_.h0[1] + off};
-            const float* qk[2] = {o_.qkv[0], o_.qkv[1]};
-            const float* dh[2] = {o_.dh0[0], o_.dh0[1]};
-            if (bnf && bnf->n_parts) *bnf->n_parts = 0;
-            return launch_attn_graph_backward(at, n, D / 2, p.in0, csr->node_offsets, csr->n_graphs, qk, dg, proj ? p.NV : p.in0, ag,
-                                              proj ? p.NV : p.in0, o_.stats, o_.dqkv, dh, g_cond, D, x_cond_, ld, o_.xc, st);
+            const float* dg[2] = {proj ? o.dagg[0] : o.dh0[0] + off, proj ? o.dagg[1] : o.dh0[1] + off};
+            const float* ag[2] = {proj ? o.agg[0] : o.h0[0] + off, proj ? o.agg[1] : o.h0[1] + off};
+            return launch_attn_graph_backward(at, n, H, p.in0, csr->node_offsets, csr->n_graphs, o.qkv, dg, proj ? p.NV : p.in0, ag,
+                                              proj ? p.NV : p.in0, o.stats, o.dqkv, o.dh0, g_cond, D, h.x_cond, ld, o.xc, st);
         }
-        return launch_attn_backward(at, n, D / 2, p.in0, csr->rowptr, csr->col, csr_t->rowptr, csr_t->col, o_.qkv, o_.dh0, o_.gst,
-                                    o_.dqkv, o_.agg, o_.dagg, o_.stats, g_cond, D, st, csr->n_edges, bnf, x_cond_, ld, o_.xc, wct_);
+        return launch_attn_backward(at, n, H, p.in0, csr->rowptr, csr->col, csr_t->rowptr, csr_t->col, o.qkv, o.dh0, o.gst,
+                                    o.dqkv, o.agg, o.dagg, o.stats, g_cond, D, st, csr->n_edges, h.bn ? &bnf : nullptr, h.x_cond,
+                                    ld, o.xc, h.wct[0] ? h.wct : nullptr);
     };
-    int32_t bn_pre = 0;  // batch-norm backward moments left by the attention backward's last kernel (partial rows)
-    DwLaunch pend[2];
+    // backward pass of the bijector in front of a half-step; nparts: rows of moments the attention backward left
+    auto bn_backward = [&](const HalfOps& h, int nparts) -> int {
+        return launch_bn_backward(flow, h.bn, h.gbn, z + h.co, ld, g + h.co, D, n, H, reinterpret_cast<double*>(wsf + p.bnpart),
+                                  st, nparts);
+    };
+
+    // ---- the merged route: what a half-step leaves for the launches of the next two -----------------------------------
+    DwLaunch pend[2];   // dW plans of the last two half-steps, by the parity of the step
     bool pend_ok[2] = {false, false};
     bool have_fold = false;  // the previous half-step left its dL/dh0 rows for this one's prologue to scatter
-    // the previous half-step's batch-norm bijector, left for this half-step's tile kernel to undo where it reads the
-    // half it updates (BwdArgs.bn_part): merged walk, partial sums left by the attention backward's last kernel, no
-    // cross-rank moments
-    struct PendingBn {
-        const GnfBatchNorm* bn = nullptr;
-        const GnfBatchNorm* gbn = nullptr;
-        int nparts = 0;
-        int co = 0;
-    } pend_bn;
-    auto flush_bn = [&]() -> int {
-        if (!pend_bn.bn) return GNF_OK;
-        const int rc_ = launch_bn_backward(flow, pend_bn.bn, pend_bn.gbn, z + pend_bn.co, ld, g + pend_bn.co, D, n, H,
-                                           reinterpret_cast<double*>(wsf + p.bnpart), st, pend_bn.nparts);
-        pend_bn.bn = nullptr;
-        return rc_;
-    };
     const float* fold_dh[2] = {nullptr, nullptr};
-    for (int i = T - 1; i >= 0; --i)
-        for (int half = 1; half >= 0; --half) {
-            const GnfMlp* nets[2] = {flow_net(flow, flow->s_nets, half, i), flow_net(flow, flow->t_nets, half, i)};
-            const GnfMlp* grads[2] = {flow_net(grad, grad->s_nets, half, i), flow_net(grad, grad->t_nets, half, i)};
-            const bool acc = flow->weight_sharing && used[half];
-            used[half] = true;
-            const int co = half == 0 ? 0 : H, uo = half == 0 ? H : 0;
-            const bool no_fused = opt(OPT_BWD_GENERIC) != 0;  // (shape forcing for the parity tests)
-            const bool attn = nets[0]->attn != nullptr;
-            const bool fused = !no_fused && fused_bwd_supported(nets[0], nets[1]);
-            const int set = step % p.n_sets;
-            BwdOperands o = bwd_operands(p, wsf, set, attn);
-            // attention front-end left behind by the forward pass (GnfFlow.attn_stash): q | k | v and the layer-0
-            // inputs of both nets are read from the half-step's slot instead of being recomputed
-            const bool stashed = attn && stash_slot > 0 && flow->attn_stash != nullptr;
-            if (stashed) {
-                float* slot = flow->attn_stash + (size_t)(2 * i + half) * stash_slot;
-                for (int q = 0; q < 2; ++q) {
-                    o.qkv[q] = slot + R.qkv[q];
-                    o.h0[q] = slot + R.h0[q];
-                    o.hin[q * p.K] = o.h0[q];
-                    // attended values (A operand of dWo) and softmax statistics of the forward pass
-                    o.agg[q] = slot + R.agg[q];
-                    o.stats[q] = slot + R.stats[q];
-                }
-            }
-            float* x_cond = z + co;
-            // this set's previous reader (the dW GEMMs of n_sets half-steps ago) must be done
-            if (aux && reuse_sets && ev_done[set]) GNF_HIP_TRY(hipStreamWaitEvent(st, ev_done[set], 0));
-            // ---- layer-0 inputs -------------------------------------------------------------------------
-            if (attn) {   // recompute the attention front-end of both nets (q | k | v kept for the way back)
-                const GnfAttn* at[2] = {nets[0]->attn, nets[1]->attn};
-                if (!stashed) {
-                    rc = attn_is_graph(at[0])
-                             ? launch_attn_graph_front(at, 2, n, x_cond, ld, H, p.in0, csr->node_offsets, csr->n_graphs, o.qkv[0], o.h0,
-                                                       st, o.agg, o.stats)
-                             : launch_attn_front(csr->rowptr, csr->col, n, x_cond, ld, H, at, 2, p.in0, o.qkv[0], o.h0, st,
-                                                 csr->n_edges, true, nullptr, o.agg, o.stats);
-                    if (rc) return rc;
-                }
-                // (the conditioning half as the dW GEMMs of Wq / Wk / Wv read it, o.xc, is copied by the attention
-                // backward's last kernel: launch_attn_backward)
-            } else if (!fused && !(mstashed && layered)) {   // (layered stash: the forward's layer-0 rows are in the slot)
-                rc = launch_aggregate(csr->rowptr, csr->col, n, x_cond, ld, H, flow->gnn.agg == GNF_AGG_MEAN,
-                                      flow->gnn.combine == GNF_COMBINE_CONCAT ? 1 : 0, flow->gnn.epsilon, o.h0[0], p.in0, st);
-                if (rc) return rc;
-            }
-            if (merged) {
-                BwdArgs ba;
-                int mt;
-                int64_t tiles;
-                size_t lds;
-                // the previous half-step's message-passing backward rides in this launch's prologue: it scatters into
-                // the gradient of the half this half-step updates (with a batch-norm bijector in between, its backward
-                // needs that gradient complete first: the scatter keeps its own launch)
-                if (mstashed) {  // layer inputs of both nets come from the half-step's slot of the stash
-                    float* slot = flow->mlp_stash + (size_t)(2 * i + half) * msl.slot;
-                    for (int q = 0; q < 2; ++q) {
-                        if (!attn) {  // (attention nets: the layer-0 inputs are the front-end's, stashed or recomputed above)
-                            o.h0[q] = slot + msl.h0;
-                            o.hin[q * p.K] = o.h0[q];
-                        }
-                        for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act_of(q, j);
-                    }
-                }
-                const float* h0c[2] = {o.h0[0], o.h0[1]};
-                BwdFold bf;
-                const bool folded = have_fold;
-                if (folded) {
-                    bf.rowptr_t = csr_t->rowptr, bf.col_t = csr_t->col;
-                    bf.invdeg = flow->gnn.agg == GNF_AGG_MEAN ? wsf + p.invdeg : nullptr;
-                    bf.dh_prev[0] = fold_dh[0], bf.dh_prev[1] = fold_dh[1];
-                }
-                rc = build_bwd_args(csr->rowptr, csr->col, n, flow->gnn, nets[0], nets[1], x_cond, z + uo, ld, g + uo, D, H,
-                                    o.h0[0], attn ? h0c : nullptr, o.hin, p.lmax, o.dPs, p.lmax, o.gst, o.dh0, &ba, &mt, &tiles, &lds,
-                                    folded ? &bf : nullptr);
-                if (rc) return rc;
-                if (pend_bn.bn) {  // (pend_bn.co is this half-step's updated half by construction)
-                    ba.bn_part = reinterpret_cast<const double*>(wsf + p.bnpart);
-                    ba.bn_nparts = pend_bn.nparts;
-                    ba.bn_gamma = pend_bn.bn->gamma, ba.bn_beta = pend_bn.bn->beta;
-                    ba.bn_mean = pend_bn.bn->batch_mean, ba.bn_var = pend_bn.bn->batch_variance;
-                    ba.bn_eps = pend_bn.bn->epsilon;
-                    ba.bn_dgamma = const_cast<float*>(pend_bn.gbn->gamma), ba.bn_dbeta = const_cast<float*>(pend_bn.gbn->beta);
-                    pend_bn.bn = nullptr;
-                }
-                bool have_dagg = false;
-                const float* wct[2] = {nullptr, nullptr};
-                if (attn && wot_packed) {  // dagg = dnew Wo^T as the tile kernel's last row instead of a GEMM launch
-                    const int ni = flow->weight_sharing ? half : half * T + i;
-                    const float* wot[2] = {wsf + p.wot + (size_t)ni * p.wot_each, wsf + p.wot + (size_t)(n_nets_each + ni) * p.wot_each};
-                    have_dagg = bwd_args_add_dagg_row(&ba, wot, o.dagg, p.C, p.NV, nets[0]->attn->concat ? H : 0);
-                    wct[0] = wsf + p.wct + (size_t)ni * p.wct_each;
-                    wct[1] = wsf + p.wct + (size_t)(n_nets_each + ni) * p.wct_each;
-                }
-                if (mstashed) {
-                    const float* slot = flow->mlp_stash + (size_t)(2 * i + half) * msl.slot;
-                    for (int q = 0; q < 2; ++q) ba.st_in[q] = slot + msl.st_of(q);
-                    ba.mask_in = reinterpret_cast<const unsigned long long*>(slot + msl.mask);
-                }
-                const int prev = (step + 1) & 1, cur = step & 1;   // pend[prev]: half-step k-1, pend[cur]: k-2
-                rc = launch_half_bwd_dw(&ba, tiles, lds, step >= 1 && pend_ok[prev] ? &pend[prev] : nullptr,
-                                        step >= 2 && pend_ok[cur] ? &pend[cur] : nullptr, mstashed, st);
-                if (rc) return rc;
-                // this half-step's dW GEMMs ride in the next launch (the last one's get the whole chip)
-                WGJob jobs[kMaxGroup];
-                const int nj = weight_grad_jobs(p, o, nets, grads, jobs);
-                const bool last = step == 2 * T - 1;
-                const int cus = big_cu_count();
-                int room = last ? cus : cus - (int)tiles;   // CUs the backward tiles of the NEXT launch leave
-                if (const int64_t force = opt(OPT_DW_WIDE_UNITS)) room = force < room ? (int)force : room;  // (shape forcing for the parity tests)
-                DwPolicy pol{room, lds, 1e30};
-                if (mstashed && !last && !opt(OPT_DW_THIN_ON_DW)) pol.tile_wgs = (int)tiles;  // (the launch that carries this plan walks the next half-step)
-                rc = plan_weight_grads(p, pol, jobs, nj, acc, wsf, cur, &pend[cur]);
-                if (rc) return rc;
-                pend_ok[cur] = pend[cur].wide && pend[cur].buf && nj <= kMergedGroup;
-                if (!pend_ok[cur]) {  // (a plan the merged launch cannot carry: run it here and now)
-                    rc = run_weight_gemms(pend[cur], st);
-                    if (rc) return rc;
-                    rc = run_weight_reduce(pend[cur], st);
-                    if (rc) return rc;
-                }
-                have_fold = !attn && !flow->bns && !last;
-                if (attn) {
-                    const GnfBatchNorm* bq = flow->bns ? &flow->bns[half * T + i] : nullptr;
-                    const AttnBnFold bnf{z + co, ld, bq ? bq->gamma : nullptr, bq ? bq->beta : nullptr,
-                                         reinterpret_cast<double*>(wsf + p.bnpart), &bn_pre};
-                    bn_pre = 0;
-                    rc = attention_backward(nets, o, g + co, bq ? &bnf : nullptr, x_cond, have_dagg, wct[0] ? wct : nullptr);
-                    if (rc) return rc;
-                } else if (have_fold) {
-                    fold_dh[0] = o.dh0[0], fold_dh[1] = o.dh0[1];
-                } else {
-                    rc = launch_aggregate_bwd(p, csr_t, flow->gnn, wsf + p.invdeg, o.dh0[0], o.dh0[1], g + co, D, st);
-                    if (rc) return rc;
-                }
-                ++step;
-                if (flow->bns) {
-                    const bool more = !(i == 0 && half == 0);
-                    if (more && attn && bn_pre > 0 && !flow->bn_allreduce && H <= 128 && !folded) {
-                        pend_bn.bn = &flow->bns[half * T + i], pend_bn.gbn = &grad->bns[half * T + i];
-                        pend_bn.nparts = bn_pre, pend_bn.co = co;
-                    } else {
-                        rc = launch_bn_backward(flow, &flow->bns[half * T + i], &grad->bns[half * T + i], z + co, ld, g + co, D, n, H,
-                                                reinterpret_cast<double*>(wsf + p.bnpart), st, attn ? bn_pre : 0);
-                        if (rc) return rc;
-                    }
-                }
-                continue;
-            }
-            // ---- recompute + coupling + dP chain -------------------------------------------------------------
-            bool nm_have_dagg = false;
-            const float* nm_wct[2] = {nullptr, nullptr};
-            if (attn && wot_packed) {
-                const int ni = flow->weight_sharing ? half : half * T + i;
-                nm_wct[0] = wsf + p.wct + (size_t)ni * p.wct_each;
-                nm_wct[1] = wsf + p.wct + (size_t)(n_nets_each + ni) * p.wct_each;
-            }
-            if (fused && mstashed) {  // (attention nets, or the auxiliary-stream scheme by option: the stash without the merged launch)
-                float* slot = flow->mlp_stash + (size_t)(2 * i + half) * msl.slot;
-                for (int q = 0; q < 2; ++q)
-                    for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act_of(q, j);
-                if (!attn) o.h0[0] = o.h0[1] = o.hin[0] = o.hin[p.K] = slot + msl.h0;
-                const float* h0c[2] = {o.h0[0], o.h0[1]};
-                BwdArgs ba;
-                int mt;
-                int64_t tiles;
-                size_t lds;
-                rc = build_bwd_args(csr->rowptr, csr->col, n, flow->gnn, nets[0], nets[1], x_cond, z + uo, ld, g + uo, D, H,
-                                    o.h0[0], attn ? h0c : nullptr, o.hin, p.lmax, o.dPs, p.lmax, o.gst, o.dh0, &ba, &mt, &tiles, &lds);
-                if (rc) return rc;
-                for (int q = 0; q < 2; ++q) ba.st_in[q] = slot + msl.st_of(q);
-                ba.mask_in = reinterpret_cast<const unsigned long long*>(slot + msl.mask);
-                if (attn && wot_packed) {  // (as on the merged walk)
-                    const int ni = flow->weight_sharing ? half : half * T + i;
-                    const float* wot[2] = {wsf + p.wot + (size_t)ni * p.wot_each, wsf + p.wot + (size_t)(n_nets_each + ni) * p.wot_each};
-                    nm_have_dagg = bwd_args_add_dagg_row(&ba, wot, o.dagg, p.C, p.NV, nets[0]->attn->concat ? H : 0);
-                }
-                rc = launch_half_bwd_fused_stashed(ba, mt, tiles, lds, st);
-            } else if (fused) {
-                const float* h0c[2] = {o.h0[0], o.h0[1]};
-                rc = launch_half_bwd_fused(csr->rowptr, csr->col, n, flow->gnn, nets[0], nets[1], x_cond, z + uo, ld,
-                                           g + uo, D, H, o.h0[0], attn ? h0c : nullptr, o.hin, p.lmax, o.dPs, p.lmax,
-                                           o.gst, o.dh0, st);
-            } else {
-                const bool rows = mstashed && layered;
-                if (rows) {  // the forward's layered path left every layer input and s, t in the half-step's slot
-                    float* slot = flow->mlp_stash + (size_t)(2 * i + half) * msl.slot;
-                    for (int q = 0; q < 2; ++q) {
-                        if (!attn) o.h0[q] = slot + msl.h0, o.hin[q * p.K] = o.h0[q];
-                        for (int j = 1; j < p.K; ++j) o.hin[q * p.K + j] = slot + msl.act_of(q, j);
-                        o.stb[q] = slot + msl.st_of(q);
-                    }
-                }
-                rc = mlp_backward_generic(p, o, flow->gnn, nets, grads, acc, x_cond, z + uo, ld, g + uo, D, wsf, st, rows);
-            }
-            if (rc) return rc;
-            // message passing: the weight gradients only read what the fused kernel has just written, so their stream
-            // forks HERE, before the scatter of dL/dx_cond (with an attention front-end they also read its backward
-            // pass and fork after it)
-            const bool early_fork = aux && !attn;
-            if (early_fork) {
+    // the previous half-step's batch-norm bijector, left for this half-step's tile kernel to undo where it reads the
+    // half it updates (BwdArgs.bn_part): partial sums left by the attention backward's last kernel, no cross-rank
+    // moments.  Never pending after the last half-step, which runs its bijector's own launch.
+    const GnfBatchNorm *pend_bn = nullptr, *pend_gbn = nullptr;
+    int pend_bn_parts = 0;
+    auto half_merged = [&](const HalfOps& h) -> int {
+        const BwdOperands& o = h.o;
+        int rc_ = layer0_inputs(h);
+        if (rc_) return rc_;
+        // the previous half-step's message-passing backward rides in this launch's prologue: it scatters into
+        // the gradient of the half this half-step updates (with a batch-norm bijector in between, its backward
+        // needs that gradient complete first: the scatter keeps its own launch)
+        BwdFold bf;
+        const bool folded = have_fold;
+        if (folded) {
+            bf.rowptr_t = csr_t->rowptr, bf.col_t = csr_t->col;
+            bf.invdeg = flow->gnn.agg == GNF_AGG_MEAN ? wsf + p.invdeg : nullptr;
+            bf.dh_prev[0] = fold_dh[0], bf.dh_prev[1] = fold_dh[1];
+        }
+        TileLaunch t;
+        rc_ = tile_launch(h, folded ? &bf : nullptr, &t);
+        if (rc_) return rc_;
+        BwdArgs& ba = t.ba;
+        if (pend_bn) {  // (the half it normalised is this half-step's updated half by construction)
+            ba.bn_part = reinterpret_cast<const double*>(wsf + p.bnpart);
+            ba.bn_nparts = pend_bn_parts;
+            ba.bn_gamma = pend_bn->gamma, ba.bn_beta = pend_bn->beta;
+            ba.bn_mean = pend_bn->batch_mean, ba.bn_var = pend_bn->batch_variance;
+            ba.bn_eps = pend_bn->epsilon;
+            ba.bn_dgamma = const_cast<float*>(pend_gbn->gamma), ba.bn_dbeta = const_cast<float*>(pend_gbn->beta);
+            pend_bn = nullptr;
+        }
+        const int step = h.step, prev = (step + 1) & 1, cur = step & 1;   // pend[prev]: half-step k-1, pend[cur]: k-2
+        rc_ = launch_half_bwd_dw(&ba, t.tiles, t.lds, step >= 1 && pend_ok[prev] ? &pend[prev] : nullptr,
+                                 step >= 2 && pend_ok[cur] ? &pend[cur] : nullptr, mstashed, st);
+        if (rc_) return rc_;
+        // this half-step's dW GEMMs ride in the next launch (the last one's get the whole chip)
+        WGJob jobs[kMaxGroup];
+        const int nj = weight_grad_jobs(p, o, h.nets, h.grads, jobs);
+        const int cus = big_cu_count();
+        int room = h.last ? cus : cus - (int)t.tiles;   // CUs the backward tiles of the NEXT launch leave
+        if (const int64_t force = opt(OPT_DW_WIDE_UNITS)) room = force < room ? (int)force : room;  // (shape forcing for the parity tests)
+        DwPolicy pol{room, t.lds, 1e30};
+        if (mstashed && !h.last && !opt(OPT_DW_THIN_ON_DW)) pol.tile_wgs = (int)t.tiles;  // (the launch that carries this plan walks the next half-step)
+        rc_ = plan_weight_grads(p, pol, jobs, nj, h.acc, wsf, cur, &pend[cur]);
+        if (rc_) return rc_;
+        pend_ok[cur] = pend[cur].wide && pend[cur].buf && nj <= kMergedGroup;
+        if (!pend_ok[cur]) {  // (a plan the merged launch cannot carry: run it here and now)
+            rc_ = run_weight_gemms(pend[cur], st);
+            if (rc_) return rc_;
+            rc_ = run_weight_reduce(pend[cur], st);
+            if (rc_) return rc_;
+        }
+        have_fold = !h.attn && !flow->bns && !h.last;
+        int32_t bn_pre = 0;
+        if (h.attn) {
+            rc_ = attention_backward(h, t.have_dagg, &bn_pre);
+            if (rc_) return rc_;
+        } else if (have_fold) {
+            fold_dh[0] = o.dh0[0], fold_dh[1] = o.dh0[1];
+        } else {
+            rc_ = launch_aggregate_bwd(p, csr_t, flow->gnn, wsf + p.invdeg, o.dh0[0], o.dh0[1], g + h.co, D, st);
+            if (rc_) return rc_;
+        }
+        if (!h.bn) return GNF_OK;
+        if (h.last || !h.attn || bn_pre <= 0 || flow->bn_allreduce || H > 128 || folded) return bn_backward(h, bn_pre);
+        pend_bn = h.bn, pend_gbn = h.gbn, pend_bn_parts = bn_pre;
+        return GNF_OK;
+    };
+
+    // ---- the stream-forking route: the dW GEMMs of every half-step go to the auxiliary stream, where the caller gave one ----
+    auto half_streams = [&](const HalfOps& h) -> int {
+        const BwdOperands& o = h.o;
+        // this set's previous reader (the dW GEMMs of n_sets half-steps ago) must be done
+        if (aux && reuse_sets && ev_done[h.set]) GNF_HIP_TRY(hipStreamWaitEvent(st, ev_done[h.set], 0));
+        int rc_ = layer0_inputs(h);
+        if (rc_) return rc_;
+        // ---- recompute + coupling + dP chain -------------------------------------------------------------
+        TileLaunch t;
+        if (h.fused && mstashed) {  // (attention nets, or the auxiliary-stream scheme by option: the stash without the merged launch)
+            rc_ = tile_launch(h, nullptr, &t);
+            if (rc_) return rc_;
+            rc_ = launch_half_bwd_fused_stashed(t.ba, t.mt, t.tiles, t.lds, st);
+        } else if (h.fused) {
+            rc_ = launch_half_bwd_fused(csr->rowptr, csr->col, n, flow->gnn, h.nets[0], h.nets[1], h.x_cond, z + h.uo, ld,
+                                        g + h.uo, D, H, o.h0[0], h.attn ? o.h0 : nullptr, o.hin, p.lmax, o.dPs, p.lmax,
+                                        o.gst, o.dh0, st);
+        } else {  // (layered stash: the forward's layered path left every layer input and s, t in the half-step's slot)
+            rc_ = mlp_backward_generic(p, o, flow->gnn, h.nets, h.grads, h.acc, h.x_cond, z + h.uo, ld, g + h.uo, D, wsf, st,
+                                       layered);
+        }
+        if (rc_) return rc_;
+        // message passing: the weight gradients only read what the fused kernel has just written, so their stream
+        // forks HERE, before the scatter of dL/dx_cond (with an attention front-end they also read its backward
+        // pass and fork after it)
+        const bool early_fork = aux && !h.attn;
+        if (early_fork) {
+            GNF_HIP_TRY(hipEventRecord(ev_ready, st));
+            GNF_HIP_TRY(hipStreamWaitEvent(aux, ev_ready, 0));
+        }
+        // ---- dL/dx_cond: on the critical path (the next half-step's coupling reads g), so it goes first -----
+        int32_t bn_pre = 0;
+        rc_ = h.attn ? attention_backward(h, t.have_dagg, &bn_pre)
+                     : launch_aggregate_bwd(p, csr_t, flow->gnn, wsf + p.invdeg, o.dh0[0], o.dh0[1], g + h.co, D, st);
+        if (rc_) return rc_;
+        // ---- weight gradients fork off behind it ------------------------------------------------------------
+        hipStream_t wst = st;
+        if (aux) {
+            if (!early_fork) {
                 GNF_HIP_TRY(hipEventRecord(ev_ready, st));
                 GNF_HIP_TRY(hipStreamWaitEvent(aux, ev_ready, 0));
             }
-            // ---- dL/dx_cond: on the critical path (the next half-step's coupling reads g), so it goes first -----
-            if (attn) {
-                const GnfBatchNorm* bq = flow->bns ? &flow->bns[half * T + i] : nullptr;
-                const AttnBnFold bnf{z + co, ld, bq ? bq->gamma : nullptr, bq ? bq->beta : nullptr,
-                                     reinterpret_cast<double*>(wsf + p.bnpart), &bn_pre};
-                bn_pre = 0;
-                rc = attention_backward(nets, o, g + co, bq ? &bnf : nullptr, x_cond, nm_have_dagg, nm_wct[0] ? nm_wct : nullptr);
-            } else {
-                rc = launch_aggregate_bwd(p, csr_t, flow->gnn, wsf + p.invdeg, o.dh0[0], o.dh0[1], g + co, D, st);
-            }
-            if (rc) return rc;
-            // ---- weight gradients fork off behind it ------------------------------------------------------------
-            {
-                hipStream_t wst = st;
-                if (aux) {
-                    if (!early_fork) {
-                        GNF_HIP_TRY(hipEventRecord(ev_ready, st));
-                        GNF_HIP_TRY(hipStreamWaitEvent(aux, ev_ready, 0));
-                    }
-                    wst = aux;
-                }
-                WGJob jobs[kMaxGroup];
-                const int nj = weight_grad_jobs(p, o, nets, grads, jobs);
-                int64_t bwd_tiles = 0;
-                size_t bwd_lds = 0;
-                // (attention nets: the edge kernels of the next half-step want every CU; the grouped kernel's short
-                // workgroups share with them better - measured 7.8 vs 8.4 ms per step)
-                if (fused && !attn) fused_bwd_launch_shape(nets[0], n, &bwd_tiles, &bwd_lds);
-                rc = launch_weight_grads(p, dw_policy(nets[0], bwd_tiles, bwd_lds), jobs, nj, acc, wsf, wst);
-                if (rc) return rc;
-                if (aux && (reuse_sets || step == 2 * T - 1)) {
-                    hipEvent_t e = call_ev[1 + (reuse_sets ? set : 0)];
-                    aux_join.armed = true;
-                    GNF_HIP_TRY(hipEventRecord(e, aux));
-                    ev_done[set] = e;
-                    ev_last = e;
-                }
-            }
-            ++step;
-            if (rc) return rc;
-            if (flow->bns) {  // the bijector sat in front of this half-step (gnn.py:310-313, 325-328)
-                rc = launch_bn_backward(flow, &flow->bns[half * T + i], &grad->bns[half * T + i], z + co, ld, g + co, D, n, H,
-                                        reinterpret_cast<double*>(wsf + p.bnpart), st, attn ? bn_pre : 0);
-                if (rc) return rc;
-            }
+            wst = aux;
         }
-    rc = flush_bn();  // (never pending here: the last half-step of the walk runs its bijector's own launch)
-    if (rc) return rc;
+        WGJob jobs[kMaxGroup];
+        const int nj = weight_grad_jobs(p, o, h.nets, h.grads, jobs);
+        int64_t bwd_tiles = 0;
+        size_t bwd_lds = 0;
+        // (attention nets: the edge kernels of the next half-step want every CU; the grouped kernel's short
+        // workgroups share with them better - measured 7.8 vs 8.4 ms per step)
+        if (h.fused && !h.attn) fused_bwd_launch_shape(h.nets[0], n, &bwd_tiles, &bwd_lds);
+        rc_ = launch_weight_grads(p, dw_policy(h.nets[0], bwd_tiles, bwd_lds), jobs, nj, h.acc, wsf, wst);
+        if (rc_) return rc_;
+        if (aux && (reuse_sets || h.last)) {
+            hipEvent_t e = call_ev[1 + (reuse_sets ? h.set : 0)];
+            aux_join.armed = true;
+            GNF_HIP_TRY(hipEventRecord(e, aux));
+            ev_done[h.set] = e;
+            ev_last = e;
+        }
+        return h.bn ? bn_backward(h, bn_pre) : GNF_OK;
+    };
+
+    int step = 0;
+    for (int i = T - 1; i >= 0; --i)
+        for (int half = 1; half >= 0; --half, ++step) {
+            const HalfOps h = resolve_half(i, half, step);
+            rc = merged ? half_merged(h) : half_streams(h);
+            if (rc) return rc;
+        }
     if (merged) {  // drain the pipeline: dW of the last half-step (+ the reduce before it), then its own reduce
         const int last = (step + 1) & 1, before = step & 1;
         rc = launch_half_bwd_dw(nullptr, 0, m_lds, pend_ok[last] ? &pend[last] : nullptr,
