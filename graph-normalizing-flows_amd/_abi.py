@@ -218,7 +218,22 @@ _ENCODER_TRAIN_SIGNATURES = {
                                                 C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/gnf_inverse_per_graph.h (included by gnf.h, added within ABI v10): per-graph likelihood of generated graphs from the
+# inverse pass, and the route report the tests read.  A table of its own for the same reason.
+_INVERSE_PER_GRAPH_SIGNATURES = {
+    "gnf_inverse_per_graph_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(GnfFlow)]),
+    "gnf_grevnet_inverse_per_graph_f32": (C.c_int, [C.POINTER(GnfCsr), C.POINTER(GnfFlow), C.c_void_p, C.c_int64, C.c_void_p,
+                                                    C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p]),
+    "gnf_last_route": (C.c_int64, []),
+}
+# enum GnfRoute: bits of gnf_last_route()
+ROUTE_BITS = {name: 1 << k for k, name in enumerate((
+    "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
+    "coupling", "coupling_rows", "layer_norm", "attn_pair", "row_sums"))}
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+INVERSE_PER_GRAPH_SYMBOLS = tuple(_INVERSE_PER_GRAPH_SIGNATURES)
 ORBIT_SYMBOLS = tuple(_ORBIT_SIGNATURES)
 ADJ_LOSS_SYMBOLS = tuple(_ADJ_LOSS_SIGNATURES)
 ENCODER_SYMBOLS = tuple(_ENCODER_SIGNATURES)
@@ -238,7 +253,8 @@ def lib():
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES,
-                                  **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES}.items():
+                                  **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
+                                  **_INVERSE_PER_GRAPH_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -260,6 +276,12 @@ def set_option(name, value):
 
 def get_option(name):
     return int(lib().gnf_get_option(name.encode()))
+
+
+def last_route():
+    """gnf_last_route as a set of names (ROUTE_BITS): the kernels this thread's last whole-flow call launched."""
+    bits = int(lib().gnf_last_route())
+    return {name for name, bit in ROUTE_BITS.items() if bits & bit}
 
 
 def check(rc, what):

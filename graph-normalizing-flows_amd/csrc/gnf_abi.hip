@@ -10,6 +10,7 @@
 namespace gnf {
 
 static thread_local char g_err[512] = "";
+thread_local int64_t g_route = 0;  // gnf_last_route
 
 std::atomic<int64_t> g_options[OPT_COUNT];  // zero-initialised: every option "auto"
 
@@ -271,6 +272,8 @@ size_t gnf_attn_stash_bytes(int64_t n_nodes, int32_t D, const GnfFlow* flow) {
 
 const char* gnf_last_error(void) { return g_err; }
 
+int64_t gnf_last_route(void) { return g_route; }
+
 int64_t gnf_packed_floats(const GnfMlp* mlp) {
     if (!mlp || mlp->num_layers < 1 || mlp->num_layers > GNF_MAX_LAYERS) {
         set_error("gnf_packed_floats: bad GnfMlp");
@@ -407,13 +410,16 @@ int gnf_grevnet_f32(const GnfCsr* csr, const GnfFlow* flow, float* x, int64_t ld
     return gnf_grevnet_from_f32(csr, flow, nullptr, 0, x, ld, D, direction, sums, ws, ws_bytes, stream);
 }
 
-// The walk over the flow's half-steps behind gnf_grevnet_from_f32 and gnf_grevnet_per_graph_f32.  row_ld (forward only;
-// NULL for the former): 2T slots of n doubles - half-step idx leaves sum_j s[r, j] of every row in slot idx, through the
-// ROWLD instance of whichever kernel runs it; bn_c: 2T doubles, bijector idx's per-node log-det term.  With both NULL the
-// launch sequence is the one it always was.
+// The walk over the flow's half-steps behind gnf_grevnet_from_f32, gnf_grevnet_per_graph_f32 and
+// gnf_grevnet_inverse_per_graph_f32.  row_ld (NULL for the first): 2T slots of n doubles - half-step idx = 2 i + half, in
+// either direction, leaves + sum_j s[r, j] of the s its coupling used for every row in slot idx, through the ROWLD instance
+// of whichever kernel runs it; bn_c: 2T doubles, bijector idx's per-node log-det term - forward: written by the pass that
+// takes the batch moments; inverse: constants of the flow (the moving statistics), one launch in front of the walk.  With
+// both NULL the launch sequence of either direction is the one it always was.
 static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
                        int32_t D, int32_t direction, double* sums, void* ws, size_t ws_bytes, gnf_stream_t stream,
                        double* row_ld, double* bn_c) {
+    g_route = 0;
     int rc = validate_flow_call(csr, flow, ld, D, "gnf_grevnet_f32");
     if (rc) return rc;
     if (x_src == x) x_src = nullptr;
@@ -624,11 +630,17 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
                 if (rc) return rc;
             }
         } else {
+            if (bn_c && flow->bns) {
+                rc = launch_bn_inverse_terms(flow, H, bn_c, st);
+                if (rc) return rc;
+            }
             for (int i = T - 1; i >= 0; --i) {  // gnn.py:347-372
                 for (int half = 1; half >= 0; --half) {
                     int32_t np_ = 0;
                     HalfStep hs = half_step(csr, flow, x, ld, H, GNF_INVERSE, half, i);
                     hs.partials = partials + used, hs.n_partials = &np_;
+                    // (the s the coupling uses comes from the conditioning half as it is BEFORE its bijector below)
+                    if (row_ld) hs.row_logdet = row_ld + (size_t)(2 * i + half) * (size_t)n;
                     mark_first(hs, half);
                     mark_attn(hs, half, i);
                     if (split_epoch) hs.split_epoch = split_epoch++;
@@ -639,7 +651,8 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
                     if (bn_on_load) hs.bnu_inv = inv_pending;
                     rc = run_half(hs, scratch, st);
                     if (rc) return rc;
-                    // partial slots are reused: the inverse pass has no log-det (gnn.py:343-373)
+                    // partial slots are reused: the inverse pass has no batch log-det (gnn.py:343-373; the per-graph entry
+                    // point takes it from the row sums)
                     if (flow->bns && bn_on_load) {
                         inv_pending = &flow->bns[half * T + i];
                     } else if (flow->bns) {
@@ -675,15 +688,14 @@ int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_
     return grevnet_run(csr, flow, x_src, ld_src, x, ld, D, direction, sums, ws, ws_bytes, stream, nullptr, nullptr);
 }
 
-// workspace of the per-graph entry point: [ gnf_workspace_bytes (256-aligned) | row log-dets [2T][n] fp64 | bijector terms [2T] fp64 ]
-static size_t per_graph_base_bytes(int64_t n_nodes, int32_t D, const GnfFlow* flow) {
-    return (gnf_workspace_bytes(n_nodes, D, flow) + 255) / 256 * 256;
+// workspace of the per-graph entry points, forward and inverse (PerGraphLayout, gnf_layout.h)
+static PerGraphLayout per_graph_ws(int64_t n_nodes, int32_t D, const GnfFlow* flow) {
+    return per_graph_layout(gnf_workspace_bytes(n_nodes, D, flow), n_nodes, flow->num_timesteps);
 }
 
 size_t gnf_per_graph_workspace_bytes(int64_t n_nodes, int64_t n_graphs, int32_t D, const GnfFlow* flow) {
     if (n_nodes < 0 || n_graphs < 0 || D < 2 || !flow || !flow->s_nets) return 0;
-    const size_t slots = 2 * (size_t)(flow->num_timesteps > 0 ? flow->num_timesteps : 1);
-    return per_graph_base_bytes(n_nodes, D, flow) + (slots * (size_t)n_nodes + slots) * sizeof(double);
+    return per_graph_ws(n_nodes, D, flow).total;
 }
 
 int gnf_grevnet_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
@@ -714,15 +726,85 @@ int gnf_grevnet_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const floa
         return ws ? GNF_EWORKSPACE : GNF_EINVAL;
     }
     const int T = flow->num_timesteps;
-    const size_t base = per_graph_base_bytes(n, D, flow);
-    double* row_ld = reinterpret_cast<double*>((char*)ws + base);
-    double* bn_c = row_ld + (size_t)2 * (T > 0 ? T : 1) * (size_t)n;
+    const PerGraphLayout L = per_graph_ws(n, D, flow);
+    const size_t base = L.base;
+    double* row_ld = reinterpret_cast<double*>((char*)ws + L.row_ld);
+    double* bn_c = reinterpret_cast<double*>((char*)ws + L.bn_c);
     // the inference walk: the training stashes are not written by this entry point
     GnfFlow fl = *flow;
     fl.attn_stash = nullptr, fl.attn_stash_bytes = 0, fl.mlp_stash = nullptr, fl.mlp_stash_bytes = 0;
     rc = grevnet_run(csr, &fl, x_src, ld_src, x, ld, D, GNF_FORWARD, sums, ws, base, stream, row_ld, flow->bns ? bn_c : nullptr);
     if (rc) return rc;
     return launch_per_graph(row_ld, 2 * T, n, bn_c, flow->bns ? 2 * T : 0, x, ld, D, csr->node_offsets, B, graph_out, st);
+}
+
+size_t gnf_inverse_per_graph_workspace_bytes(int64_t n_nodes, int64_t n_graphs, int32_t D, const GnfFlow* flow) {
+    if (n_nodes < 0 || n_graphs < 0 || D < 2 || !flow || !flow->s_nets) return 0;
+    return per_graph_ws(n_nodes, D, flow).total;
+}
+
+int gnf_grevnet_inverse_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const float* z_src, int64_t ld_src, float* x,
+                                      int64_t ld, int32_t D, double* sums, double* graph_out, void* ws, size_t ws_bytes,
+                                      gnf_stream_t stream) {
+    const char* const what = "gnf_grevnet_inverse_per_graph_f32";
+    g_route = 0;
+    int rc = validate_flow_call(csr, flow, ld, D, what);
+    if (rc) return rc;
+    const int64_t n = csr->n_nodes, B = csr->n_graphs;
+    // every GNN family needs the graph boundaries here, not only graph-scope attention
+    // (a batch without nodes and without graphs is the one call that has no boundaries to give)
+    if (B < 0 || B >= INT32_MAX || (n > 0 && B < 1) || ((n > 0 || B > 0) && !csr->node_offsets)) {
+        set_error("%s: needs GnfCsr.node_offsets (device int32 [n_graphs + 1]) and n_graphs >= 1; got node_offsets=%p n_graphs=%lld", what, (const void*)csr->node_offsets, (long long)B);
+        return GNF_EINVAL;
+    }
+    if (!sums || (B > 0 && !graph_out)) {
+        set_error("%s: null sums / graph_out", what);
+        return GNF_EINVAL;
+    }
+    if (z_src == x) z_src = nullptr;
+    if (z_src && ld_src < D) {
+        set_error("%s: ld_src=%lld < D=%d", what, (long long)ld_src, D);
+        return GNF_ESHAPE;
+    }
+    const int T = flow->num_timesteps;
+    if (flow->bns)
+        for (int q = 0; q < 2 * T; ++q) {
+            rc = validate_bn(&flow->bns[q], GNF_INVERSE, what, q);
+            if (rc) return rc;
+        }
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {  // nothing to transform: zeros in sums and in every graph's entries
+        GNF_HIP_TRY(hipMemsetAsync(sums, 0, 2 * sizeof(double), st));
+        if (B > 0) GNF_HIP_TRY(hipMemsetAsync(graph_out, 0, (size_t)B * 2 * sizeof(double), st));
+        return GNF_OK;
+    }
+    if (!x) {
+        set_error("%s: null x", what);
+        return GNF_EINVAL;
+    }
+    const PerGraphLayout L = per_graph_ws(n, D, flow);
+    if (!ws || ws_bytes < L.total) {
+        set_error("%s: workspace %zu < %zu bytes (gnf_inverse_per_graph_workspace_bytes)", what, ws_bytes, L.total);
+        return ws ? GNF_EWORKSPACE : GNF_EINVAL;
+    }
+    double* row_ld = reinterpret_cast<double*>((char*)ws + L.row_ld);
+    double* bn_c = reinterpret_cast<double*>((char*)ws + L.bn_c);
+    // the inference walk: nothing of g is stashed, and nothing of it crosses ranks
+    GnfFlow fl = *flow;
+    fl.attn_stash = nullptr, fl.attn_stash_bytes = 0, fl.mlp_stash = nullptr, fl.mlp_stash_bytes = 0;
+    fl.bn_allreduce = nullptr;
+    const int n_c = flow->bns ? 2 * T : 0;
+    // Everything grevnet_run checks for an inverse call (the flow, ld_src, the bijectors, x / ws, the workspace size: L.base
+    // covers its plan) has been checked above, so what follows fails only where a launch itself fails.
+    if (!z_src) {  // in place: sum z^2 of every graph's rows before the walk overwrites them
+        rc = launch_per_graph(nullptr, 0, n, nullptr, 0, x, ld, D, csr->node_offsets, B, graph_out, st, true);
+        if (rc) return rc;
+    }
+    rc = grevnet_run(csr, &fl, z_src, ld_src, x, ld, D, GNF_INVERSE, nullptr, ws, L.base, stream, row_ld, flow->bns ? bn_c : nullptr);
+    if (rc) return rc;
+    rc = launch_per_graph(row_ld, T > 0 ? 2 * T : 0, n, bn_c, n_c, z_src, ld_src, D, csr->node_offsets, B, graph_out, st, true);
+    if (rc) return rc;
+    return launch_graph_sums(graph_out, B, sums, st);
 }
 
 int gnf_gauss_sumsq_f32(const float* z, int64_t n_nodes, int32_t D, int64_t ld, double* out,

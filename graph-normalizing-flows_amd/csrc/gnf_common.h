@@ -90,10 +90,11 @@ struct HalfStep {
     // inverse pass, the same idea: the bijector behind the PREVIOUS half-step of the walk, applied where this one reads the
     // half it rewrites (moving statistics: no moments to gather), or NULL
     const GnfBatchNorm* bnu_inv = nullptr;
-    // per-graph log-likelihoods (gnf_grevnet_per_graph_f32, forward only): this half-step's slot of the per-row log-det
-    // buffer - row_logdet[r] = sum_j s[r, j] in fp64, n_nodes values, written (not accumulated) by the workgroup that owns
-    // the row.  Not NULL selects the ROWLD instance of whichever epilogue kernel runs the half-step; NULL launches exactly
-    // the instances of a call without it.  bnc_c: with the bijector on load (bnc), where its per-node log-det term c goes.
+    // per-graph log-likelihoods (gnf_grevnet_per_graph_f32, gnf_grevnet_inverse_per_graph_f32): this half-step's slot of the
+    // per-row log-det buffer - row_logdet[r] = + sum_j s[r, j] of the s the coupling used (either direction) in fp64, n_nodes
+    // values, written (not accumulated) by the workgroup that owns the row.  Not NULL selects the ROWLD instance of whichever
+    // epilogue kernel runs the half-step; NULL launches exactly the instances of a call without it.  bnc_c: forward with the
+    // bijector on load (bnc), where its per-node log-det term c goes.
     double* row_logdet = nullptr;
     double* bnc_c = nullptr;
 };
@@ -143,6 +144,10 @@ struct WorkspacePlan {
 WorkspacePlan plan_workspace(int64_t n_nodes, int32_t H, const GnfMlp* net, int32_t combine,
                              int64_t n_halfsteps);
 
+// gnf_last_route: the GNF_ROUTE_* bits of the calling thread's last whole-flow call (host bookkeeping, gnf_abi.hip)
+extern thread_local int64_t g_route;
+inline void note_route(int64_t bits) { g_route |= bits; }
+
 // ---- launchers (each returns GNF_OK / GNF_E*) --------------------------------------------------
 bool fused_supported(const HalfStep& hs);
 bool fused_fits_lds(const GnfMlp* m);      // forward kernel, smallest shape
@@ -182,7 +187,13 @@ int launch_finalize(const double* a, int64_t na, const double* b, int64_t nb, do
 // per-graph reduction behind a forward flow (gnf_per_graph.hip): graph_out[g] = { sum over the graph's rows of the n_slots
 // per-row log-det slots (row_ld[slot * n + r]) + n_g * sum of the n_c bijector terms bn_c[], sum_rows sum_j z[r, j]^2 }
 int launch_per_graph(const double* row_ld, int n_slots, int64_t n, const double* bn_c, int n_c, const float* z, int64_t ld,
-                     int32_t D, const int32_t* node_offsets, int64_t n_graphs, double* graph_out, hipStream_t st);
+                     int32_t D, const int32_t* node_offsets, int64_t n_graphs, double* graph_out, hipStream_t st, bool inverse = false);
+// (inverse, behind an inverse flow: graph_out[g] = { n_g * sum bn_c[] - the row sums, sum z^2 of the rows of z }; row_ld == NULL
+// writes the second entry only, z == NULL the first only - the two launches around an in-place walk)
+// bn_c[2 i + half] = sum_f (0.5 log(moving_var_f + eps) - log gamma_f) of bijector (half, i): the per-node log-det term of g
+int launch_bn_inverse_terms(const GnfFlow* flow, int32_t H, double* bn_c, hipStream_t st);
+// sums[k] = sum over g of graph_out[g][k], k = 0, 1, in graph order
+int launch_graph_sums(const double* graph_out, int64_t n_graphs, double* sums, hipStream_t st);
 int launch_copy_rows(const float* src, int64_t lds_, float* dst, int64_t ldd, int64_t n, int32_t W, hipStream_t st);
 int launch_pack_mlp(const GnfMlp* mlp, float* packed, hipStream_t st);
 int64_t packed_floats(const GnfMlp* mlp);

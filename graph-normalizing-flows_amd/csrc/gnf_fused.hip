@@ -305,8 +305,9 @@ __device__ __forceinline__ int nets2_tile(int bid, int nwg) {
 // kernel's prologue and leaves the layer-0 input rows of both nets in the activation buffers - no launch boundary, no
 // trip of those rows through global memory.  Its staging area (x rows, q | v of the sender window: 149 KB at the
 // reference's head geometry) ALIASES the activation buffers; bias / reduction scratch / layer table sit behind it.
-// ROWLD (NETS = 2, forward): the coupling epilogue also leaves every row's sum_j s[r, j] in rla.row (per-graph
-// log-likelihoods, gnf_grevnet_per_graph_f32) - instances of their own, so that the plain ones carry none of it.
+// ROWLD (NETS = 2, either direction: the coupling picks its direction at run time and keeps the s it used): the coupling
+// epilogue also leaves every row's + sum_j s[r, j] in rla.row (per-graph log-likelihoods, gnf_grevnet_per_graph_f32 and
+// gnf_grevnet_inverse_per_graph_f32) - instances of their own, so that the plain ones carry none of it.
 template <int MT, int NETS, bool STASH = false, bool FRONT = false, bool FIXED = false, bool ROWLD = false>
 __global__ __launch_bounds__(kFusedThreads) void k_half_fused(const FusedArgs a, const FrontArgs fa, const RowLdArgs rla) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1290,10 +1291,11 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
     // per-graph log-likelihoods: the same shape choice, the ROWLD instance of it
     const bool rowld = hs.row_logdet != nullptr;
     const RowLdArgs rla{hs.row_logdet, hs.bnc_c};
-    if (rowld && (hs.direction != GNF_FORWARD || hs.mlp_stash)) {
-        set_error("internal: per-row log-det on an inverse half-step or beside the MLP-row stash");
+    if (rowld && hs.mlp_stash) {
+        set_error("internal: per-row log-det beside the MLP-row stash");
         return GNF_EINVAL;
     }
+    if (rowld) note_route(GNF_ROUTE_ROW_SUMS);
     if (hs.bnu_inv) {
         if (!fold || hs.direction != GNF_INVERSE) {
             set_error("internal: batch norm on load (inverse) handed to a half-step that does not run the fused attention instance");
@@ -1390,6 +1392,7 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
             }
         }
         int n_wg = 0;
+        if (s->attn && !fold) note_route(GNF_ROUTE_ATTN_PAIR);
         rc = launch_half_big(a, hs.n_nodes, big, st, &n_wg, rowld ? hs.row_logdet : nullptr);
         return rc ? rc : report(n_wg);
     }
@@ -1413,14 +1416,18 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
             a.stash_ld = L.ld_act;
             a.stash_mask = reinterpret_cast<unsigned long long*>(hs.mlp_stash + L.mask);
             a.stash_mld = L.mld;
+            note_route(GNF_ROUTE_FUSED_16 | (fold ? GNF_ROUTE_FUSED_FRONT | GNF_ROUTE_FUSED_FIXED : 0) | (s->attn && !fold ? GNF_ROUTE_ATTN_PAIR : 0));
             rc = fold ? launch_shape<1, 2, true, true, true>(a, (unsigned)tiles, front_lds, st, &fa)
                       : launch_shape<1, 2, true>(a, (unsigned)tiles, lds + (size_t)L.mask_words * sizeof(unsigned long long), st);
         } else if (MT == 1 && !fold && geo_matches<2, 16, 5, 2>(hs, a)) {
             // the reference's default MLP (in0 = H = 32, L = 256, K = 5): what a plain benchmark run is sixteen launches of
             // (both nets per wave, a barrier inside each phase; force_shape = kForceGeoParent: a net per wave, a barrier per layer)
+            note_route(GNF_ROUTE_FUSED_GEO);
             rc = opt(OPT_FORCE_SHAPE) == kForceGeoParent ? launch_geo<2, 16, 5, 2, false>(a, (unsigned)tiles, st)
                                                          : launch_geo<2, 16, 5, 2, true>(a, (unsigned)tiles, st);
         } else {
+            note_route((MT == 2 ? GNF_ROUTE_FUSED_32 : GNF_ROUTE_FUSED_16) | (fold ? GNF_ROUTE_FUSED_FRONT : 0) |
+                       (fold && attn_front_fixed_geometry(fa.d) ? GNF_ROUTE_FUSED_FIXED : 0) | (s->attn && !fold ? GNF_ROUTE_ATTN_PAIR : 0));
             rc = rowld ? launch_nets2<true>(a, MT, fold, fa, &rla, (unsigned)tiles, lds, front_lds, st)
                        : launch_nets2<false>(a, MT, fold, fa, nullptr, (unsigned)tiles, lds, front_lds, st);
         }
@@ -1431,6 +1438,7 @@ int launch_half_fused(const HalfStep& hs, float* scratch, hipStream_t st) {
         return GNF_EINVAL;
     }
     const unsigned grid = (unsigned)(8 * ((tiles + 3) / 4));  // 4 tile slots x 2 nets per group of 8 blocks
+    note_route((MT == 2 ? GNF_ROUTE_ONE_NET_32 : GNF_ROUTE_ONE_NET_16) | (s->attn ? GNF_ROUTE_ATTN_PAIR : 0));
     rc = MT == 2 ? launch_shape<2, 1>(a, grid, lds, st) : launch_shape<1, 1>(a, grid, lds, st);
     if (rc) return rc;
     if (s->attn && s->attn->layer_norm) {

@@ -289,7 +289,7 @@ __device__ __forceinline__ void big_chunk_thin(float* __restrict__ act, const BC
 }
 
 // SPLIT: the launch has split row tiles (big_seg_kind != 0 somewhere); the plain instance carries none of that code
-// ROWLD (forward): the workgroup also leaves sum_j s[r, j] of every row it couples in row_ld (per-graph log-likelihoods)
+// ROWLD (either direction): the workgroup also leaves + sum_j s[r, j] of every row it couples in row_ld (per-graph log-likelihoods)
 template <bool SPLIT, bool ROWLD = false>
 __global__ __launch_bounds__(kBigThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_half_big(const FusedArgs a, double* __restrict__ row_ld) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -770,6 +770,7 @@ int launch_half_big(FusedArgs& a, int64_t n_nodes, int cap, hipStream_t st, int*
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 84 * 1024)));
     bool any_split = false;
     for (int k = 0; k < 6; ++k) any_split = any_split || (a.big_seg_n[k] > 0 && a.big_seg_kind[k] != 0);
+    note_route(any_split ? GNF_ROUTE_BIG_SPLIT : GNF_ROUTE_BIG);
     if (row_logdet) {
         GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_half_big<false, true>),
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 84 * 1024));

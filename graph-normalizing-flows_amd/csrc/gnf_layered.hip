@@ -273,7 +273,7 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh) {
     return tot;  // valid on thread 0
 }
 
-// ROWLD instances of the two coupling kernels (per-graph log-likelihoods): sum_j s[r, j] of the rows [ra, rb) this workgroup
+// ROWLD instances of the two coupling kernels (per-graph log-likelihoods, forward and inverse): + sum_j s[r, j] of the rows [ra, rb) this workgroup
 // owns, fp64, a wave per row with the lanes strided over the features (fixed order).  s is formed exactly as the coupling
 // loop forms it - bias + the slabs in slab order, + the residual row - from buffers the launch only reads.
 __device__ __forceinline__ void coupling_rows_logdet(const float* __restrict__ s, int64_t lds_, const SlabSrc& sl,
@@ -724,6 +724,7 @@ int launch_half_layer_norm(const HalfStep& hs, float* sbuf, float* tbuf, const f
     a.ldx = hs.ld;
     a.n = hs.n_nodes;
     a.W = hs.H;
+    note_route(GNF_ROUTE_LAYER_NORM);
     return launch_layer_norm(a, 2, st);
 }
 
@@ -731,6 +732,7 @@ int launch_half_layered(const HalfStep& hs, float* scratch, hipStream_t st) {
     const int64_t n = hs.n_nodes;
     *hs.n_partials = 0;
     if (n == 0) return GNF_OK;
+    note_route(GNF_ROUTE_LAYERED | (hs.s_net->attn ? GNF_ROUTE_ATTN_PAIR : 0));
     const int H = hs.H;
     const int in0 = hs.s_net->dims[0];
     const int lmax = hidden_max(hs.s_net, hs.t_net);
@@ -817,8 +819,9 @@ int launch_coupling(const float* sbuf, const float* tbuf, const HalfStep& hs, co
     SlabSrc sl;
     memset(&sl, 0, sizeof(sl));
     if (slabs) sl = *slabs;
-    // per-graph log-likelihoods (forward): the ROWLD instance of whichever of the two kernels the launch takes anyway
-    const bool rowld = hs.row_logdet != nullptr && hs.direction == GNF_FORWARD;
+    // per-graph log-likelihoods (either direction): the ROWLD instance of whichever of the two kernels the launch takes anyway
+    const bool rowld = hs.row_logdet != nullptr;
+    if (rowld) note_route(GNF_ROUTE_ROW_SUMS);
     if (hs.bn_part && hs.n_bn && hs.direction == GNF_FORWARD && H <= 256 && n > 0) {
         // (16 rows per workgroup: (n + 15) / 16 partial rows - the caller sized both partial buffers for exactly that)
         const int rows = 16;
@@ -830,6 +833,7 @@ int launch_coupling(const float* sbuf, const float* tbuf, const HalfStep& hs, co
             hipLaunchKernelGGL(k_coupling_rows<false>, dim3((unsigned)blocks), dim3(256), 0, st, sbuf, tbuf, (int64_t)H, hs.x_upd, hs.ld, n, H,
                                rows, hs.partials, xres, hs.bn_part, sl, (double*)nullptr);
         GNF_LAUNCH_CHECK("k_coupling_rows");
+        note_route(GNF_ROUTE_COUPLING_ROWS);
         *hs.n_partials = (int32_t)blocks;
         *hs.n_bn = (int32_t)blocks;
         return GNF_OK;
@@ -852,6 +856,7 @@ int launch_coupling(const float* sbuf, const float* tbuf, const HalfStep& hs, co
     }
 #undef GNF_COUPLING
     GNF_LAUNCH_CHECK("k_coupling");
+    note_route(GNF_ROUTE_COUPLING);
     *hs.n_partials = (int32_t)blocks;
     return GNF_OK;
 }

@@ -83,4 +83,22 @@ struct MlpStashLayout {
 };
 MlpStashLayout mlp_stash_layout(const GnfMlp* net, int64_t n, int32_t H);  // gnf_fused.hip
 
+// ---- workspace of the per-graph entry points, forward and inverse (byte offsets) ---------------------------------
+// the plain call's workspace (gnf_workspace_bytes, 256-aligned) | row sums fp64 [2T][n] | bijector terms fp64 [2T].
+// sum z^2 of the inverse call's source rows needs no room: the reduction reads z_src, or (in place) a launch in front of
+// the walk leaves each graph's value in its graph_out entry.
+struct PerGraphLayout {
+    size_t base, row_ld, bn_c, total;
+    int slots;  // 2T (2 for a flow without timesteps)
+};
+inline PerGraphLayout per_graph_layout(size_t plain_bytes, int64_t n, int32_t T) {
+    PerGraphLayout L;
+    L.slots = 2 * (T > 0 ? T : 1);
+    L.base = (plain_bytes + 255) / 256 * 256;
+    L.row_ld = L.base;
+    L.bn_c = L.row_ld + (size_t)L.slots * (size_t)n * sizeof(double);
+    L.total = L.bn_c + (size_t)L.slots * sizeof(double);
+    return L;
+}
+
 }  // namespace gnf

@@ -124,6 +124,37 @@ def sample(grevnet, graph, generator=None):
     return {"sample": z, "sample_log_prob": sample_log_prob, "grevnet_top": top, "grevnet_top_nodes": top.nodes}
 
 
+def sample_per_graph(grevnet, graph, generator=None):
+    """sample, with the flow's own density of every graph it generates from the same inverse pass (GRevNet.g_per_graph):
+    what sample returns (same generator state: the same z, the same x bit for bit) plus [B] device fp64 tensors
+      log_det_jacobian[g] = log|det dg/dz| of graph g's block, log_prob_zs[g] = -0.5 * sum_{n in g} |z_n|^2 - n_g * D/2 * ln(2 pi)
+      (sum z^2 from the library call), log_prob_xs = log_prob_zs - log_det_jacobian, num_nodes[g],
+      log_prob_xs_per_node[g] (an empty graph: 0, not NaN).
+    The bijectors of g use the moving statistics: a graph's values do not depend on the rest of the batch."""
+    n, d = graph.nodes.shape
+    z = torch.randn(n, d, dtype=torch.float32, device=graph.nodes.device, generator=generator)
+    sample_log_prob = -0.5 * (z.double() ** 2).sum(dim=1) - 0.5 * d * LN_2PI
+    out = {"sample": z, "sample_log_prob": sample_log_prob}
+    out.update(inverse_per_graph(grevnet, graph.replace(nodes=z)))
+    return out
+
+
+PER_GRAPH_KEYS = ("log_det_jacobian", "log_prob_zs", "log_prob_xs", "num_nodes", "log_prob_xs_per_node")
+
+
+def inverse_per_graph(grevnet, z_graph):
+    """x = g(z) of given latent rows with the five per-graph tensors of sample_per_graph (PER_GRAPH_KEYS) from the same
+    pass, plus "grevnet_top" / "grevnet_top_nodes" as sample names them."""
+    top, logdet = grevnet.g_per_graph(z_graph)
+    gs = grevnet.last_graph_sums
+    d = z_graph.nodes.shape[1]
+    num = z_graph.n_node.to(device=gs.device, dtype=torch.float64)
+    log_prob_zs = -0.5 * gs[:, 1] - 0.5 * d * LN_2PI * num
+    log_prob_xs = log_prob_zs - logdet
+    return {"grevnet_top": top, "grevnet_top_nodes": top.nodes, "log_det_jacobian": logdet, "log_prob_zs": log_prob_zs,
+            "log_prob_xs": log_prob_xs, "num_nodes": num, "log_prob_xs_per_node": log_prob_xs / torch.clamp(num, min=1.0)}
+
+
 def scaled_hacky_sigmoid_l2(*_a, **_k):
     """Token for the distance function of loss.py:45-53 (the only one pred_adj is used with on this
     path); the arithmetic runs inside gnf_pred_adj_f32."""
@@ -264,13 +295,15 @@ def decode_graphs(gnn_output, threshold=0.5, self_loops=False, edge_capacity=Non
 
 
 def generate_graphs(grevnet, shell_graph, generator=None, threshold=0.5, self_loops=False,
-                    distance_fn=scaled_hacky_sigmoid_l2):
+                    distance_fn=scaled_hacky_sigmoid_l2, log_prob=False):
     """generate_graphs.py:57-84 / train_grevnet_with_data.py:526-540 in one call: sample z ~ N(0, I) on shell_graph's
     topology, run the flow in reverse, decode the embeddings to graphs (decode_graphs, exact-size mode).  Returns what
     decode_graphs returns, what sample returns, and "sample_log_prob_per_graph": the mean of sample_log_prob over each
     graph's nodes (generate_graphs.py:76; device fp64 [B], 0 for a graph without nodes).  distance_fn: the function the
-    encoder whose embeddings the flow models was trained against (decode_graphs' argument)."""
-    out = sample(grevnet, shell_graph, generator=generator)
+    encoder whose embeddings the flow models was trained against (decode_graphs' argument).  log_prob=True samples
+    through sample_per_graph instead - the same graphs, edge lists and sample_log_prob_per_graph for the same generator
+    state - and adds its five [B] tensors (PER_GRAPH_KEYS): the flow's own density of each generated graph."""
+    out = (sample_per_graph if log_prob else sample)(grevnet, shell_graph, generator=generator)
     top = out["grevnet_top"]
     res = decode_graphs(top, threshold=threshold, self_loops=self_loops, distance_fn=distance_fn)
     dev = top.nodes.device

@@ -658,7 +658,7 @@ class GRevNet:
         self._cache_fast = None  # (device, hdim, fused, sync world, mutation epoch) the cache was last validated at
         self.fused = True        # False: hide the packed weights -> the layered (generic) kernels run
         self.last_sums = None    # device fp64 [2]: log_det_jacobian, sum(z^2) of the last f()
-        self.last_graph_sums = None   # device fp64 [B, 2]: the same two per graph, of the last f_per_graph()
+        self.last_graph_sums = None   # device fp64 [B, 2]: the same two per graph, of the last f_per_graph() / g_per_graph()
 
     # ---- parameter plumbing ------------------------------------------------------------------
     def _gnns(self, kind):
@@ -904,6 +904,41 @@ class GRevNet:
         """gnn.py:343-373: latent -> data (sampling direction)."""
         x, _ = self._run(z, _abi.GNF_INVERSE)
         return z.replace(nodes=x)
+
+    def g_per_graph(self, z, sums_out=None):
+        """g with the flow's own log-det of every graph it generates: ONE batched inverse pass
+        (gnf_grevnet_inverse_per_graph_f32), the same x as g, bit for bit.  Returns (GraphsTuple with nodes = x, logdet_g [B]
+        device fp64: log|det dg/dz| of each graph's block); `last_graph_sums` holds the [B, 2] buffer (logdet_g, sum z^2 of
+        graph g's INPUT rows), `last_sums` their sums over the graphs, [2].  The bijectors of g use the moving statistics, so
+        the graphs of a batch are independent even with batch norm: log p(x_g) = log N(z_g) - logdet_g[g]."""
+        lib = _abi.lib()
+        nodes = z.nodes
+        if nodes.device.type != "cuda":
+            raise _abi.GnfError("GRevNet runs on a HIP device only (no CPU path)")
+        if nodes.ndim != 2 or nodes.shape[1] % 2:
+            raise ValueError(f"nodes must be [N, D] with even D (tf.split, gnn.py:306); got {tuple(nodes.shape)}")
+        n, d = nodes.shape
+        dev = nodes.device
+        b = int(z.n_node.shape[0])
+        src = nodes.to(torch.float32)
+        if n > 0 and (src.stride(1) != 1 or src.stride(0) < d):
+            src = src.contiguous()
+        out = torch.empty((n, d), dtype=torch.float32, device=dev)
+        flow = self._flow(d // 2, dev)
+        csr = csr_desc(z, csr_of(z), True)   # every GNN family: the per-graph reduction reads the graph boundaries
+        with torch.cuda.device(dev):
+            ws_bytes = lib.gnf_inverse_per_graph_workspace_bytes(n, b, d, C.byref(flow))
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+        sums = sums_out if sums_out is not None else torch.zeros(2, dtype=torch.float64, device=dev)
+        graph_sums = torch.zeros((b, 2), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _abi.check(lib.gnf_grevnet_inverse_per_graph_f32(C.byref(csr), C.byref(flow), _abi.ptr(src), src.stride(0) if n else d,
+                                                             _abi.ptr(out), d, d, _abi.ptr(sums), _abi.ptr(graph_sums),
+                                                             _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                       "gnf_grevnet_inverse_per_graph_f32")
+        self.last_sums = sums
+        self.last_graph_sums = graph_sums
+        return z.replace(nodes=out), graph_sums[:, 0]
 
     def log_prob(self, x):
         """gnn.py:375-377 with the prior the drivers use (standard normal, run_grevnet.py:292-294)."""

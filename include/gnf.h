@@ -518,6 +518,8 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 #include "gnf_timestep_gnn.h"
 /* Added within ABI v10: the encoder's training forward (with a stash) and its backward pass (gnf_timestep_gnn_train.h) - likewise. */
 #include "gnf_timestep_gnn_train.h"
+/* Added within ABI v10: per-graph likelihood of generated graphs from the inverse pass (gnf_inverse_per_graph.h) - likewise. */
+#include "gnf_inverse_per_graph.h"
 
 #ifdef __cplusplus
 }
