@@ -227,6 +227,14 @@ _INVERSE_PER_GRAPH_SIGNATURES = {
                                                     C.c_void_p]),
     "gnf_last_route": (C.c_int64, []),
 }
+
+# include/gnf_graph_spectra.h (included by gnf.h, added within ABI v10): normalised-Laplacian eigenvalues of a batch of graphs and
+# their per-graph histograms.  A table of its own for the same reason.
+_SPECTRA_SIGNATURES = {
+    "gnf_graph_spectra_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_graph_spectra": (C.c_int, [C.POINTER(GnfCsr), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -239,6 +247,7 @@ ADJ_LOSS_SYMBOLS = tuple(_ADJ_LOSS_SIGNATURES)
 ENCODER_SYMBOLS = tuple(_ENCODER_SIGNATURES)
 ENCODER_TRAIN_SYMBOLS = tuple(_ENCODER_TRAIN_SIGNATURES)
 DISTANCE_SYMBOLS = tuple(_DISTANCE_SIGNATURES)
+SPECTRA_SYMBOLS = tuple(_SPECTRA_SIGNATURES)
 
 _lib = None
 
@@ -254,7 +263,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES,
                                   **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
-                                  **_INVERSE_PER_GRAPH_SIGNATURES}.items():
+                                  **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

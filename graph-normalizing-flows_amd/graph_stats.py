@@ -7,6 +7,9 @@ hist_mmd (gnf_hist_mmd_f64) reduces two histogram sets to one MMD^2, evaluate_ge
 The third statistic of that evaluation, orbit counts: graph_orbits (gnf_graph_orbits) counts the 15 node orbits of the
 graphlets on 2, 3 and 4 nodes, orbit_mmd (gnf_vec_mmd_i64) is the MMD^2 of two sets of per-graph mean orbit vectors under a
 Gaussian kernel; evaluate_generated(..., orbits=True) adds it.
+The fourth statistic, the one reported since GRAN: graph_spectra (gnf_graph_spectra) computes the eigenvalues of every
+graph's normalised Laplacian and their per-graph histogram, spectral_mmd is hist_mmd on those histograms under the
+total-variation kernel; evaluate_generated(..., spectral=True) adds it.
 Every graph is read as undirected and simple (self loops ignored, duplicates once, one direction is enough).  HIP only:
 CPU tensors raise GnfError.
 """
@@ -22,6 +25,10 @@ STATS_KEYS = ("degree", "triangles", "clustering", "degree_hist", "clustering_hi
 ORBIT_MAX_NODES_PER_GRAPH = 8192   # gnf_graph_orbits: the cost per node grows with n_g + d_i d_mean
 N_ORBITS = 15
 ORBIT_KEYS = ("orbits", "orbit_sums", "orbit_mean", "n_node")
+SPECTRA_MAX_NODES_PER_GRAPH = 2048   # gnf_graph_spectra: a dense eigenvalue solver, n^3 work per graph
+SPECTRA_LDS_NODES = 139              # up to here a graph's matrix lives in LDS, above it in the workspace
+SPECTRA_SLOTS = 256                  # matrix slots of the workspace route
+SPECTRA_KEYS = ("eigenvalues", "spectral_hist", "n_node")
 
 
 def _node_bound(graph, max_nodes_per_graph, n_node_host, limit):
@@ -203,12 +210,70 @@ def orbit_mmd(orbits_a, orbits_b, sigma=30.0):
     return out5[0] / (out5[3] * out5[3]) + out5[1] / (out5[4] * out5[4]) - 2.0 * out5[2] / (out5[3] * out5[4])
 
 
-def evaluate_generated(generated, reference, orbits=False):
+def graph_spectra(graph, max_nodes_per_graph=None, n_node_host=None, bins=200, lo=-1e-5, hi=2.0):
+    """Normalised-Laplacian spectrum of every graph of a GraphsTuple, as a dict of device tensors:
+      "eigenvalues"    float64 [N]: the eigenvalues of graph g, ascending, in the rows of its nodes.  L_ii = 1 (0 for an isolated
+                       node), L_ij = -1 / sqrt(d_i d_j) for an edge: an isolated node contributes an eigenvalue 0
+      "spectral_hist"  int32 [B, bins]: eigenvalue x counts in bin clamp(floor((x - lo) * bins / (hi - lo)), 0, bins - 1) - values
+                       outside [lo, hi) land in the first / last bin, none is dropped; a row sums to n_node
+      "n_node"         int32 [B]
+    The defaults (200 bins over [-1e-5, 2]) are GRAN's setting.  The CSR comes from graphs.csr_of: on the result of
+    decode_graphs / generate_graphs no gnf_build_csr runs.  As for graph_stats, with max_nodes_per_graph (any upper bound on
+    n_node, at most 2048) or n_node_host nothing is copied to the host and nothing synchronises, so the call can be captured;
+    otherwise n_node is read once.  Up to 139 nodes per graph the matrices live in LDS, above that in a workspace of
+    min(B, 256) * max_nodes_per_graph^2 doubles."""
+    from .graphs import csr_desc, csr_of
+    lib = _abi.lib()
+    dev = graph.senders.device
+    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
+        raise _abi.GnfError("graph_spectra runs on a HIP device only (no CPU path)")
+    n = int(graph.nodes.shape[0])
+    b = int(graph.n_node.shape[0])
+    bins = int(bins)
+    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, SPECTRA_MAX_NODES_PER_GRAPH)
+    if bins < 1 or not float(hi) > float(lo):
+        raise ValueError(f"bins={bins} lo={lo} hi={hi}")
+    csr = csr_of(graph)
+    desc = csr_desc(graph, csr, node_offsets=True)
+    out = {"eigenvalues": torch.empty(n, dtype=torch.float64, device=dev),
+           "spectral_hist": torch.empty((b, bins), dtype=torch.int32, device=dev)}
+    ws_bytes = lib.gnf_graph_spectra_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_graph_spectra(C.byref(desc), cap, _abi.ptr(out["eigenvalues"]), _abi.ptr(out["spectral_hist"]), bins,
+                                         float(lo), float(hi), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                   "gnf_graph_spectra")
+    out["n_node"] = graph.n_node.to(torch.int32)
+    return out
+
+
+def spectral_mmd(a, b, sigma=1.0):
+    """MMD^2 of the eigenvalue histograms of two sets of graphs - two results of graph_spectra, or two int32 [rows, bins]
+    histogram tensors on the device - under the Gaussian kernel on the total variation of the normalised rows, sigma = 1 as
+    in GRAN's evaluation: the estimator of hist_mmd(..., "gaussian_tv", sigma, 1.0) on the same entry point
+    (gnf_hist_mmd_f64), a 0-d float64 device tensor.  Graphs without nodes are left out.  Two identical sets give exactly 0:
+    gnf_hist_mmd_f64 adds a same-set block up from its upper triangle and the cross block row by row, so its three sums of
+    two identical sets agree only to rounding; here every block is read off as the CROSS block of a call of its own - (a, a),
+    (b, b), (a, b) - three sums formed in one order, equal bit for bit when the sets are.  Raises ValueError when a set has
+    no other row: reading the two counts is the call's only copy to the host."""
+    ha, hb = (x["spectral_hist"] if isinstance(x, dict) else x for x in (a, b))
+    ab = _hist_mmd_sums(ha, hb, "gaussian_tv", sigma, 1.0)
+    cnt_a, cnt_b = ab[3:5].tolist()
+    if cnt_a < 1 or cnt_b < 1:
+        raise ValueError(f"spectral_mmd: {int(cnt_a)} / {int(cnt_b)} non-empty histograms in the two sets; both need one")
+    aa = _hist_mmd_sums(ha, ha, "gaussian_tv", sigma, 1.0)
+    hb = hb.to(ha.device)
+    bb = _hist_mmd_sums(hb, hb, "gaussian_tv", sigma, 1.0)
+    return aa[2] / (ab[3] * ab[3]) + bb[2] / (ab[4] * ab[4]) - 2.0 * ab[2] / (ab[3] * ab[4])
+
+
+def evaluate_generated(generated, reference, orbits=False, spectral=False):
     """Degree and clustering MMD^2 of a generated batch against a reference batch: two GraphsTuples, or two results of
     graph_stats (clustering_hist with 100 bins).  Degree: EMD kernel, sigma 1, distance_scaling 1.  Clustering: 100 bins,
     EMD kernel, sigma 0.1, distance_scaling 100.  Returns {"degree_mmd", "clustering_mmd"}, 0-d float64 device tensors.
     orbits=True adds "orbit_mmd" (orbit_mmd, sigma 30); dicts passed instead of GraphsTuples must then also hold the
-    result of graph_orbits ({**graph_stats(g), **graph_orbits(g)})."""
+    result of graph_orbits ({**graph_stats(g), **graph_orbits(g)}).  spectral=True adds "spectral_mmd" (spectral_mmd on
+    graph_spectra's default histograms, sigma 1); dicts must then also hold "spectral_hist"."""
     inputs = (generated, reference)
     stats = [s if isinstance(s, dict) else graph_stats(s, clustering_bins=100) for s in inputs]
     for s in stats:
@@ -222,4 +287,10 @@ def evaluate_generated(generated, reference, orbits=False):
                 raise ValueError("evaluate_generated(orbits=True) on a dict needs the result of graph_orbits in it")
         sets = [s if isinstance(s, dict) else graph_orbits(s) for s in inputs]
         out["orbit_mmd"] = orbit_mmd(sets[0], sets[1], 30.0)
+    if spectral:
+        for s in inputs:
+            if isinstance(s, dict) and "spectral_hist" not in s:
+                raise ValueError("evaluate_generated(spectral=True) on a dict needs the result of graph_spectra in it")
+        sets = [s if isinstance(s, dict) else graph_spectra(s) for s in inputs]
+        out["spectral_mmd"] = spectral_mmd(sets[0], sets[1], 1.0)
     return out

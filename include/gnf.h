@@ -520,6 +520,8 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 #include "gnf_timestep_gnn_train.h"
 /* Added within ABI v10: per-graph likelihood of generated graphs from the inverse pass (gnf_inverse_per_graph.h) - likewise. */
 #include "gnf_inverse_per_graph.h"
+/* Added within ABI v10: normalised-Laplacian eigenvalues of a batch of graphs and their histograms (gnf_graph_spectra.h) - likewise. */
+#include "gnf_graph_spectra.h"
 
 #ifdef __cplusplus
 }
