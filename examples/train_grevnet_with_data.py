@@ -85,6 +85,8 @@ def main():
     ap.add_argument("--clip_gradient_norm", type=float, default=10.0)
     ap.add_argument("--random_seed", type=int, default=12345)
     ap.add_argument("--sample_log_prob_xs", action="store_true")   # also log the flow's own density of each generated graph
+    # reduce every generated graph to its largest connected component / its nodes with a neighbour (graph_stats.keep_subgraphs)
+    ap.add_argument("--keep_generated", default="all", choices=["all", "largest_component", "non_isolated"])
     F = ap.parse_args()
     random.seed(F.random_seed)
     np.random.seed(F.random_seed)
@@ -156,11 +158,18 @@ def main():
     n_node = np.asarray(random.sample(list(data.n_node) * F.sample_size, F.sample_size), np.int32)
     shell = D.transform_example(np.zeros((int(n_node.sum()), F.node_embedding_dim), np.float32), n_node, dev)
     # sample -> flow in reverse -> edge lists + CSR, all on the device (--sample_log_prob_xs: log p(x) of each graph from the same pass)
-    out = generate_graphs(grevnet, shell, log_prob=F.sample_log_prob_xs, **decode_with)
+    keep = None if F.keep_generated == "all" else F.keep_generated
+    out = generate_graphs(grevnet, shell, log_prob=F.sample_log_prob_xs, keep=keep, **decode_with)
     rows = torch.stack([out["graph"].n_node.to(dev, torch.float64), out["graph"].n_edge.to(torch.float64),
                         out["sample_log_prob_per_graph"]]).cpu().numpy()          # the one device-to-host copy of the tail
     for i, (nodes, edges, mean_lp) in enumerate(rows.T):
         print(f"sampled graph {i}: {int(nodes)} nodes, {int(edges) // 2} edges, mean sample log-prob {mean_lp:.2f}")
+    if keep is not None:
+        from gnf_amd.graph_stats import graph_components
+        parts = graph_components(out["graph"])["n_components"].to(torch.float64).mean()
+        share = float(out["kept"]["total_nodes"]) / max(int(n_node.sum()), 1)
+        print(f"generated graphs: mean n_components {float(parts):.2f}, --keep_generated {keep} keeps {share:.1%} of the nodes, "
+              f"{int(out['kept']['total_edges']) // 2} edges")
     if F.sample_log_prob_xs:
         for i, lp in enumerate(out["log_prob_xs_per_node"].cpu().numpy()):
             print(f"sampled graph {i}: log_prob_xs_per_node {lp:.4f}")

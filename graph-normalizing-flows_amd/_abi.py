@@ -16,6 +16,7 @@ GNF_ACT_RELU, GNF_ACT_LEAKY_RELU = 0, 1
 GNF_FORWARD, GNF_INVERSE = 0, 1
 GNF_ATTN_EDGES, GNF_ATTN_GRAPH = 0, 1   # GnfAttn.scope (ABI v10)
 GNF_MMD_GAUSSIAN_EMD, GNF_MMD_GAUSSIAN_TV = 0, 1   # gnf_hist_mmd_f64 kernel
+GNF_KEEP_LARGEST_COMPONENT, GNF_KEEP_NON_ISOLATED, GNF_KEEP_MASK = 0, 1, 2   # gnf_graph_subgraph_count rule
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNF_LIB_PATH: developer override (a library built from another checkout, for A/B runs); still a HIP build
@@ -235,6 +236,19 @@ _SPECTRA_SIGNATURES = {
     "gnf_graph_spectra": (C.c_int, [C.POINTER(GnfCsr), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+
+# include/gnf_graph_components.h (included by gnf.h, added within ABI v10): connected components of a batch of graphs and the
+# extraction of node-induced subgraph batches.  A table of its own for the same reason.
+_COMPONENT_SIGNATURES = {
+    "gnf_graph_components_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_graph_components": (C.c_int, [C.POINTER(GnfCsr), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_graph_subgraph_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_graph_subgraph_count": (C.c_int, [C.POINTER(GnfCsr), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_graph_subgraph_fill": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -248,6 +262,7 @@ ENCODER_SYMBOLS = tuple(_ENCODER_SIGNATURES)
 ENCODER_TRAIN_SYMBOLS = tuple(_ENCODER_TRAIN_SIGNATURES)
 DISTANCE_SYMBOLS = tuple(_DISTANCE_SIGNATURES)
 SPECTRA_SYMBOLS = tuple(_SPECTRA_SIGNATURES)
+COMPONENT_SYMBOLS = tuple(_COMPONENT_SIGNATURES)
 
 _lib = None
 
@@ -263,7 +278,8 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES,
                                   **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
-                                  **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES}.items():
+                                  **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
+                                  **_COMPONENT_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

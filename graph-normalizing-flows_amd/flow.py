@@ -295,14 +295,17 @@ def decode_graphs(gnn_output, threshold=0.5, self_loops=False, edge_capacity=Non
 
 
 def generate_graphs(grevnet, shell_graph, generator=None, threshold=0.5, self_loops=False,
-                    distance_fn=scaled_hacky_sigmoid_l2, log_prob=False):
+                    distance_fn=scaled_hacky_sigmoid_l2, log_prob=False, keep=None):
     """generate_graphs.py:57-84 / train_grevnet_with_data.py:526-540 in one call: sample z ~ N(0, I) on shell_graph's
     topology, run the flow in reverse, decode the embeddings to graphs (decode_graphs, exact-size mode).  Returns what
     decode_graphs returns, what sample returns, and "sample_log_prob_per_graph": the mean of sample_log_prob over each
     graph's nodes (generate_graphs.py:76; device fp64 [B], 0 for a graph without nodes).  distance_fn: the function the
     encoder whose embeddings the flow models was trained against (decode_graphs' argument).  log_prob=True samples
     through sample_per_graph instead - the same graphs, edge lists and sample_log_prob_per_graph for the same generator
-    state - and adds its five [B] tensors (PER_GRAPH_KEYS): the flow's own density of each generated graph."""
+    state - and adds its five [B] tensors (PER_GRAPH_KEYS): the flow's own density of each generated graph.
+    keep ("largest_component", "non_isolated" or a mask: graph_stats.keep_subgraphs' argument) adds "kept", the result of
+    keep_subgraphs(result["graph"], keep, self_loops=self_loops) - the generated batch reduced to the nodes to keep, all B
+    graphs still in place; every other key is what a call without it returns.  None launches nothing more."""
     out = (sample_per_graph if log_prob else sample)(grevnet, shell_graph, generator=generator)
     top = out["grevnet_top"]
     res = decode_graphs(top, threshold=threshold, self_loops=self_loops, distance_fn=distance_fn)
@@ -313,4 +316,7 @@ def generate_graphs(grevnet, shell_graph, generator=None, threshold=0.5, self_lo
     sums = torch.zeros(b, dtype=torch.float64, device=dev).index_add_(0, gid, out["sample_log_prob"])
     res.update(out)
     res["sample_log_prob_per_graph"] = sums / torch.clamp(nn, min=1).to(torch.float64)
+    if keep is not None:
+        from .graph_stats import keep_subgraphs
+        res["kept"] = keep_subgraphs(res["graph"], keep, self_loops=self_loops)
     return res

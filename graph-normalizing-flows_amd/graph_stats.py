@@ -10,6 +10,10 @@ Gaussian kernel; evaluate_generated(..., orbits=True) adds it.
 The fourth statistic, the one reported since GRAN: graph_spectra (gnf_graph_spectra) computes the eigenvalues of every
 graph's normalised Laplacian and their per-graph histogram, spectral_mmd is hist_mmd on those histograms under the
 total-variation kernel; evaluate_generated(..., spectral=True) adds it.
+Before any of them: graph_components (gnf_graph_components) says whether a generated graph is one graph at all - `pred_adj >
+threshold` decides every pair of nodes on its own - and keep_subgraphs (gnf_graph_subgraph_count / _fill) reduces a batch to
+its largest components, its non-isolated nodes or a mask, as a batch everything here and the flow accept as it is;
+evaluate_generated(..., keep=...) does that to the generated batch first.
 Every graph is read as undirected and simple (self loops ignored, duplicates once, one direction is enough).  HIP only:
 CPU tensors raise GnfError.
 """
@@ -29,6 +33,8 @@ SPECTRA_MAX_NODES_PER_GRAPH = 2048   # gnf_graph_spectra: a dense eigenvalue sol
 SPECTRA_LDS_NODES = 139              # up to here a graph's matrix lives in LDS, above it in the workspace
 SPECTRA_SLOTS = 256                  # matrix slots of the workspace route
 SPECTRA_KEYS = ("eigenvalues", "spectral_hist", "n_node")
+COMPONENT_KEYS = ("component", "component_size", "n_components", "largest_component_size", "largest_component_root", "n_isolated")
+_KEEP_RULES = {"largest_component": _abi.GNF_KEEP_LARGEST_COMPONENT, "non_isolated": _abi.GNF_KEEP_NON_ISOLATED}
 
 
 def _node_bound(graph, max_nodes_per_graph, n_node_host, limit):
@@ -267,13 +273,123 @@ def spectral_mmd(a, b, sigma=1.0):
     return aa[2] / (ab[3] * ab[3]) + bb[2] / (ab[4] * ab[4]) - 2.0 * ab[2] / (ab[3] * ab[4])
 
 
-def evaluate_generated(generated, reference, orbits=False, spectral=False):
+def graph_components(graph, max_nodes_per_graph=None, n_node_host=None):
+    """Connected components of every graph of a GraphsTuple (gnf_graph_components), as a dict of int32 device tensors:
+      "component"               [N]: the batch-wide row of the smallest node of each node's component - canonical, whatever
+                                the search order; a root is its own label
+      "component_size"          [N]: the number of nodes of that component
+      "n_components"            [B]: an isolated node is a component of size 1, a graph without nodes has 0
+      "largest_component_size"  [B]
+      "largest_component_root"  [B]: among the largest components the one with the smallest root; -1 for a graph without nodes
+      "n_isolated"              [B]: nodes of degree 0
+    The CSR comes from graphs.csr_of: on the result of decode_graphs / generate_graphs no gnf_build_csr runs.  As for
+    graph_stats, with max_nodes_per_graph (any upper bound on n_node, at most 65536) or n_node_host nothing is copied to the
+    host and nothing synchronises, so the call can be captured; otherwise n_node is read once.  A level-synchronous search:
+    one pair of workgroup barriers per level, a path on n nodes costs up to n levels."""
+    from .graphs import csr_desc, csr_of
+    lib = _abi.lib()
+    dev = graph.senders.device
+    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
+        raise _abi.GnfError("graph_components runs on a HIP device only (no CPU path)")
+    n = int(graph.nodes.shape[0])
+    b = int(graph.n_node.shape[0])
+    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
+    csr = csr_of(graph)
+    desc = csr_desc(graph, csr, node_offsets=True)
+    out = {k: torch.empty(n if k in COMPONENT_KEYS[:2] else b, dtype=torch.int32, device=dev) for k in COMPONENT_KEYS}
+    ws_bytes = lib.gnf_graph_components_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_graph_components(C.byref(desc), cap, *(_abi.ptr(out[k]) for k in COMPONENT_KEYS), _abi.ptr(ws),
+                                            ws_bytes, _abi.stream_ptr(dev)), "gnf_graph_components")
+    return out
+
+
+def keep_subgraphs(graph, keep="largest_component", self_loops=False, max_nodes_per_graph=None, n_node_host=None):
+    """The batch that is left when only some nodes of every graph are kept (gnf_graph_subgraph_count / _fill): the subgraph of
+    the simple undirected graph that the kept nodes induce, in decode_graphs' convention.
+      keep   "largest_component" (ties: the component with the smallest node), "non_isolated" (degree > 0), or a bool /
+             uint8 tensor [N], nonzero = keep
+    Returns a dict:
+      "graph"        GraphsTuple with all B graphs (one with nothing kept has n_node = 0, so per-graph tensors of the input
+                     still line up): nodes = the input's rows in their old order (index_select), int32 senders / receivers
+                     (both directions of every edge, receivers ascending, senders ascending within a receiver; the diagonal
+                     only with self_loops=True, and then on every kept node), zero edges, the input's globals, new n_node /
+                     n_edge
+      "csr"          graphs.Csr over (rowptr, senders): the receiver-sorted CSR and, the edge set being symmetric, its
+                     by-sender transpose; csr_of's cache is seeded for both, so a GRevNet call, a trainer step or one of the
+                     scores on result["graph"] launches no gnf_build_csr
+      "node_index"   int32 [N']: the old row of each new node      "new_id"  int32 [N]: the new row of each old node, or -1
+      "total_nodes", "total_edges"   0-d device int64
+    Exact-size mode only: the call reads N' and E' once (one 16-byte copy, its only synchronisation when max_nodes_per_graph
+    or n_node_host says how large the graphs are) and allocates exactly that.  A capacity / capture mode, as decode_graphs
+    has one, is out of scope here (the two entry points take capacities; this wrapper does not)."""
+    from .graphs import Csr, GraphsTuple, csr_desc, csr_of, seed_csr_cache
+    lib = _abi.lib()
+    dev = graph.senders.device
+    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
+        raise _abi.GnfError("keep_subgraphs runs on a HIP device only (no CPU path)")
+    n = int(graph.nodes.shape[0])
+    b = int(graph.n_node.shape[0])
+    mask = None
+    if isinstance(keep, torch.Tensor):
+        if keep.dim() != 1 or int(keep.shape[0]) != n or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"keep: a bool / uint8 tensor [{n}], got {keep.dtype} {tuple(keep.shape)}")
+        if keep.device.type != "cuda":
+            raise _abi.GnfError("keep_subgraphs runs on a HIP device only (no CPU path)")
+        rule, mask = _abi.GNF_KEEP_MASK, keep.to(device=dev, dtype=torch.uint8).contiguous()
+    elif keep in _KEEP_RULES:
+        rule = _KEEP_RULES[keep]
+    else:
+        raise ValueError(f"keep={keep!r}: one of {sorted(_KEEP_RULES)} or a bool / uint8 tensor [N]")
+    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
+    if n * (cap + 1) > 2 ** 31 - 1:
+        raise ValueError(f"{n} nodes x (max_nodes_per_graph={cap} + 1) exceeds the int32 edge ids")
+    csr = csr_of(graph)
+    desc = csr_desc(graph, csr, node_offsets=True)
+    new_id = torch.empty(n, dtype=torch.int32, device=dev)
+    new_n_node = torch.zeros(b, dtype=torch.int32, device=dev)
+    n_edge = torch.zeros(b, dtype=torch.int32, device=dev)
+    rowptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)     # (an empty batch: the call writes nothing)
+    ws_bytes = lib.gnf_graph_subgraph_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_graph_subgraph_count(C.byref(desc), cap, rule, _abi.ptr(mask), int(bool(self_loops)), _abi.ptr(new_id),
+                                                _abi.ptr(new_n_node), _abi.ptr(rowptr), _abi.ptr(n_edge), _abi.ptr(totals),
+                                                _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_graph_subgraph_count")
+        n_new, e_new = totals.tolist()
+        node_index = torch.empty(n_new, dtype=torch.int32, device=dev)
+        senders = torch.empty(e_new, dtype=torch.int32, device=dev)
+        receivers = torch.empty(e_new, dtype=torch.int32, device=dev)
+        _abi.check(lib.gnf_graph_subgraph_fill(b, n, cap, _abi.ptr(rowptr), n_new, e_new, _abi.ptr(node_index), _abi.ptr(senders),
+                                               _abi.ptr(receivers), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                   "gnf_graph_subgraph_fill")
+    rowptr = rowptr[:n_new + 1]
+    kept = GraphsTuple(nodes=graph.nodes.index_select(0, node_index.to(graph.nodes.device)),
+                       edges=torch.zeros(e_new, dtype=torch.float32, device=dev), receivers=receivers, senders=senders,
+                       globals=graph.globals, n_node=new_n_node, n_edge=n_edge)
+    sub = Csr(rowptr, senders, n_new, e_new)
+    seed_csr_cache(kept, sub, by_sender=False)
+    seed_csr_cache(kept, sub, by_sender=True)
+    return {"graph": kept, "csr": sub, "node_index": node_index, "new_id": new_id, "total_nodes": totals[0],
+            "total_edges": totals[1]}
+
+
+def evaluate_generated(generated, reference, orbits=False, spectral=False, keep=None):
     """Degree and clustering MMD^2 of a generated batch against a reference batch: two GraphsTuples, or two results of
     graph_stats (clustering_hist with 100 bins).  Degree: EMD kernel, sigma 1, distance_scaling 1.  Clustering: 100 bins,
     EMD kernel, sigma 0.1, distance_scaling 100.  Returns {"degree_mmd", "clustering_mmd"}, 0-d float64 device tensors.
     orbits=True adds "orbit_mmd" (orbit_mmd, sigma 30); dicts passed instead of GraphsTuples must then also hold the
     result of graph_orbits ({**graph_stats(g), **graph_orbits(g)}).  spectral=True adds "spectral_mmd" (spectral_mmd on
-    graph_spectra's default histograms, sigma 1); dicts must then also hold "spectral_hist"."""
+    graph_spectra's default histograms, sigma 1); dicts must then also hold "spectral_hist".
+    keep (keep_subgraphs' argument: "largest_component", "non_isolated" or a mask) reduces the GENERATED batch, a
+    GraphsTuple, before it is scored - the usual post-processing of generated graphs; the reference batch is scored as
+    given.  With a dict for `generated` there is no graph to reduce: ValueError."""
+    if keep is not None:
+        if isinstance(generated, dict):
+            raise ValueError("evaluate_generated(keep=...) needs the generated batch as a GraphsTuple, not its statistics")
+        generated = keep_subgraphs(generated, keep)["graph"]
     inputs = (generated, reference)
     stats = [s if isinstance(s, dict) else graph_stats(s, clustering_bins=100) for s in inputs]
     for s in stats:

@@ -522,6 +522,8 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 #include "gnf_inverse_per_graph.h"
 /* Added within ABI v10: normalised-Laplacian eigenvalues of a batch of graphs and their histograms (gnf_graph_spectra.h) - likewise. */
 #include "gnf_graph_spectra.h"
+/* Added within ABI v10: connected components of a batch of graphs and node-induced subgraph batches (gnf_graph_components.h) - likewise. */
+#include "gnf_graph_components.h"
 
 #ifdef __cplusplus
 }
