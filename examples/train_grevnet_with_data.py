@@ -87,6 +87,8 @@ def main():
     ap.add_argument("--sample_log_prob_xs", action="store_true")   # also log the flow's own density of each generated graph
     # reduce every generated graph to its largest connected component / its nodes with a neighbour (graph_stats.keep_subgraphs)
     ap.add_argument("--keep_generated", default="all", choices=["all", "largest_component", "non_isolated"])
+    # uniqueness and novelty of the sampled graphs against the training graphs of --dataset (graph_stats.uniqueness_novelty)
+    ap.add_argument("--report_novelty", action="store_true")
     F = ap.parse_args()
     random.seed(F.random_seed)
     np.random.seed(F.random_seed)
@@ -170,6 +172,17 @@ def main():
         share = float(out["kept"]["total_nodes"]) / max(int(n_node.sum()), 1)
         print(f"generated graphs: mean n_components {float(parts):.2f}, --keep_generated {keep} keeps {share:.1%} of the nodes, "
               f"{int(out['kept']['total_edges']) // 2} edges")
+    if F.report_novelty:
+        from gnf_amd.graphs import data_dicts_to_graphs_tuple
+        from gnf_amd.graph_stats import graph_hashes, uniqueness_novelty
+        ds = D.GraphDataset(F.dataset, 1, seed=F.random_seed)
+        train = graph_hashes(data_dicts_to_graphs_tuple(ds.all.data_dicts(ds.train_ids, ds._features), dev))   # hashed once
+        classes = uniqueness_novelty(train, train)["counts"][1]
+        sampled = out["kept"]["graph"] if keep is not None else out["graph"]
+        u = uniqueness_novelty(sampled, train)
+        print(f"sampled graphs: uniqueness {float(u['uniqueness']):.1%}, novelty {float(u['novelty']):.1%}, unique and novel "
+              f"{float(u['unique_novel']):.1%} of {int(u['counts'][0])}; the {len(ds.train_ids)} training graphs of {F.dataset} "
+              f"fall into {int(classes)} isomorphism classes (Weisfeiler-Lehman hash, 3 rounds)")
     if F.sample_log_prob_xs:
         for i, lp in enumerate(out["log_prob_xs_per_node"].cpu().numpy()):
             print(f"sampled graph {i}: log_prob_xs_per_node {lp:.4f}")

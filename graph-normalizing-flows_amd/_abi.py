@@ -249,6 +249,17 @@ _COMPONENT_SIGNATURES = {
     "gnf_graph_subgraph_fill": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+
+# include/gnf_graph_hashes.h (included by gnf.h, added within ABI v10): Weisfeiler-Lehman hashes of a batch of graphs and the
+# matching of two hash sets (uniqueness / novelty).  A table of its own for the same reason.
+_HASH_SIGNATURES = {
+    "gnf_graph_hashes_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_graph_hashes": (C.c_int, [C.POINTER(GnfCsr), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_graph_hash_match_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gnf_graph_hash_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -263,6 +274,7 @@ ENCODER_TRAIN_SYMBOLS = tuple(_ENCODER_TRAIN_SIGNATURES)
 DISTANCE_SYMBOLS = tuple(_DISTANCE_SIGNATURES)
 SPECTRA_SYMBOLS = tuple(_SPECTRA_SIGNATURES)
 COMPONENT_SYMBOLS = tuple(_COMPONENT_SIGNATURES)
+HASH_SYMBOLS = tuple(_HASH_SIGNATURES)
 
 _lib = None
 
@@ -279,7 +291,7 @@ def lib():
         for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES,
                                   **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
                                   **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
-                                  **_COMPONENT_SIGNATURES}.items():
+                                  **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

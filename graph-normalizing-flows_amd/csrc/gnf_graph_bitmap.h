@@ -68,4 +68,39 @@ inline unsigned stats_grid(int64_t items) {
     return (unsigned)(items > kStatsGridMax ? kStatsGridMax : items);
 }
 
+// what the per-graph entry points on the bitmap (gnf_graph_components, gnf_graph_subgraph_count, gnf_graph_hashes) ask of csr
+// and max_nodes_per_graph (host only; `limit` is the entry point's largest bound)
+inline int graph_csr_ok(const char* what, const GnfCsr* csr, int32_t cap, int32_t limit) {
+    if (!csr) {
+        set_error("%s: null csr", what);
+        return GNF_EINVAL;
+    }
+    if (cap < 0 || cap > limit) {
+        set_error("%s: max_nodes_per_graph=%d (0 <= max_nodes_per_graph <= %d)", what, cap, limit);
+        return GNF_ESHAPE;
+    }
+    if (csr->n_nodes < 0 || csr->n_edges < 0 || csr->n_graphs < 0 || csr->n_graphs > 0x7fffffff || csr->n_nodes > 0x7fffffff) {
+        set_error("%s: n_nodes=%lld n_edges=%lld n_graphs=%lld", what, (long long)csr->n_nodes, (long long)csr->n_edges,
+                  (long long)csr->n_graphs);
+        return GNF_ESHAPE;
+    }
+    if (csr->n_nodes > 0 && (!csr->node_offsets || csr->n_graphs < 1)) {
+        set_error("%s: csr->node_offsets / csr->n_graphs are required", what);
+        return GNF_EINVAL;
+    }
+    if (csr->n_graphs > 0 && !csr->node_offsets) {
+        set_error("%s: csr->node_offsets is null with n_graphs=%lld", what, (long long)csr->n_graphs);
+        return GNF_EINVAL;
+    }
+    if ((csr->n_nodes > 0 && !csr->rowptr) || (csr->n_edges > 0 && !csr->col)) {
+        set_error("%s: null pointer argument", what);
+        return GNF_EINVAL;
+    }
+    if (csr->n_nodes > 0 && cap == 0) {
+        set_error("%s: max_nodes_per_graph=0 with %lld nodes", what, (long long)csr->n_nodes);
+        return GNF_ESHAPE;
+    }
+    return GNF_OK;
+}
+
 }  // namespace gnf

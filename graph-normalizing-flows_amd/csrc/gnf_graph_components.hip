@@ -436,40 +436,6 @@ __global__ __launch_bounds__(256) void k_sub_fill(const int32_t* __restrict__ of
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-// what gnf_graph_components and gnf_graph_subgraph_count ask of csr and max_nodes_per_graph
-static int comp_csr_ok(const char* what, const GnfCsr* csr, int32_t cap) {
-    if (!csr) {
-        set_error("%s: null csr", what);
-        return GNF_EINVAL;
-    }
-    if (cap < 0 || cap > kCompMaxNodes) {
-        set_error("%s: max_nodes_per_graph=%d (0 <= max_nodes_per_graph <= %d)", what, cap, kCompMaxNodes);
-        return GNF_ESHAPE;
-    }
-    if (csr->n_nodes < 0 || csr->n_edges < 0 || csr->n_graphs < 0 || csr->n_graphs > 0x7fffffff || csr->n_nodes > 0x7fffffff) {
-        set_error("%s: n_nodes=%lld n_edges=%lld n_graphs=%lld", what, (long long)csr->n_nodes, (long long)csr->n_edges,
-                  (long long)csr->n_graphs);
-        return GNF_ESHAPE;
-    }
-    if (csr->n_nodes > 0 && (!csr->node_offsets || csr->n_graphs < 1)) {
-        set_error("%s: csr->node_offsets / csr->n_graphs are required", what);
-        return GNF_EINVAL;
-    }
-    if (csr->n_graphs > 0 && !csr->node_offsets) {
-        set_error("%s: csr->node_offsets is null with n_graphs=%lld", what, (long long)csr->n_graphs);
-        return GNF_EINVAL;
-    }
-    if ((csr->n_nodes > 0 && !csr->rowptr) || (csr->n_edges > 0 && !csr->col)) {
-        set_error("%s: null pointer argument", what);
-        return GNF_EINVAL;
-    }
-    if (csr->n_nodes > 0 && cap == 0) {
-        set_error("%s: max_nodes_per_graph=0 with %lld nodes", what, (long long)csr->n_nodes);
-        return GNF_ESHAPE;
-    }
-    return GNF_OK;
-}
-
 static bool sub_sizes_ok(int64_t n_graphs, int64_t n_nodes, int32_t cap) {
     return n_graphs >= 0 && n_graphs <= 0x7fffffff && n_nodes >= 0 && cap >= 0 && cap <= kCompMaxNodes &&
            n_nodes * ((int64_t)cap + 1) <= INT32_MAX;
@@ -513,7 +479,7 @@ int gnf_graph_components(const GnfCsr* csr, int32_t max_nodes_per_graph, int32_t
                          int32_t* n_components, int32_t* largest_size, int32_t* largest_root, int32_t* n_isolated, void* ws,
                          size_t ws_bytes, gnf_stream_t stream) {
     const char* what = "gnf_graph_components";
-    if (int rc = comp_csr_ok(what, csr, max_nodes_per_graph)) return rc;
+    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kCompMaxNodes)) return rc;
     const int64_t n = csr->n_nodes, b = csr->n_graphs;
     if ((n > 0 && (!component || !component_size || !ws)) ||
         (b > 0 && (!n_components || !largest_size || !largest_root || !n_isolated))) {
@@ -547,7 +513,7 @@ int gnf_graph_subgraph_count(const GnfCsr* csr, int32_t max_nodes_per_graph, int
                              int32_t self_loops, int32_t* new_id, int32_t* new_n_node, int32_t* rowptr, int32_t* n_edge,
                              int64_t* totals, void* ws, size_t ws_bytes, gnf_stream_t stream) {
     const char* what = "gnf_graph_subgraph_count";
-    if (int rc = comp_csr_ok(what, csr, max_nodes_per_graph)) return rc;
+    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kCompMaxNodes)) return rc;
     const int64_t n = csr->n_nodes, b = csr->n_graphs;
     if (!sub_sizes_ok(b, n, max_nodes_per_graph)) {
         set_error("%s: n_nodes=%lld x (max_nodes_per_graph=%d + 1) exceeds the int32 edge ids", what, (long long)n,

@@ -14,6 +14,10 @@ Before any of them: graph_components (gnf_graph_components) says whether a gener
 threshold` decides every pair of nodes on its own - and keep_subgraphs (gnf_graph_subgraph_count / _fill) reduces a batch to
 its largest components, its non-isolated nodes or a mask, as a batch everything here and the flow accept as it is;
 evaluate_generated(..., keep=...) does that to the generated batch first.
+And what none of the four can see - a sampler that replays its training set scores a perfect MMD: graph_hashes
+(gnf_graph_hashes) gives every graph a Weisfeiler-Lehman hash that does not depend on the node numbering, uniqueness_novelty
+(gnf_graph_hash_match) turns two hash sets into the shares of generated graphs that repeat no earlier generated graph and no
+training graph; evaluate_generated(..., train=...) adds them.
 Every graph is read as undirected and simple (self loops ignored, duplicates once, one direction is enough).  HIP only:
 CPU tensors raise GnfError.
 """
@@ -34,6 +38,10 @@ SPECTRA_LDS_NODES = 139              # up to here a graph's matrix lives in LDS,
 SPECTRA_SLOTS = 256                  # matrix slots of the workspace route
 SPECTRA_KEYS = ("eigenvalues", "spectral_hist", "n_node")
 COMPONENT_KEYS = ("component", "component_size", "n_components", "largest_component_size", "largest_component_root", "n_isolated")
+WL_MAX_ITERATIONS = 64    # gnf_graph_hashes: refinement rounds
+WL_LDS_NODES = 4096       # up to here a graph's colours live in LDS (one launch), above it in the workspace (one per round)
+HASH_KEYS = ("hash", "node_colour", "n_edges", "n_node")
+NOVELTY_KEYS = ("uniqueness", "novelty", "unique_novel", "first_in_generated", "match_in_training", "counts")
 _KEEP_RULES = {"largest_component": _abi.GNF_KEEP_LARGEST_COMPONENT, "non_isolated": _abi.GNF_KEEP_NON_ISOLATED}
 
 
@@ -376,7 +384,106 @@ def keep_subgraphs(graph, keep="largest_component", self_loops=False, max_nodes_
             "total_edges": totals[1]}
 
 
-def evaluate_generated(generated, reference, orbits=False, spectral=False, keep=None):
+def graph_hashes(graph, iterations=3, labels=None, max_nodes_per_graph=None, n_node_host=None):
+    """Weisfeiler-Lehman hash of every graph of a GraphsTuple (gnf_graph_hashes; the definition is in
+    include/gnf_graph_hashes.h), as a dict of device tensors:
+      "hash"         int64 [B]: the 64-bit hash as its bit pattern - compare for equality only
+      "node_colour"  int64 [N]: every node's colour after the last round, likewise
+      "n_edges"      int64 [B]: simple undirected edges
+      "n_node"       int32 [B]: the batch's sizes (the second half of the key uniqueness_novelty compares)
+    Isomorphic graphs get equal hashes, whatever their node numbering.  The converse holds only as far as 1-dimensional
+    colour refinement sees: a 6-cycle and two triangles, or two regular graphs of equal size and degree, collide by
+    definition.  labels (int64 [N] on the device, permuted with the nodes) replaces the degree as the initial colour and is the
+    way out - the triangle column of graph_orbits separates that pair.
+    The CSR comes from graphs.csr_of: on the result of decode_graphs / generate_graphs no gnf_build_csr runs.  As for
+    graph_stats, with max_nodes_per_graph (any upper bound on n_node, at most 65536) or n_node_host nothing is copied to the
+    host and nothing synchronises, so the call can be captured; otherwise n_node is read once.  Up to WL_LDS_NODES columns
+    one launch does all rounds; above, one launch per round.  Both give the same bits."""
+    from .graphs import csr_desc, csr_of
+    lib = _abi.lib()
+    dev = graph.senders.device
+    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
+        raise _abi.GnfError("graph_hashes runs on a HIP device only (no CPU path)")
+    n = int(graph.nodes.shape[0])
+    b = int(graph.n_node.shape[0])
+    iterations = int(iterations)
+    if not 0 <= iterations <= WL_MAX_ITERATIONS:
+        raise ValueError(f"iterations={iterations}: 0 .. {WL_MAX_ITERATIONS}")
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
+            raise ValueError(f"labels: an int64 tensor [{n}]")
+        if labels.device.type != "cuda":
+            raise _abi.GnfError("graph_hashes runs on a HIP device only (no CPU path)")
+        labels = labels.to(dev).contiguous()
+    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
+    csr = csr_of(graph)
+    desc = csr_desc(graph, csr, node_offsets=True)
+    out = {"hash": torch.empty(b, dtype=torch.int64, device=dev),
+           "node_colour": torch.empty(n, dtype=torch.int64, device=dev),
+           "n_edges": torch.empty(b, dtype=torch.int64, device=dev)}
+    ws_bytes = lib.gnf_graph_hashes_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_graph_hashes(C.byref(desc), cap, iterations, _abi.ptr(labels), _abi.ptr(out["hash"]),
+                                        _abi.ptr(out["node_colour"]), _abi.ptr(out["n_edges"]), _abi.ptr(ws), ws_bytes,
+                                        _abi.stream_ptr(dev)), "gnf_graph_hashes")
+    out["n_node"] = graph.n_node.to(torch.int32)
+    return out
+
+
+def _hash_set(x, iterations, dev=None):
+    """(hash int64 [rows], n_node int32 [rows]), contiguous on one device, of a GraphsTuple or a graph_hashes result"""
+    if not isinstance(x, dict):
+        x = graph_hashes(x, iterations)
+    elif not ("hash" in x and "n_node" in x):
+        raise ValueError("uniqueness_novelty on a dict needs the result of graph_hashes in it")
+    h, cnt = x["hash"], x["n_node"]
+    for v in (h, cnt):
+        if not isinstance(v, torch.Tensor) or v.device.type != "cuda":
+            raise _abi.GnfError("uniqueness_novelty runs on a HIP device only (no CPU path)")
+    if h.dim() != 1 or cnt.shape != h.shape or h.dtype != torch.int64:
+        raise ValueError(f"uniqueness_novelty takes int64 [rows] hashes with [rows] sizes, got {h.dtype} {tuple(h.shape)} and "
+                         f"{tuple(cnt.shape)}")
+    dev = h.device if dev is None else dev
+    return h.to(dev).contiguous(), cnt.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def uniqueness_novelty(generated, training, iterations=3):
+    """Whether the generated graphs repeat each other or the training set (gnf_graph_hash_match).  Each argument is a
+    GraphsTuple (hashed here with graph_hashes(g, iterations)) or a result of graph_hashes - hash the training set once and
+    pass the result.  Two graphs count as the same when their hash and their n_node are equal: isomorphic graphs always do,
+    and so do the pairs colour refinement cannot separate (see graph_hashes).  Graphs without nodes are left out.  Returns
+      "uniqueness"          distinct / valid: the share of generated graphs that repeat no EARLIER generated graph
+      "novelty"             novel / valid: the share that match no training graph
+      "unique_novel"        the share that do neither                    (all three 0-d float64 device tensors)
+      "first_in_generated"  int32 [A]: the first generated graph with this graph's key - itself for the first of its kind
+      "match_in_training"   int32 [A]: the first matching training graph, else -1   (both -1 for a graph without nodes)
+      "counts"              int64 [4]: valid, distinct, novel, distinct and novel
+    An empty training set is allowed: everything is novel.  Raises ValueError when no generated graph has a node: reading the
+    counts for that check is the call's only copy to the host when both arguments are graph_hashes results."""
+    lib = _abi.lib()
+    ha, ca = _hash_set(generated, iterations)
+    dev = ha.device
+    hb, cb = _hash_set(training, iterations, dev)
+    a, b = int(ha.shape[0]), int(hb.shape[0])
+    first = torch.empty(a, dtype=torch.int32, device=dev)
+    match = torch.empty(a, dtype=torch.int32, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    ws_bytes = lib.gnf_graph_hash_match_workspace_bytes(a, b)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_graph_hash_match(_abi.ptr(ha), _abi.ptr(ca), a, _abi.ptr(hb), _abi.ptr(cb), b, _abi.ptr(first),
+                                            _abi.ptr(match), _abi.ptr(counts), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                   "gnf_graph_hash_match")
+    if counts[0].item() < 1:
+        raise ValueError("uniqueness_novelty: no generated graph has a node")
+    valid = counts[0].to(torch.float64)
+    return {"uniqueness": counts[1].to(torch.float64) / valid, "novelty": counts[2].to(torch.float64) / valid,
+            "unique_novel": counts[3].to(torch.float64) / valid, "first_in_generated": first, "match_in_training": match,
+            "counts": counts}
+
+
+def evaluate_generated(generated, reference, orbits=False, spectral=False, keep=None, train=None):
     """Degree and clustering MMD^2 of a generated batch against a reference batch: two GraphsTuples, or two results of
     graph_stats (clustering_hist with 100 bins).  Degree: EMD kernel, sigma 1, distance_scaling 1.  Clustering: 100 bins,
     EMD kernel, sigma 0.1, distance_scaling 100.  Returns {"degree_mmd", "clustering_mmd"}, 0-d float64 device tensors.
@@ -385,11 +492,16 @@ def evaluate_generated(generated, reference, orbits=False, spectral=False, keep=
     graph_spectra's default histograms, sigma 1); dicts must then also hold "spectral_hist".
     keep (keep_subgraphs' argument: "largest_component", "non_isolated" or a mask) reduces the GENERATED batch, a
     GraphsTuple, before it is scored - the usual post-processing of generated graphs; the reference batch is scored as
-    given.  With a dict for `generated` there is no graph to reduce: ValueError."""
+    given.  With a dict for `generated` there is no graph to reduce: ValueError.
+    train (the TRAINING batch as a GraphsTuple, or its graph_hashes result - hash it once) adds "uniqueness", "novelty" and
+    "unique_novel" (uniqueness_novelty, 3 rounds) of the generated batch, after keep= is applied - what the MMDs cannot see:
+    a sampler that replays its training set.  A dict for `generated` must then hold the result of graph_hashes."""
     if keep is not None:
         if isinstance(generated, dict):
             raise ValueError("evaluate_generated(keep=...) needs the generated batch as a GraphsTuple, not its statistics")
         generated = keep_subgraphs(generated, keep)["graph"]
+    if train is not None and isinstance(generated, dict) and not ("hash" in generated and "n_node" in generated):
+        raise ValueError("evaluate_generated(train=...) on a dict needs the result of graph_hashes in it")
     inputs = (generated, reference)
     stats = [s if isinstance(s, dict) else graph_stats(s, clustering_bins=100) for s in inputs]
     for s in stats:
@@ -409,4 +521,7 @@ def evaluate_generated(generated, reference, orbits=False, spectral=False, keep=
                 raise ValueError("evaluate_generated(spectral=True) on a dict needs the result of graph_spectra in it")
         sets = [s if isinstance(s, dict) else graph_spectra(s) for s in inputs]
         out["spectral_mmd"] = spectral_mmd(sets[0], sets[1], 1.0)
+    if train is not None:
+        shares = uniqueness_novelty(generated, train, 3)
+        out.update({k: shares[k] for k in NOVELTY_KEYS[:3]})
     return out
