@@ -110,11 +110,22 @@ def problem(c):
     return pr
 
 
+def register_problem(c, pr):
+    """A case of another family (tests/backward_routes.py) with the problem its own module built: any hashable `c` with .t,
+    `pr` with the keys of problem()'s result (+ "ws": weight sharing, False where absent).  _gather_run, _grads_with_sides
+    and check_grads then work on it as on this module's cases."""
+    _PROBLEMS[c] = pr
+    return pr
+
+
 def flat_grads(g):
-    """(name, array) of every tensor of a gradient container, bijectors last; the same order for the same layout."""
+    """(name, array) of every tensor of a gradient container, bijectors last; the same order for the same layout.  With
+    weight sharing a half holds one net (its list of (W, b)) instead of a list of T nets: named as net 0 of that half."""
     out = []
     for kind in ("s", "t"):
         for half, nets in enumerate(g[kind]):
+            if nets and isinstance(nets[0], tuple) and hasattr(nets[0][0], "shape"):
+                nets = [nets]
             for i, net in enumerate(nets):
                 mlp = net["mlp"] if isinstance(net, dict) else net
                 if isinstance(net, dict):
@@ -153,11 +164,11 @@ def _gather_run(pr, t, dtype, inverse=True):
 
     o = Recording(pr["s"], pr["r"], pr["n"], dtype=dtype, **pr["kw"])
     o.moments, o.pre = [], {}
-    pt = o.prep_params(pr["p"])
+    pt, ws = o.prep_params(pr["p"]), pr.get("ws", False)
     with torch.no_grad():
-        o.f(o.to_t(pr["x"]), pt, t)
+        o.f(o.to_t(pr["x"]), pt, t, ws)
         pre, o.pre = o.pre, None
-        gz = o.g(o.to_t(pr["zs"]), pt, t).numpy().astype(np.float64) if inverse else None
+        gz = o.g(o.to_t(pr["zs"]), pt, t, ws).numpy().astype(np.float64) if inverse else None
     moments = {(q % 2, q // 2): mv for q, mv in enumerate(o.moments)}      # f visits (0, i) then (1, i)
     return moments, gz, pre
 
@@ -309,7 +320,8 @@ def _grads_with_sides(c, ref, flips):
     for key, v, u in flips:
         masks[key][v, u] = not masks[key][v, u]
     state = {"masks": masks, "tol": k["tol"]}
-    out = flat_grads(O.loss_and_grads(pr["s"], pr["r"], pr["n"], pr["x"], pr["p"], c.t, kink=state, **pr["kw"])["grads"])
+    out = flat_grads(O.loss_and_grads(pr["s"], pr["r"], pr["n"], pr["x"], pr["p"], c.t, pr.get("ws", False), kink=state,
+                                      **pr["kw"])["grads"])
     assert state.get("outside", 0) == 0, state
     return out
 

@@ -661,7 +661,10 @@ def test_training_with_batch_norm_updates_moving_statistics(grid_small):
 def test_randomised_parity_sweep():
     """tools/fuzz_parity.py: random flow hyper-parameters (message passing / attention, batch norm, weight sharing,
     K = 1..4, odd widths) x random ragged batches (isolated nodes, duplicated / directed edges, complete graphs, a
-    high-degree star) through forward, inverse and gradients on both kernel paths vs the float64 oracle."""
+    high-degree star) through forward, inverse and gradients on both kernel paths vs the float64 oracle.
+    Every one of the 24 cases is accounted for: the tool skips a case only on the reference's own evidence (the float64
+    oracle overflows, or the float32 oracle's round trip g(f(x)) misses the reconstruction threshold), and on this seed the
+    reference does neither (|z|max <= 38; round trip <= 1.9e-6 against 5e-5 .. 9e-5) - so nothing may come back "skipped"."""
     import importlib.util
     import os
     spec = importlib.util.spec_from_file_location(
@@ -669,7 +672,8 @@ def test_randomised_parity_sweep():
     fz = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(fz)
     results = [fz.run_case(i, 20260928) for i in range(24)]
-    assert sum(r.startswith("ok") for r in results) >= 20, results
+    missed = {i: r for i, r in enumerate(results) if not r.startswith("ok")}
+    assert not missed, f"cases of seed 20260928 that did not pass (re-run one with tools/fuzz_parity.py --seed 20260928 --only <index>): {missed}"
 
 
 def test_gradients_on_a_batch_with_more_tiles_than_cus(community_medium):
