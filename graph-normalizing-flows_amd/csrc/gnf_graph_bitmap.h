@@ -1,8 +1,7 @@
-// What gnf_graph_stats.hip and gnf_graph_orbits.hip share: the 64-bit adjacency bitmap of a batch read as undirected simple
-// graphs (one word per (node, 64 graph-local columns); layout and construction are described in gnf_graph_stats.hip), the
-// graph-range helpers, the wave sums and the grid cap.  k_stats_bitmap is DEFINED in gnf_graph_stats.hip and only declared
-// here: there is no relocatable device code in this library, a launch from another unit goes through the host-side handle
-// that unit registers.
+// What the graph scores (gnf_graph_stats / _orbits / _spectra / _components / _hashes .hip) share: the 64-bit adjacency bitmap of
+// a batch read as undirected simple graphs (one word per (node, 64 graph-local columns); the layout is described in
+// gnf_graph_stats.hip, gnf_graph_bitmap.hip builds it), the graph-range helpers, the row preamble, the per-node degree and
+// triangle walk, the wave sums, the grid cap and the host-side check of csr and max_nodes_per_graph.
 #pragma once
 #include "gnf_common.h"
 
@@ -23,6 +22,10 @@ inline StatsWs stats_ws(int64_t n_nodes, int32_t max_nodes) {
     L.total = (L.gid + (size_t)n_nodes * sizeof(int32_t) + 7) / 8 * 8;
     return L;
 }
+
+// Zeroes the bitmap of a validated batch with nodes (n > 0, b > 0) on the stream and fills it and gid (k_stats_bitmap,
+// gnf_graph_bitmap.hip); bitmap [N][W] and gid [N] are the two arrays of a StatsWs, W = ceil(cap / 64).
+int build_graph_bitmap(const GnfCsr* csr, int32_t cap, int64_t W, unsigned long long* bitmap, int32_t* gid, hipStream_t st);
 
 // graph of node i: the last g with node_offsets[g] <= i (empty graphs share their offset with the next one), -1 when i lies
 // past node_offsets[n_graphs].  n0 / ng: its first row and size, cut to the node buffer and to the bitmap's columns - offsets
@@ -47,12 +50,16 @@ __device__ __forceinline__ void stats_graph_range(const int32_t* __restrict__ of
     ng = c > 0 ? (int)c : 0;
 }
 
-// one wave per CSR row i sets bit (i, j - n0) and bit (j, i - n0) of the zeroed bitmap for every entry (receiver i, sender j),
-// i != j, inside the graph's window, and writes gid[i]; grid stats_grid((n_nodes + 3) / 4), 256 threads
-__global__ __launch_bounds__(256) void k_stats_bitmap(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                      int64_t n_nodes, int64_t n_edges, const int32_t* __restrict__ off,
-                                                      int64_t n_graphs, int max_nodes, int64_t W,
-                                                      unsigned long long* __restrict__ bitmap, int32_t* __restrict__ gid);
+// the graph of bitmap row i and its window; false for a row in no graph or past the bound inside its graph (g, n0, ng are then
+// not to be used).  gid is written by k_stats_bitmap alone: -1 or a graph of the batch.
+__device__ __forceinline__ bool graph_of_row(const int32_t* __restrict__ off, const int32_t* __restrict__ gid, int64_t n_nodes,
+                                             int max_nodes, int64_t i, int& g, int64_t& n0, int& ng) {
+    g = gid[i];
+    if (g < 0) return false;
+    stats_graph_range(off, g, n_nodes, max_nodes, n0, ng);
+    const int64_t li = i - n0;
+    return li >= 0 && li < ng;
+}
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -63,23 +70,72 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return __shfl(v, 0, 64);
 }
 
+// Hands the set bits of the LDS row to the lanes 64 at a time through the 128-entry LDS queue: a node of any degree keeps the
+// wave full.  One wave per workgroup; visit(lj) runs once per neighbour lj.
+template <class Visit>
+__device__ __forceinline__ void for_each_neighbour(const unsigned long long* row, int32_t* queue, int words, int lane,
+                                                   Visit visit) {
+    int q = 0;   // entries waiting in the queue (< 64 between words)
+    for (int w = 0; w < words; ++w) {
+        const unsigned long long word = row[w];
+        if (word == 0) continue;
+        if ((word >> lane) & 1ull) queue[q + __popcll(word & ((1ull << lane) - 1ull))] = w * 64 + lane;
+        q += __popcll(word);
+        __syncthreads();
+        if (q >= 64) {
+            visit(queue[lane]);
+            const int32_t tail = queue[64 + lane];
+            __syncthreads();
+            q -= 64;
+            if (lane < q) queue[lane] = tail;
+            __syncthreads();
+        }
+    }
+    if (lane < q) visit(queue[lane]);
+}
+
+// Degree d and triangle count t of bitmap row i (graph window n0, `words` words), by the one wave of a workgroup; every lane
+// gets both.  Loads the row into LDS (row [W] words, queue [128] graph-local neighbour ids) and leaves it there:
+// d = sum_w popc(row_i[w]), t = 1/2 sum_{j in N(i)} sum_w popc(row_i[w] & row_j[w]), lane = one neighbour j reading row_j from
+// global memory.
+__device__ __forceinline__ void row_degree_triangles(const unsigned long long* __restrict__ bitmap, int64_t i,
+                                                     unsigned long long* row, int32_t* queue, int words, int64_t n0, int64_t W,
+                                                     unsigned long long& d, unsigned long long& t) {
+    const int lane = threadIdx.x;
+    __syncthreads();   // the previous node's readers are done
+    d = 0;
+    for (int w = lane; w < words; w += 64) {
+        const unsigned long long v = bitmap[i * W + w];
+        row[w] = v;
+        d += __popcll(v);
+    }
+    __syncthreads();
+    d = wave_sum_u64(d);
+    unsigned long long acc = 0;   // common neighbours of i and the neighbour a lane holds
+    for_each_neighbour(row, queue, words, lane, [&](int lj) {
+        const unsigned long long* rj = bitmap + (n0 + lj) * W;
+        for (int w = 0; w < words; ++w) acc += __popcll(row[w] & rj[w]);
+    });
+    t = wave_sum_u64(acc) >> 1;
+}
+
 inline unsigned stats_grid(int64_t items) {
     if (items < 1) items = 1;
     return (unsigned)(items > kStatsGridMax ? kStatsGridMax : items);
 }
 
-// what the per-graph entry points on the bitmap (gnf_graph_components, gnf_graph_subgraph_count, gnf_graph_hashes) ask of csr
-// and max_nodes_per_graph (host only; `limit` is the entry point's largest bound)
-inline int graph_csr_ok(const char* what, const GnfCsr* csr, int32_t cap, int32_t limit) {
+// what every batch entry point on the bitmap asks of csr and max_nodes_per_graph (host only; `limit` is the entry point's
+// largest bound, `why` the reason for it).  n_nodes above INT32_MAX is the caller's to refuse where node ids are held in int32.
+inline int graph_csr_ok(const char* what, const GnfCsr* csr, int32_t cap, int32_t limit, const char* why) {
     if (!csr) {
         set_error("%s: null csr", what);
         return GNF_EINVAL;
     }
     if (cap < 0 || cap > limit) {
-        set_error("%s: max_nodes_per_graph=%d (0 <= max_nodes_per_graph <= %d)", what, cap, limit);
+        set_error("%s: max_nodes_per_graph=%d (0 <= max_nodes_per_graph <= %d: %s)", what, cap, limit, why);
         return GNF_ESHAPE;
     }
-    if (csr->n_nodes < 0 || csr->n_edges < 0 || csr->n_graphs < 0 || csr->n_graphs > 0x7fffffff || csr->n_nodes > 0x7fffffff) {
+    if (csr->n_nodes < 0 || csr->n_edges < 0 || csr->n_graphs < 0 || csr->n_graphs > 0x7fffffff) {
         set_error("%s: n_nodes=%lld n_edges=%lld n_graphs=%lld", what, (long long)csr->n_nodes, (long long)csr->n_edges,
                   (long long)csr->n_graphs);
         return GNF_ESHAPE;

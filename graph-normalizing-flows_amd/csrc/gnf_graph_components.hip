@@ -3,8 +3,8 @@
 // its own, nothing makes the result one graph.  The reference stops at pickling the graphs (generate_graphs.py:68-84); nothing
 // in it corresponds to these kernels.
 //
-// Graph model and bitmap: as in gnf_graph_stats.hip (undirected, simple; k_stats_bitmap on a zeroed bitmap), shared through
-// gnf_graph_bitmap.h.  A component is named by the batch-wide row of its smallest node: a definition, not a search order.
+// Graph model and bitmap: as in gnf_graph_stats.hip (undirected, simple), built by build_graph_bitmap (gnf_graph_bitmap.h:
+// k_stats_bitmap on a zeroed bitmap).  A component is named by the batch-wide row of its smallest node: a definition, not a search order.
 //
 // gnf_graph_components.  k_stats_bitmap, then k_components - one workgroup of 256 threads per graph, striding over graphs;
 // the bitmap rows stay in global memory, three bitsets of W = ceil(max_nodes / 64) words sit in LDS (visited | frontier | next,
@@ -224,13 +224,10 @@ __global__ __launch_bounds__(256) void k_sub_degree_flags(const int32_t* __restr
                                                           const int32_t* __restrict__ gid, uint8_t* __restrict__ flags) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_nodes; i += (int64_t)gridDim.x * 4) {
-        const int g = gid[i];
-        int64_t n0 = 0;
-        int n = 0;
-        if (g >= 0) stats_graph_range(off, g, n_nodes, cap, n0, n);
-        const int64_t li = i - n0;
+        int g, n;
+        int64_t n0;
         unsigned long long any = 0ull;
-        if (g >= 0 && li >= 0 && li < n)
+        if (graph_of_row(off, gid, n_nodes, cap, i, g, n0, n))
             for (int w = lane; w < (n + 63) / 64; w += 64) any |= bitmap[i * W + w];
         const bool has = __ballot(any != 0ull) != 0ull;
         if (lane == 0) flags[i] = has ? 1 : 0;
@@ -329,21 +326,18 @@ __device__ __forceinline__ int32_t sub_new_row(const unsigned long long* __restr
 }
 
 // a wave per old row: new_id, and the degree of a kept row at its new row
-__global__ __launch_bounds__(256) void k_sub_rows(const int32_t* __restrict__ off, int64_t n_graphs, int64_t n_nodes, int cap,
-                                                  int64_t W, int self_loops, const unsigned long long* __restrict__ bitmap,
+__global__ __launch_bounds__(256) void k_sub_rows(const int32_t* __restrict__ off, int64_t n_nodes, int cap, int64_t W,
+                                                  int self_loops, const unsigned long long* __restrict__ bitmap,
                                                   const int32_t* __restrict__ gid, const unsigned long long* __restrict__ keep,
                                                   const int32_t* __restrict__ rank, const int32_t* __restrict__ new_off,
                                                   int32_t* __restrict__ new_id, int32_t* __restrict__ new_id_ws,
                                                   int32_t* __restrict__ rowcnt) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_nodes; i += (int64_t)gridDim.x * 4) {
-        const int g = gid[i];
-        int64_t n0 = 0;
-        int n = 0;
-        if (g >= 0 && g < n_graphs) stats_graph_range(off, g, n_nodes, cap, n0, n);
-        const int64_t li = i - n0;
+        int g, n;
+        int64_t n0;
         int32_t r = -1;
-        if (li >= 0 && li < n) r = sub_new_row(keep, rank, new_off, g, n0, li);
+        if (graph_of_row(off, gid, n_nodes, cap, i, g, n0, n)) r = sub_new_row(keep, rank, new_off, g, n0, i - n0);
         if (r >= n_nodes) r = -1;   // (offsets that do not describe the batch)
         if (lane == 0) {
             new_id[i] = r;
@@ -448,10 +442,7 @@ static int launch_components(const GnfCsr* csr, int32_t cap, const CompWs& L, vo
     const int64_t n = csr->n_nodes, b = csr->n_graphs;
     unsigned long long* bitmap = (unsigned long long*)((char*)ws + L.stats.bitmap);
     int32_t* gid = (int32_t*)((char*)ws + L.stats.gid);
-    GNF_HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)n * (size_t)L.stats.W * sizeof(uint64_t), st));
-    hipLaunchKernelGGL(k_stats_bitmap, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->rowptr, csr->col, n, csr->n_edges,
-                       csr->node_offsets, b, cap, L.stats.W, bitmap, gid);
-    GNF_LAUNCH_CHECK("k_stats_bitmap");
+    if (int rc = build_graph_bitmap(csr, cap, L.stats.W, bitmap, gid, st)) return rc;
     if (!search) return GNF_OK;
     GNF_HIP_TRY(hipMemsetAsync(component, 0xff, (size_t)n * sizeof(int32_t), st));   // rows no graph (or no column) covers: -1
     GNF_HIP_TRY(hipMemsetAsync(component_size, 0, (size_t)n * sizeof(int32_t), st));
@@ -479,8 +470,12 @@ int gnf_graph_components(const GnfCsr* csr, int32_t max_nodes_per_graph, int32_t
                          int32_t* n_components, int32_t* largest_size, int32_t* largest_root, int32_t* n_isolated, void* ws,
                          size_t ws_bytes, gnf_stream_t stream) {
     const char* what = "gnf_graph_components";
-    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kCompMaxNodes)) return rc;
+    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kCompMaxNodes, "gnf_graph_stats' limit")) return rc;
     const int64_t n = csr->n_nodes, b = csr->n_graphs;
+    if (n > 0x7fffffff) {
+        set_error("%s: n_nodes=%lld does not fit the int32 node ids", what, (long long)n);
+        return GNF_ESHAPE;
+    }
     if ((n > 0 && (!component || !component_size || !ws)) ||
         (b > 0 && (!n_components || !largest_size || !largest_root || !n_isolated))) {
         set_error("%s: null pointer argument", what);
@@ -513,7 +508,7 @@ int gnf_graph_subgraph_count(const GnfCsr* csr, int32_t max_nodes_per_graph, int
                              int32_t self_loops, int32_t* new_id, int32_t* new_n_node, int32_t* rowptr, int32_t* n_edge,
                              int64_t* totals, void* ws, size_t ws_bytes, gnf_stream_t stream) {
     const char* what = "gnf_graph_subgraph_count";
-    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kCompMaxNodes)) return rc;
+    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kCompMaxNodes, "gnf_graph_stats' limit")) return rc;
     const int64_t n = csr->n_nodes, b = csr->n_graphs;
     if (!sub_sizes_ok(b, n, max_nodes_per_graph)) {
         set_error("%s: n_nodes=%lld x (max_nodes_per_graph=%d + 1) exceeds the int32 edge ids", what, (long long)n,
@@ -578,7 +573,7 @@ int gnf_graph_subgraph_count(const GnfCsr* csr, int32_t max_nodes_per_graph, int
     hipLaunchKernelGGL(k_sub_offsets, dim3(1), dim3(256), 0, st, csr->node_offsets, new_n_node, b, self_loops,
                        (int32_t*)(base + L.off), new_off, (int32_t*)(base + L.hdr), totals);
     GNF_LAUNCH_CHECK("k_sub_offsets");
-    hipLaunchKernelGGL(k_sub_rows, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->node_offsets, b, n, cap, L.comp.stats.W,
+    hipLaunchKernelGGL(k_sub_rows, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->node_offsets, n, cap, L.comp.stats.W,
                        self_loops, bitmap, gid, keep, rank, new_off, new_id, (int32_t*)(base + L.new_id),
                        (int32_t*)(base + L.rowcnt));
     GNF_LAUNCH_CHECK("k_sub_rows");

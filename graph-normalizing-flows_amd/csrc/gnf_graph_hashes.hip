@@ -3,8 +3,8 @@
 // sampler that replays its training set scores a perfect MMD.  The reference stops at pickling the graphs
 // (generate_graphs.py:68-84); nothing in it corresponds to these kernels.
 //
-// Graph model and bitmap: as in gnf_graph_stats.hip (undirected, simple; k_stats_bitmap on a zeroed bitmap), shared through
-// gnf_graph_bitmap.h.  The hash is DEFINED in include/gnf_graph_hashes.h (wl_mix and the four constants below restate it): every
+// Graph model and bitmap: as in gnf_graph_stats.hip (undirected, simple), built by build_graph_bitmap (gnf_graph_bitmap.h:
+// k_stats_bitmap on a zeroed bitmap).  The hash is DEFINED in include/gnf_graph_hashes.h (wl_mix and the four constants below restate it): every
 // sum in it is a wrapping 64-bit integer sum, so neither the order of the nodes nor the order in which lanes, waves or atomics
 // add changes a bit, and the two routes below agree bit for bit.
 //
@@ -155,19 +155,9 @@ __global__ __launch_bounds__(1024) void k_wl_lds(const int32_t* __restrict__ off
 }
 
 // ---- global route ----------------------------------------------------------------------------------------------------------
-// the graph of row i and its window; false for a row in no graph or past the bound inside its graph
-__device__ __forceinline__ bool wl_row_graph(const int32_t* __restrict__ off, const int32_t* __restrict__ gid, int64_t n_graphs,
-                                             int64_t n_nodes, int cap, int64_t i, int& g, int64_t& n0, int& n) {
-    g = gid[i];
-    if (g < 0 || g >= n_graphs) return false;
-    stats_graph_range(off, g, n_nodes, cap, n0, n);
-    const int64_t li = i - n0;
-    return li >= 0 && li < n;
-}
-
 // a wave per row: colour 0 into `out`, its term into table[0][g], its degree into n_edges[g] (a degree sum until k_wl_fold)
-__global__ __launch_bounds__(256) void k_wl_init(const int32_t* __restrict__ off, int64_t n_graphs, int64_t n_nodes, int cap,
-                                                 int64_t W, const unsigned long long* __restrict__ bitmap,
+__global__ __launch_bounds__(256) void k_wl_init(const int32_t* __restrict__ off, int64_t n_nodes, int cap, int64_t W,
+                                                 const unsigned long long* __restrict__ bitmap,
                                                  const int32_t* __restrict__ gid, const int64_t* __restrict__ labels,
                                                  unsigned long long* __restrict__ out, unsigned long long* __restrict__ table,
                                                  unsigned long long* __restrict__ degree_sum) {
@@ -175,7 +165,7 @@ __global__ __launch_bounds__(256) void k_wl_init(const int32_t* __restrict__ off
     for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_nodes; i += (int64_t)gridDim.x * 4) {
         int g, n;
         int64_t n0;
-        if (!wl_row_graph(off, gid, n_graphs, n_nodes, cap, i, g, n0, n)) continue;   // (uniform over the wave)
+        if (!graph_of_row(off, gid, n_nodes, cap, i, g, n0, n)) continue;   // (uniform over the wave)
         const unsigned long long* row = bitmap + i * W;
         unsigned long long d = 0ull;
         for (int w = lane; w < (n + 63) / 64; w += 64) d += __popcll(wl_row_word(row, w, n));
@@ -199,7 +189,7 @@ __global__ __launch_bounds__(256) void k_wl_round(const int32_t* __restrict__ of
     for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_nodes; i += (int64_t)gridDim.x * 4) {
         int g, n;
         int64_t n0;
-        if (!wl_row_graph(off, gid, n_graphs, n_nodes, cap, i, g, n0, n)) continue;   // (uniform over the wave)
+        if (!graph_of_row(off, gid, n_nodes, cap, i, g, n0, n)) continue;   // (uniform over the wave)
         const unsigned long long* row = bitmap + i * W;
         const unsigned long long sum = wl_neighbour_sum(row, (n + 63) / 64, n, in + n0, lane);
         const unsigned long long c = wl_mix(in[i] * kWlC + sum + (unsigned long long)t);
@@ -288,7 +278,11 @@ size_t gnf_graph_hashes_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32
 int gnf_graph_hashes(const GnfCsr* csr, int32_t max_nodes_per_graph, int32_t iterations, const int64_t* labels, uint64_t* hash,
                      uint64_t* node_colour, int64_t* n_edges, void* ws, size_t ws_bytes, gnf_stream_t stream) {
     const char* what = "gnf_graph_hashes";
-    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kWlMaxNodes)) return rc;
+    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kWlMaxNodes, "gnf_graph_stats' limit")) return rc;
+    if (csr->n_nodes > 0x7fffffff) {
+        set_error("%s: n_nodes=%lld does not fit the int32 node ids", what, (long long)csr->n_nodes);
+        return GNF_ESHAPE;
+    }
     if (iterations < 0 || iterations > kWlMaxIter) {
         set_error("%s: iterations=%d (0 <= iterations <= %d)", what, iterations, kWlMaxIter);
         return GNF_ESHAPE;
@@ -317,11 +311,8 @@ int gnf_graph_hashes(const GnfCsr* csr, int32_t max_nodes_per_graph, int32_t ite
     char* base = (char*)ws;
     unsigned long long* bitmap = (unsigned long long*)(base + L.stats.bitmap);
     int32_t* gid = (int32_t*)(base + L.stats.gid);
-    GNF_HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)n * (size_t)L.stats.W * sizeof(uint64_t), st));
     GNF_HIP_TRY(hipMemsetAsync(node_colour, 0, (size_t)n * sizeof(uint64_t), st));   // rows no graph (or no column) covers: 0
-    hipLaunchKernelGGL(k_stats_bitmap, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->rowptr, csr->col, n, csr->n_edges,
-                       csr->node_offsets, b, cap, L.stats.W, bitmap, gid);
-    GNF_LAUNCH_CHECK("k_stats_bitmap");
+    if (int rc = build_graph_bitmap(csr, cap, L.stats.W, bitmap, gid, st)) return rc;
     if (cap <= kWlLdsNodes) {
         const size_t lds = 2 * (size_t)cap * sizeof(uint64_t);   // <= 64 KiB, + 512 bytes of static slots
         GNF_ONCE_PER_DEVICE(GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wl_lds),
@@ -339,7 +330,7 @@ int gnf_graph_hashes(const GnfCsr* csr, int32_t max_nodes_per_graph, int32_t ite
     const dim3 rows(stats_grid((n + 3) / 4));
     // round t reads what round t - 1 wrote and writes buffer t & 1; the last round writes node_colour itself
     unsigned long long* out = iterations == 0 ? colour : buf[0];
-    hipLaunchKernelGGL(k_wl_init, rows, dim3(256), 0, st, csr->node_offsets, b, n, cap, L.stats.W, bitmap, gid, labels, out, table,
+    hipLaunchKernelGGL(k_wl_init, rows, dim3(256), 0, st, csr->node_offsets, n, cap, L.stats.W, bitmap, gid, labels, out, table,
                        (unsigned long long*)n_edges);
     GNF_LAUNCH_CHECK("k_wl_init");
     for (int t = 1; t <= iterations; ++t) {

@@ -3,19 +3,19 @@
 // clustering MMD of gnf_graph_stats.hip the third number GraphRNN-style evaluation reports.  The reference stops at pickling
 // the graphs (generate_graphs.py:68-84); nothing in it corresponds to these kernels.
 //
-// Graph model and bitmap: as in gnf_graph_stats.hip (undirected, simple; k_stats_bitmap on a zeroed bitmap), shared through
-// gnf_graph_bitmap.h.  orbit[v][o] = number of INDUCED connected subgraphs on 2..4 nodes that contain v with v in orbit o:
+// Graph model and bitmap: as in gnf_graph_stats.hip (undirected, simple), built by build_graph_bitmap (gnf_graph_bitmap.h:
+// k_stats_bitmap on a zeroed bitmap).  orbit[v][o] = number of INDUCED connected subgraphs on 2..4 nodes that contain v with v in orbit o:
 //   0 edge | 1 2 path3 end, middle | 3 triangle | 4 5 path4 end, inner | 6 7 star leaf, centre | 8 4-cycle |
 //   9 10 11 tailed triangle: tail end, triangle node of degree 2, of degree 3 | 12 13 chorded 4-cycle: degree 2, 3 | 14 K4
 //
-// Launches: k_stats_bitmap; k_orbit_degtri (one wave per node, the inner part of k_stats_nodes: d_k, t_k into the workspace);
+// Launches: k_stats_bitmap; k_orbit_degtri (one wave per node, row_degree_triangles as k_stats_nodes: d_k, t_k into the workspace);
 // k_orbit_nodes (one wave = one workgroup per node i, row_i in LDS).  All arithmetic is 64-bit integer.
 // With c_ik = popc(row_i & row_k), C2(x) = x (x - 1) / 2, C3(x) = x (x - 1) (x - 2) / 6, d = d_i, t = t_i = 1/2 sum_{j in N(i)} c_ij:
 //   sweep (lane = a node k != i of the graph, any k):   Q  = sum C2(c_ik)              4-cycles through i
 //                                                       X  = sum (d_k - 1) c_ik        walks i - j - k - l, l != j
 //         (k in N(i), a bit test on the LDS row):       A  = sum (d_k - 1)   Tn = sum t_k   D2 = sum C2(d_k - 1)
 //                                                       P  = sum c_ik (d_k - 2)   E2 = sum C2(c_ik)
-//   queue (lane = a neighbour j, 64 at a time, as k_stats_nodes; for every k > j in N(i) & N(j)):
+//   queue (lane = a neighbour j, 64 at a time, for_each_neighbour; for every k > j in N(i) & N(j)):
 //                                                       R  = sum (popc(row_j & row_k) - 1)     triangle i j k + one on edge j k
 //                                                       K3 = sum popc(row_i & row_j & row_k)   = 3 * (K4 through i)
 // These are NON-INDUCED rooted counts:  n4 = X - 2t, n5 = (d - 1) A - 2t, n6 = D2, n7 = C3(d), n8 = Q, n9 = Tn - 2t, n10 = P,
@@ -61,30 +61,6 @@ static OrbitWs orbit_ws(int64_t n_nodes, int32_t max_nodes) {
 
 __device__ __forceinline__ long long wave_sum_i64(long long v) { return (long long)wave_sum_u64((unsigned long long)v); }
 
-// Hands the set bits of the LDS row to the lanes 64 at a time through the 128-entry LDS queue (k_stats_nodes' scheme): a
-// node of any degree keeps the wave full.  One wave per workgroup; visit(lj) runs once per neighbour lj.
-template <class Visit>
-__device__ __forceinline__ void for_each_neighbour(const unsigned long long* row, int32_t* queue, int words, int lane,
-                                                   Visit visit) {
-    int q = 0;   // entries waiting in the queue (< 64 between words)
-    for (int w = 0; w < words; ++w) {
-        const unsigned long long word = row[w];
-        if (word == 0) continue;
-        if ((word >> lane) & 1ull) queue[q + __popcll(word & ((1ull << lane) - 1ull))] = w * 64 + lane;
-        q += __popcll(word);
-        __syncthreads();
-        if (q >= 64) {
-            visit(queue[lane]);
-            const int32_t tail = queue[64 + lane];
-            __syncthreads();
-            q -= 64;
-            if (lane < q) queue[lane] = tail;
-            __syncthreads();
-        }
-    }
-    if (lane < q) visit(queue[lane]);
-}
-
 // one wave = one workgroup per node: d_i and t_i into the workspace, 0 for a row no graph (or no bitmap column) covers.
 // LDS: row_i [W] words | queue [128]
 __global__ __launch_bounds__(64) void k_orbit_degtri(const int32_t* __restrict__ off, int64_t n_nodes, int max_nodes, int64_t W,
@@ -96,34 +72,17 @@ __global__ __launch_bounds__(64) void k_orbit_degtri(const int32_t* __restrict__
     int32_t* queue = (int32_t*)(orbit_lds + W);  // [128]
     const int lane = threadIdx.x;
     for (int64_t i = blockIdx.x; i < n_nodes; i += gridDim.x) {   // (uniform over the workgroup)
-        const int g = gid[i];
-        int64_t n0 = 0;
-        int ng = 0;
-        if (g >= 0) stats_graph_range(off, g, n_nodes, max_nodes, n0, ng);
-        const int64_t li = i - n0;
-        if (g < 0 || li < 0 || li >= ng) {
+        int g, ng;
+        int64_t n0;
+        if (!graph_of_row(off, gid, n_nodes, max_nodes, i, g, n0, ng)) {
             if (lane == 0) {
                 deg[i] = 0;
                 tri[i] = 0;
             }
             continue;
         }
-        const int words = (ng + 63) / 64;
-        __syncthreads();   // the previous node's readers are done
-        unsigned long long d = 0;
-        for (int w = lane; w < words; w += 64) {
-            const unsigned long long v = bitmap[i * W + w];
-            row[w] = v;
-            d += __popcll(v);
-        }
-        __syncthreads();
-        d = wave_sum_u64(d);
-        unsigned long long t = 0;
-        for_each_neighbour(row, queue, words, lane, [&](int lj) {
-            const unsigned long long* rj = bitmap + (n0 + lj) * W;
-            for (int w = 0; w < words; ++w) t += __popcll(row[w] & rj[w]);
-        });
-        t = wave_sum_u64(t) >> 1;
+        unsigned long long d, t;
+        row_degree_triangles(bitmap, i, row, queue, (ng + 63) / 64, n0, W, d, t);
         if (lane == 0) {
             deg[i] = (int32_t)d;
             tri[i] = (int32_t)t;   // <= C(8191, 2)
@@ -145,15 +104,13 @@ __global__ __launch_bounds__(64) void k_orbit_nodes(const int32_t* __restrict__ 
     int32_t* queue = (int32_t*)(orbit_lds + W + 16);    // [128]
     const int lane = threadIdx.x;
     for (int64_t i = blockIdx.x; i < n_nodes; i += gridDim.x) {   // (uniform over the workgroup)
-        const int g = gid[i];
-        int64_t n0 = 0;
-        int ng = 0;
-        if (g >= 0) stats_graph_range(off, g, n_nodes, max_nodes, n0, ng);
-        const int64_t li = i - n0;
-        if (g < 0 || li < 0 || li >= ng) {   // a row no graph (or no bitmap column) covers: zeros, no share in a sum
+        int g, ng;
+        int64_t n0;
+        if (!graph_of_row(off, gid, n_nodes, max_nodes, i, g, n0, ng)) {   // zeros, no share in a sum
             if (lane < kOrbits) orbits[i * ld + lane] = 0;
             continue;
         }
+        const int64_t li = i - n0;
         const int words = (ng + 63) / 64;
         __syncthreads();   // the previous node's readers are done
         for (int w = lane; w < words; w += 64) row[w] = bitmap[i * W + w];
@@ -329,36 +286,16 @@ size_t gnf_graph_orbits_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32
 int gnf_graph_orbits(const GnfCsr* csr, int32_t max_nodes_per_graph, int64_t* orbits, int64_t ld_orbits, int64_t* orbit_sums,
                      void* ws, size_t ws_bytes, gnf_stream_t stream) {
     const char* what = "gnf_graph_orbits";
-    if (!csr) {
-        set_error("%s: null csr", what);
-        return GNF_EINVAL;
-    }
-    if (max_nodes_per_graph < 0 || max_nodes_per_graph > kOrbitMaxNodes || ld_orbits < kOrbits) {
-        set_error("%s: max_nodes_per_graph=%d ld_orbits=%lld (0 <= max_nodes_per_graph <= %d: the cost per node grows with "
-                  "n_g + d_i d_mean; ld_orbits >= %d)", what, max_nodes_per_graph, (long long)ld_orbits, kOrbitMaxNodes, kOrbits);
-        return GNF_ESHAPE;
-    }
-    if (csr->n_nodes < 0 || csr->n_edges < 0 || csr->n_graphs < 0 || csr->n_graphs > 0x7fffffff) {
-        set_error("%s: n_nodes=%lld n_edges=%lld n_graphs=%lld", what, (long long)csr->n_nodes, (long long)csr->n_edges,
-                  (long long)csr->n_graphs);
+    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kOrbitMaxNodes, "the cost per node grows with n_g + d_i d_mean"))
+        return rc;
+    if (ld_orbits < kOrbits) {
+        set_error("%s: ld_orbits=%lld (ld_orbits >= %d)", what, (long long)ld_orbits, kOrbits);
         return GNF_ESHAPE;
     }
     const int64_t n = csr->n_nodes, b = csr->n_graphs;
-    if (n > 0 && (!csr->node_offsets || b < 1)) {
-        set_error("%s: csr->node_offsets / csr->n_graphs are required", what);
-        return GNF_EINVAL;
-    }
-    if (b > 0 && !csr->node_offsets) {
-        set_error("%s: csr->node_offsets is null with n_graphs=%lld", what, (long long)b);
-        return GNF_EINVAL;
-    }
-    if ((n > 0 && (!csr->rowptr || !orbits || !ws)) || (csr->n_edges > 0 && !csr->col) || (b > 0 && !orbit_sums)) {
+    if ((n > 0 && (!orbits || !ws)) || (b > 0 && !orbit_sums)) {
         set_error("%s: null pointer argument", what);
         return GNF_EINVAL;
-    }
-    if (n > 0 && max_nodes_per_graph == 0) {
-        set_error("%s: max_nodes_per_graph=0 with %lld nodes", what, (long long)n);
-        return GNF_ESHAPE;
     }
     const OrbitWs L = orbit_ws(n, max_nodes_per_graph);
     if (ws_bytes < L.total) {
@@ -373,10 +310,7 @@ int gnf_graph_orbits(const GnfCsr* csr, int32_t max_nodes_per_graph, int64_t* or
     int32_t* gid = (int32_t*)((char*)ws + L.gid);
     int32_t* deg = (int32_t*)((char*)ws + L.deg);
     int32_t* tri = (int32_t*)((char*)ws + L.tri);
-    GNF_HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)n * (size_t)L.W * sizeof(uint64_t), st));
-    hipLaunchKernelGGL(k_stats_bitmap, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->rowptr, csr->col, n, csr->n_edges,
-                       csr->node_offsets, b, max_nodes_per_graph, L.W, bitmap, gid);
-    GNF_LAUNCH_CHECK("k_stats_bitmap");
+    if (int rc = build_graph_bitmap(csr, max_nodes_per_graph, L.W, bitmap, gid, st)) return rc;
     const size_t lds = (size_t)L.W * sizeof(uint64_t) + 128 * sizeof(int32_t);   // <= 1.5 KB
     hipLaunchKernelGGL(k_orbit_degtri, dim3(stats_grid(n)), dim3(64), lds, st, csr->node_offsets, n, max_nodes_per_graph, L.W,
                        bitmap, gid, deg, tri);

@@ -3,8 +3,8 @@
 // number graph-generation papers since GRAN report (the MMD itself is gnf_hist_mmd_f64 on the histograms).  The reference
 // stops at pickling the graphs (generate_graphs.py:68-84); nothing in it corresponds to this kernel.
 //
-// Graph model and bitmap: as in gnf_graph_stats.hip (undirected, simple; k_stats_bitmap on a zeroed bitmap), shared through
-// gnf_graph_bitmap.h.  L_ii = 1 if d_i > 0 else 0, L_ij = -1 / sqrt(d_i d_j) for an edge, else 0.
+// Graph model and bitmap: as in gnf_graph_stats.hip (undirected, simple), built by build_graph_bitmap (gnf_graph_bitmap.h:
+// k_stats_bitmap on a zeroed bitmap).  L_ii = 1 if d_i > 0 else 0, L_ij = -1 / sqrt(d_i d_j) for an edge, else 0.
 //
 // Launches: k_stats_bitmap; k_spectra<LDS, NT> - one workgroup of NT threads per graph slot, everything in fp64:
 //   1. degrees by popcount of the bitmap rows; L formed densely (both triangles) in the slot's matrix S [n_g][n_g].
@@ -227,44 +227,20 @@ size_t gnf_graph_spectra_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int3
 int gnf_graph_spectra(const GnfCsr* csr, int32_t max_nodes_per_graph, double* eigenvalues, int32_t* hist, int32_t bins, double lo,
                       double hi, void* ws, size_t ws_bytes, gnf_stream_t stream) {
     const char* what = "gnf_graph_spectra";
-    if (!csr) {
-        set_error("%s: null csr", what);
-        return GNF_EINVAL;
-    }
-    if (max_nodes_per_graph < 0 || max_nodes_per_graph > kSpectraMaxNodes) {
-        set_error("%s: max_nodes_per_graph=%d (0 <= max_nodes_per_graph <= %d: a dense eigenvalue solver, n^3 work per graph)",
-                  what, max_nodes_per_graph, kSpectraMaxNodes);
-        return GNF_ESHAPE;
-    }
+    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kSpectraMaxNodes, "a dense eigenvalue solver, n^3 work per graph"))
+        return rc;
     if (bins < 0 || (bins > 0 && !(hi > lo))) {
         set_error("%s: bins=%d lo=%g hi=%g (bins >= 0, and lo < hi with bins > 0)", what, bins, lo, hi);
         return GNF_ESHAPE;
     }
-    if (csr->n_nodes < 0 || csr->n_edges < 0 || csr->n_graphs < 0 || csr->n_graphs > 0x7fffffff) {
-        set_error("%s: n_nodes=%lld n_edges=%lld n_graphs=%lld", what, (long long)csr->n_nodes, (long long)csr->n_edges,
-                  (long long)csr->n_graphs);
-        return GNF_ESHAPE;
-    }
     const int64_t n = csr->n_nodes, b = csr->n_graphs;
-    if (n > 0 && (!csr->node_offsets || b < 1)) {
-        set_error("%s: csr->node_offsets / csr->n_graphs are required", what);
-        return GNF_EINVAL;
-    }
-    if (b > 0 && !csr->node_offsets) {
-        set_error("%s: csr->node_offsets is null with n_graphs=%lld", what, (long long)b);
-        return GNF_EINVAL;
-    }
-    if ((n > 0 && (!csr->rowptr || !eigenvalues || !ws)) || (csr->n_edges > 0 && !csr->col)) {
+    if (n > 0 && (!eigenvalues || !ws)) {
         set_error("%s: null pointer argument", what);
         return GNF_EINVAL;
     }
     if (bins > 0 && b > 0 && !hist) {
         set_error("%s: hist is null with bins=%d", what, bins);
         return GNF_EINVAL;
-    }
-    if (n > 0 && max_nodes_per_graph == 0) {
-        set_error("%s: max_nodes_per_graph=0 with %lld nodes", what, (long long)n);
-        return GNF_ESHAPE;
     }
     const SpectraWs L = spectra_ws(b, n, max_nodes_per_graph);
     if (ws_bytes < L.total) {
@@ -280,10 +256,7 @@ int gnf_graph_spectra(const GnfCsr* csr, int32_t max_nodes_per_graph, double* ei
     unsigned long long* bitmap = (unsigned long long*)((char*)ws + L.stats.bitmap);
     int32_t* gid = (int32_t*)((char*)ws + L.stats.gid);
     GNF_HIP_TRY(hipMemsetAsync(eigenvalues, 0, (size_t)n * sizeof(double), st));   // rows no graph (or no column) covers
-    GNF_HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)n * (size_t)L.stats.W * sizeof(uint64_t), st));
-    hipLaunchKernelGGL(k_stats_bitmap, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->rowptr, csr->col, n, csr->n_edges,
-                       csr->node_offsets, b, max_nodes_per_graph, L.stats.W, bitmap, gid);
-    GNF_LAUNCH_CHECK("k_stats_bitmap");
+    if (int rc = build_graph_bitmap(csr, max_nodes_per_graph, L.stats.W, bitmap, gid, st)) return rc;
     GNF_ONCE_PER_DEVICE(
         GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_spectra<true, kSpectraBlockLds>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

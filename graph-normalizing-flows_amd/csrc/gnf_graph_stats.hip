@@ -7,10 +7,11 @@
 // duplicate edges count once, an edge present in one direction only counts in both, and the order of the senders inside a
 // CSR row does not matter.  That is what the adjacency bitmap gives for free: one 64-bit word per (node, 64 graph-local
 // columns) - the decoder's shape (gnf_decode_edges.hip) - zeroed on the stream, then for every CSR entry (receiver i,
-// sender j), i != j, bit (i, j - n0) and bit (j, i - n0) are set with a global 64-bit atomicOr.  OR is order-independent: the
-// bitmap, and everything below, is deterministic.
+// sender j), i != j, bit (i, j - n0) and bit (j, i - n0) are set with a global 64-bit atomicOr (build_graph_bitmap,
+// gnf_graph_bitmap.hip).  OR is order-independent: the bitmap, and everything below, is deterministic.
 //
-// Per node (one wave, one workgroup): deg_i = sum_w popc(row_i[w]);  tri_i = 1/2 sum_{j in N(i)} sum_w popc(row_i[w] & row_j[w]).
+// Per node (one wave, one workgroup; row_degree_triangles, gnf_graph_bitmap.h): deg_i = sum_w popc(row_i[w]);
+// tri_i = 1/2 sum_{j in N(i)} sum_w popc(row_i[w] & row_j[w]).
 // row_i sits in LDS; the set bits of the row are compacted into a 128-entry LDS queue and handed out to the lanes 64 at a time
 // (lane = one neighbour j, reading row_j from global memory), so a node of any degree keeps the wave full.
 //
@@ -34,34 +35,6 @@ namespace gnf {
 
 static constexpr int kStatsMaxNodes = 65536;   // tri_i <= C(n - 1, 2) must fit int32
 
-// one wave per CSR row i: lanes take its entries 64 at a time.  An entry whose endpoints are not both inside the graph's
-// [n0, n0 + ng) window is dropped (never an access outside the bitmap).
-__global__ __launch_bounds__(256) void k_stats_bitmap(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                      int64_t n_nodes, int64_t n_edges, const int32_t* __restrict__ off,
-                                                      int64_t n_graphs, int max_nodes, int64_t W,
-                                                      unsigned long long* __restrict__ bitmap, int32_t* __restrict__ gid) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_nodes; i += (int64_t)gridDim.x * 4) {
-        const int g = stats_graph_of(off, n_graphs, i);
-        if (lane == 0) gid[i] = g;
-        if (g < 0) continue;
-        int64_t n0;
-        int ng;
-        stats_graph_range(off, g, n_nodes, max_nodes, n0, ng);
-        const int64_t li = i - n0;
-        if (li < 0 || li >= ng) continue;
-        int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
-        if (e0 < 0) e0 = 0;
-        if (e1 > n_edges) e1 = n_edges;
-        for (int64_t e = e0 + lane; e < e1; e += 64) {
-            const int64_t lj = (int64_t)col[e] - n0;
-            if (lj < 0 || lj >= ng || lj == li) continue;
-            atomicOr(&bitmap[i * W + (lj >> 6)], 1ull << (lj & 63));
-            atomicOr(&bitmap[(n0 + lj) * W + (li >> 6)], 1ull << (li & 63));
-        }
-    }
-}
-
 // one wave = one workgroup per node.  LDS: row_i [W] words | queue [128] graph-local neighbour ids.
 __global__ __launch_bounds__(64) void k_stats_nodes(const int32_t* __restrict__ off, int64_t n_nodes, int max_nodes, int64_t W,
                                                     int bins, const unsigned long long* __restrict__ bitmap,
@@ -75,52 +48,17 @@ __global__ __launch_bounds__(64) void k_stats_nodes(const int32_t* __restrict__ 
     int32_t* queue = (int32_t*)(stats_lds + W);  // [128]
     const int lane = threadIdx.x;
     for (int64_t i = blockIdx.x; i < n_nodes; i += gridDim.x) {   // (uniform over the workgroup)
-        const int g = gid[i];
-        int64_t n0 = 0;
-        int ng = 0;
-        if (g >= 0) stats_graph_range(off, g, n_nodes, max_nodes, n0, ng);
-        const int64_t li = i - n0;
-        if (g < 0 || li < 0 || li >= ng) {   // a row no graph (or no bitmap column) covers: the caller's error, no histogram entry
+        int g, ng;
+        int64_t n0;
+        if (!graph_of_row(off, gid, n_nodes, max_nodes, i, g, n0, ng)) {   // the caller's error: zeros, no histogram entry
             if (lane == 0) {
                 degree[i] = 0;
                 triangles[i] = 0;
             }
             continue;
         }
-        const int words = (ng + 63) / 64;
-        __syncthreads();   // the previous node's readers are done
-        unsigned long long d = 0;
-        for (int w = lane; w < words; w += 64) {
-            const unsigned long long v = bitmap[i * W + w];
-            row[w] = v;
-            d += __popcll(v);
-        }
-        __syncthreads();
-        d = wave_sum_u64(d);
-        unsigned long long t = 0;
-        // common neighbours of i and the neighbour a lane holds
-        auto visit = [&](int lj) {
-            const unsigned long long* rj = bitmap + (n0 + lj) * W;
-            for (int w = 0; w < words; ++w) t += __popcll(row[w] & rj[w]);
-        };
-        int q = 0;   // entries waiting in the queue (< 64 between words)
-        for (int w = 0; w < words; ++w) {
-            const unsigned long long word = row[w];
-            if (word == 0) continue;
-            if ((word >> lane) & 1ull) queue[q + __popcll(word & ((1ull << lane) - 1ull))] = w * 64 + lane;
-            q += __popcll(word);
-            __syncthreads();
-            if (q >= 64) {
-                visit(queue[lane]);
-                const int32_t tail = queue[64 + lane];
-                __syncthreads();
-                q -= 64;
-                if (lane < q) queue[lane] = tail;
-                __syncthreads();
-            }
-        }
-        if (lane < q) visit(queue[lane]);
-        t = wave_sum_u64(t) >> 1;
+        unsigned long long d, t;
+        row_degree_triangles(bitmap, i, row, queue, (ng + 63) / 64, n0, W, d, t);
         if (lane == 0) {
             degree[i] = (int32_t)d;
             triangles[i] = (int32_t)t;
@@ -257,37 +195,16 @@ int gnf_graph_stats(const GnfCsr* csr, int32_t max_nodes_per_graph, int32_t clus
                     int32_t* triangles, int32_t* degree_hist, int32_t* clustering_hist, int64_t* n_edges,
                     int64_t* n_triangles, void* ws, size_t ws_bytes, gnf_stream_t stream) {
     const char* what = "gnf_graph_stats";
-    if (!csr) {
-        set_error("%s: null csr", what);
-        return GNF_EINVAL;
-    }
-    if (clustering_bins < 1 || max_nodes_per_graph < 0 || max_nodes_per_graph > kStatsMaxNodes) {
-        set_error("%s: clustering_bins=%d max_nodes_per_graph=%d (bins >= 1, 0 <= max_nodes_per_graph <= %d: a node's triangle "
-                  "count must fit int32)", what, clustering_bins, max_nodes_per_graph, kStatsMaxNodes);
-        return GNF_ESHAPE;
-    }
-    if (csr->n_nodes < 0 || csr->n_edges < 0 || csr->n_graphs < 0 || csr->n_graphs > 0x7fffffff) {
-        set_error("%s: n_nodes=%lld n_edges=%lld n_graphs=%lld", what, (long long)csr->n_nodes, (long long)csr->n_edges,
-                  (long long)csr->n_graphs);
+    if (int rc = graph_csr_ok(what, csr, max_nodes_per_graph, kStatsMaxNodes, "a node's triangle count must fit int32")) return rc;
+    if (clustering_bins < 1) {
+        set_error("%s: clustering_bins=%d (bins >= 1)", what, clustering_bins);
         return GNF_ESHAPE;
     }
     const int64_t n = csr->n_nodes, b = csr->n_graphs;
-    if (n > 0 && (!csr->node_offsets || b < 1)) {
-        set_error("%s: csr->node_offsets / csr->n_graphs are required", what);
-        return GNF_EINVAL;
-    }
-    if (b > 0 && !csr->node_offsets) {
-        set_error("%s: csr->node_offsets is null with n_graphs=%lld", what, (long long)b);
-        return GNF_EINVAL;
-    }
-    if ((n > 0 && (!csr->rowptr || !degree || !triangles || !ws)) || (csr->n_edges > 0 && !csr->col) ||
+    if ((n > 0 && (!degree || !triangles || !ws)) ||
         (b > 0 && (!clustering_hist || !n_edges || !n_triangles || (max_nodes_per_graph > 0 && !degree_hist)))) {
         set_error("%s: null pointer argument", what);
         return GNF_EINVAL;
-    }
-    if (n > 0 && max_nodes_per_graph == 0) {
-        set_error("%s: max_nodes_per_graph=0 with %lld nodes", what, (long long)n);
-        return GNF_ESHAPE;
     }
     const StatsWs L = stats_ws(n, max_nodes_per_graph);
     if (ws_bytes < L.total) {
@@ -304,10 +221,7 @@ int gnf_graph_stats(const GnfCsr* csr, int32_t max_nodes_per_graph, int32_t clus
     if (n == 0) return GNF_OK;
     unsigned long long* bitmap = (unsigned long long*)((char*)ws + L.bitmap);
     int32_t* gid = (int32_t*)((char*)ws + L.gid);
-    GNF_HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)n * (size_t)L.W * sizeof(uint64_t), st));
-    hipLaunchKernelGGL(k_stats_bitmap, dim3(stats_grid((n + 3) / 4)), dim3(256), 0, st, csr->rowptr, csr->col, n, csr->n_edges,
-                       csr->node_offsets, b, max_nodes_per_graph, L.W, bitmap, gid);
-    GNF_LAUNCH_CHECK("k_stats_bitmap");
+    if (int rc = build_graph_bitmap(csr, max_nodes_per_graph, L.W, bitmap, gid, st)) return rc;
     const size_t lds = (size_t)L.W * sizeof(uint64_t) + 128 * sizeof(int32_t);   // <= 8.5 KB
     hipLaunchKernelGGL(k_stats_nodes, dim3(stats_grid(n)), dim3(64), lds, st, csr->node_offsets, n, max_nodes_per_graph, L.W,
                        clustering_bins, bitmap, gid, degree, triangles, degree_hist, clustering_hist,

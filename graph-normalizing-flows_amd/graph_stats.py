@@ -66,6 +66,53 @@ def _node_bound(graph, max_nodes_per_graph, n_node_host, limit):
     return cap
 
 
+def _call(dev, entry, sizes, args, query=None, ws=None):
+    """One library call on dev's current stream: entry(*args, workspace, workspace bytes, stream), the workspace as
+    `query` (entry + "_workspace_bytes" unless given) sizes it for `sizes`.  Returns the workspace; ws= passes on the one an
+    earlier call left (gnf_graph_subgraph_fill reads what gnf_graph_subgraph_count wrote)."""
+    lib = _abi.lib()
+    ws_bytes = getattr(lib, query or entry + "_workspace_bytes")(*sizes)
+    if ws is None:
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(getattr(lib, entry)(*args, _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), entry)
+    return ws
+
+
+class _Batch:
+    """A GraphsTuple as the batch entry points on the adjacency bitmap take it.  Three steps, so that every caller keeps its
+    own argument checks where they stand between them: the constructor refuses a batch that is not on a HIP device and reads
+    the sizes; bound() is the first step that may copy n_node to the host; call() is the first that may launch (csr_of:
+    gnf_build_csr, unless the batch came from decode_graphs or keep_subgraphs)."""
+
+    def __init__(self, name, graph):
+        self.graph, self.dev = graph, graph.senders.device
+        if self.dev.type != "cuda" or graph.n_node.device.type != "cuda":
+            raise _abi.GnfError(f"{name} runs on a HIP device only (no CPU path)")
+        self.n = int(graph.nodes.shape[0])
+        self.b = int(graph.n_node.shape[0])
+
+    def bound(self, max_nodes_per_graph, n_node_host, limit):
+        self.cap = _node_bound(self.graph, max_nodes_per_graph, n_node_host, limit)
+        return self.cap
+
+    def call(self, entry, *args, query=None):
+        """entry(csr with node offsets, max_nodes_per_graph, *args, workspace, workspace bytes, stream)"""
+        from .graphs import csr_desc, csr_of
+        csr = csr_of(self.graph)
+        desc = csr_desc(self.graph, csr, node_offsets=True)
+        return _call(self.dev, entry, (self.b, self.n, self.cap), (C.byref(desc), self.cap) + args, query)
+
+
+def _mmd2(name, out5, what):
+    """The biased V-statistic sum_AA / cnt_a^2 + sum_BB / cnt_b^2 - 2 sum_AB / (cnt_a cnt_b) of out5 = {sum AA, sum BB, sum AB,
+    cnt_a, cnt_b} as a 0-d device tensor; reading the two counts is the one copy to the host."""
+    cnt_a, cnt_b = out5[3:5].tolist()
+    if cnt_a < 1 or cnt_b < 1:
+        raise ValueError(f"{name}: {int(cnt_a)} / {int(cnt_b)} non-empty {what} in the two sets; both need one")
+    return out5[0] / (out5[3] * out5[3]) + out5[1] / (out5[4] * out5[4]) - 2.0 * out5[2] / (out5[3] * out5[4])
+
+
 def graph_stats(graph, max_nodes_per_graph=None, n_node_host=None, clustering_bins=100):
     """Degree and clustering statistics of every graph of a GraphsTuple, as a dict of device tensors:
       "degree", "triangles"   int32 [N]: neighbours of each node, triangles through it
@@ -77,32 +124,20 @@ def graph_stats(graph, max_nodes_per_graph=None, n_node_host=None, clustering_bi
     The CSR comes from graphs.csr_of: on the result of decode_graphs / generate_graphs no gnf_build_csr runs.
     With max_nodes_per_graph (any upper bound on n_node) or n_node_host (the sizes as a host sequence) nothing is copied to
     the host and nothing synchronises, so the call can be captured; otherwise n_node is read once, as pred_adj does."""
-    from .graphs import csr_desc, csr_of
-    lib = _abi.lib()
-    dev = graph.senders.device
-    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
-        raise _abi.GnfError("graph_stats runs on a HIP device only (no CPU path)")
-    n = int(graph.nodes.shape[0])
-    b = int(graph.n_node.shape[0])
+    batch = _Batch("graph_stats", graph)
+    dev, n, b = batch.dev, batch.n, batch.b
     bins = int(clustering_bins)
-    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
+    cap = batch.bound(max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
     if bins < 1:
         raise ValueError(f"clustering_bins={bins}")
-    csr = csr_of(graph)
-    desc = csr_desc(graph, csr, node_offsets=True)
     out = {"degree": torch.empty(n, dtype=torch.int32, device=dev),
            "triangles": torch.empty(n, dtype=torch.int32, device=dev),
            "degree_hist": torch.empty((b, cap), dtype=torch.int32, device=dev),
            "clustering_hist": torch.empty((b, bins), dtype=torch.int32, device=dev),
            "n_edges": torch.empty(b, dtype=torch.int64, device=dev),
            "n_triangles": torch.empty(b, dtype=torch.int64, device=dev)}
-    ws_bytes = lib.gnf_graph_stats_workspace_bytes(b, n, cap)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_graph_stats(C.byref(desc), cap, bins, _abi.ptr(out["degree"]), _abi.ptr(out["triangles"]),
-                                       _abi.ptr(out["degree_hist"]), _abi.ptr(out["clustering_hist"]),
-                                       _abi.ptr(out["n_edges"]), _abi.ptr(out["n_triangles"]), _abi.ptr(ws), ws_bytes,
-                                       _abi.stream_ptr(dev)), "gnf_graph_stats")
+    batch.call("gnf_graph_stats", bins, *(_abi.ptr(out[k]) for k in ("degree", "triangles", "degree_hist", "clustering_hist",
+                                                                        "n_edges", "n_triangles")))
     d = out["degree"].to(torch.float64)
     pairs = d * (d - 1.0)
     out["clustering"] = torch.where(pairs > 0, 2.0 * out["triangles"].to(torch.float64) / pairs.clamp(min=1.0),
@@ -113,7 +148,6 @@ def graph_stats(graph, max_nodes_per_graph=None, n_node_host=None, clustering_bi
 def _hist_mmd_sums(hists_a, hists_b, kernel, sigma, distance_scaling):
     if kernel not in _KERNELS:
         raise ValueError(f"kernel={kernel!r}: one of {sorted(_KERNELS)}")
-    lib = _abi.lib()
     for h in (hists_a, hists_b):
         if not isinstance(h, torch.Tensor) or h.device.type != "cuda":
             raise _abi.GnfError("hist_mmd runs on a HIP device only (no CPU path)")
@@ -125,12 +159,8 @@ def _hist_mmd_sums(hists_a, hists_b, kernel, sigma, distance_scaling):
     a, la = int(ha.shape[0]), int(ha.shape[1])
     b, lb = int(hb.shape[0]), int(hb.shape[1])
     out5 = torch.empty(5, dtype=torch.float64, device=dev)
-    ws_bytes = lib.gnf_hist_mmd_workspace_bytes(a, b)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_hist_mmd_f64(_abi.ptr(ha), a, la, la, _abi.ptr(hb), b, lb, lb, _KERNELS[kernel], float(sigma),
-                                        float(distance_scaling), _abi.ptr(out5), _abi.ptr(ws), ws_bytes,
-                                        _abi.stream_ptr(dev)), "gnf_hist_mmd_f64")
+    _call(dev, "gnf_hist_mmd_f64", (a, b), (_abi.ptr(ha), a, la, la, _abi.ptr(hb), b, lb, lb, _KERNELS[kernel], float(sigma),
+                                            float(distance_scaling), _abi.ptr(out5)), query="gnf_hist_mmd_workspace_bytes")
     return out5
 
 
@@ -141,11 +171,7 @@ def hist_mmd(hists_a, hists_b, kernel="gaussian_emd", sigma=1.0, distance_scalin
     ("gaussian_emd") or their total variation ("gaussian_tv") - the biased V-statistic, diagonals in, as in GraphRNN's
     evaluation.  All-zero rows (graphs without nodes) are left out.  Raises ValueError when a set has no other row: reading
     the two counts is the call's only copy to the host."""
-    out5 = _hist_mmd_sums(hists_a, hists_b, kernel, sigma, distance_scaling)
-    cnt_a, cnt_b = out5[3:5].tolist()
-    if cnt_a < 1 or cnt_b < 1:
-        raise ValueError(f"hist_mmd: {int(cnt_a)} / {int(cnt_b)} non-empty histograms in the two sets; both need one")
-    return out5[0] / (out5[3] * out5[3]) + out5[1] / (out5[4] * out5[4]) - 2.0 * out5[2] / (out5[3] * out5[4])
+    return _mmd2("hist_mmd", _hist_mmd_sums(hists_a, hists_b, kernel, sigma, distance_scaling), "histograms")
 
 
 def graph_orbits(graph, max_nodes_per_graph=None, n_node_host=None):
@@ -159,23 +185,11 @@ def graph_orbits(graph, max_nodes_per_graph=None, n_node_host=None):
     The CSR comes from graphs.csr_of: on the result of decode_graphs / generate_graphs no gnf_build_csr runs.  As for
     graph_stats, with max_nodes_per_graph (any upper bound on n_node, at most 8192) or n_node_host nothing is copied to the
     host and nothing synchronises, so the call can be captured; otherwise n_node is read once."""
-    from .graphs import csr_desc, csr_of
-    lib = _abi.lib()
-    dev = graph.senders.device
-    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
-        raise _abi.GnfError("graph_orbits runs on a HIP device only (no CPU path)")
-    n = int(graph.nodes.shape[0])
-    b = int(graph.n_node.shape[0])
-    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, ORBIT_MAX_NODES_PER_GRAPH)
-    csr = csr_of(graph)
-    desc = csr_desc(graph, csr, node_offsets=True)
-    out = {"orbits": torch.empty((n, N_ORBITS), dtype=torch.int64, device=dev),
-           "orbit_sums": torch.empty((b, N_ORBITS), dtype=torch.int64, device=dev)}
-    ws_bytes = lib.gnf_graph_orbits_workspace_bytes(b, n, cap)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_graph_orbits(C.byref(desc), cap, _abi.ptr(out["orbits"]), N_ORBITS, _abi.ptr(out["orbit_sums"]),
-                                        _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_graph_orbits")
+    batch = _Batch("graph_orbits", graph)
+    batch.bound(max_nodes_per_graph, n_node_host, ORBIT_MAX_NODES_PER_GRAPH)
+    out = {"orbits": torch.empty((batch.n, N_ORBITS), dtype=torch.int64, device=batch.dev),
+           "orbit_sums": torch.empty((batch.b, N_ORBITS), dtype=torch.int64, device=batch.dev)}
+    batch.call("gnf_graph_orbits", _abi.ptr(out["orbits"]), N_ORBITS, _abi.ptr(out["orbit_sums"]))
     out["n_node"] = graph.n_node.to(torch.int32)
     out["orbit_mean"] = out["orbit_sums"].to(torch.float64) / out["n_node"].clamp(min=1).to(torch.float64).unsqueeze(1)
     return out
@@ -194,7 +208,6 @@ def _orbit_set(x, dev=None):
 
 
 def _orbit_mmd_sums(orbits_a, orbits_b, sigma):
-    lib = _abi.lib()
     xa, ca = _orbit_set(orbits_a)
     dev = xa.device
     xb, cb = _orbit_set(orbits_b, dev)
@@ -202,12 +215,8 @@ def _orbit_mmd_sums(orbits_a, orbits_b, sigma):
     if int(xb.shape[1]) != width:
         raise ValueError(f"orbit_mmd: vectors of {width} and {int(xb.shape[1])} entries")
     out5 = torch.empty(5, dtype=torch.float64, device=dev)
-    ws_bytes = lib.gnf_vec_mmd_workspace_bytes(a, b)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_vec_mmd_i64(_abi.ptr(xa), _abi.ptr(ca), a, width, _abi.ptr(xb), _abi.ptr(cb), b, width, width,
-                                       float(sigma), _abi.ptr(out5), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                   "gnf_vec_mmd_i64")
+    _call(dev, "gnf_vec_mmd_i64", (a, b), (_abi.ptr(xa), _abi.ptr(ca), a, width, _abi.ptr(xb), _abi.ptr(cb), b, width, width,
+                                           float(sigma), _abi.ptr(out5)), query="gnf_vec_mmd_workspace_bytes")
     return out5
 
 
@@ -217,11 +226,7 @@ def orbit_mmd(orbits_a, orbits_b, sigma=30.0):
     exp(-|x - y|^2 / (2 sigma^2)), sigma = 30 as in GraphRNN's orbit evaluation: the same biased V-statistic as hist_mmd, as
     a 0-d float64 device tensor.  Graphs without nodes are left out.  Two identical sets give exactly 0.  Raises ValueError
     when a set has no other graph: reading the two counts is the call's only copy to the host."""
-    out5 = _orbit_mmd_sums(orbits_a, orbits_b, sigma)
-    cnt_a, cnt_b = out5[3:5].tolist()
-    if cnt_a < 1 or cnt_b < 1:
-        raise ValueError(f"orbit_mmd: {int(cnt_a)} / {int(cnt_b)} non-empty graphs in the two sets; both need one")
-    return out5[0] / (out5[3] * out5[3]) + out5[1] / (out5[4] * out5[4]) - 2.0 * out5[2] / (out5[3] * out5[4])
+    return _mmd2("orbit_mmd", _orbit_mmd_sums(orbits_a, orbits_b, sigma), "graphs")
 
 
 def graph_spectra(graph, max_nodes_per_graph=None, n_node_host=None, bins=200, lo=-1e-5, hi=2.0):
@@ -236,27 +241,14 @@ def graph_spectra(graph, max_nodes_per_graph=None, n_node_host=None, bins=200, l
     n_node, at most 2048) or n_node_host nothing is copied to the host and nothing synchronises, so the call can be captured;
     otherwise n_node is read once.  Up to 139 nodes per graph the matrices live in LDS, above that in a workspace of
     min(B, 256) * max_nodes_per_graph^2 doubles."""
-    from .graphs import csr_desc, csr_of
-    lib = _abi.lib()
-    dev = graph.senders.device
-    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
-        raise _abi.GnfError("graph_spectra runs on a HIP device only (no CPU path)")
-    n = int(graph.nodes.shape[0])
-    b = int(graph.n_node.shape[0])
+    batch = _Batch("graph_spectra", graph)
     bins = int(bins)
-    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, SPECTRA_MAX_NODES_PER_GRAPH)
+    batch.bound(max_nodes_per_graph, n_node_host, SPECTRA_MAX_NODES_PER_GRAPH)
     if bins < 1 or not float(hi) > float(lo):
         raise ValueError(f"bins={bins} lo={lo} hi={hi}")
-    csr = csr_of(graph)
-    desc = csr_desc(graph, csr, node_offsets=True)
-    out = {"eigenvalues": torch.empty(n, dtype=torch.float64, device=dev),
-           "spectral_hist": torch.empty((b, bins), dtype=torch.int32, device=dev)}
-    ws_bytes = lib.gnf_graph_spectra_workspace_bytes(b, n, cap)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_graph_spectra(C.byref(desc), cap, _abi.ptr(out["eigenvalues"]), _abi.ptr(out["spectral_hist"]), bins,
-                                         float(lo), float(hi), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                   "gnf_graph_spectra")
+    out = {"eigenvalues": torch.empty(batch.n, dtype=torch.float64, device=batch.dev),
+           "spectral_hist": torch.empty((batch.b, bins), dtype=torch.int32, device=batch.dev)}
+    batch.call("gnf_graph_spectra", _abi.ptr(out["eigenvalues"]), _abi.ptr(out["spectral_hist"]), bins, float(lo), float(hi))
     out["n_node"] = graph.n_node.to(torch.int32)
     return out
 
@@ -294,22 +286,11 @@ def graph_components(graph, max_nodes_per_graph=None, n_node_host=None):
     graph_stats, with max_nodes_per_graph (any upper bound on n_node, at most 65536) or n_node_host nothing is copied to the
     host and nothing synchronises, so the call can be captured; otherwise n_node is read once.  A level-synchronous search:
     one pair of workgroup barriers per level, a path on n nodes costs up to n levels."""
-    from .graphs import csr_desc, csr_of
-    lib = _abi.lib()
-    dev = graph.senders.device
-    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
-        raise _abi.GnfError("graph_components runs on a HIP device only (no CPU path)")
-    n = int(graph.nodes.shape[0])
-    b = int(graph.n_node.shape[0])
-    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
-    csr = csr_of(graph)
-    desc = csr_desc(graph, csr, node_offsets=True)
-    out = {k: torch.empty(n if k in COMPONENT_KEYS[:2] else b, dtype=torch.int32, device=dev) for k in COMPONENT_KEYS}
-    ws_bytes = lib.gnf_graph_components_workspace_bytes(b, n, cap)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_graph_components(C.byref(desc), cap, *(_abi.ptr(out[k]) for k in COMPONENT_KEYS), _abi.ptr(ws),
-                                            ws_bytes, _abi.stream_ptr(dev)), "gnf_graph_components")
+    batch = _Batch("graph_components", graph)
+    batch.bound(max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
+    out = {k: torch.empty(batch.n if k in COMPONENT_KEYS[:2] else batch.b, dtype=torch.int32, device=batch.dev)
+           for k in COMPONENT_KEYS}
+    batch.call("gnf_graph_components", *(_abi.ptr(out[k]) for k in COMPONENT_KEYS))
     return out
 
 
@@ -332,13 +313,9 @@ def keep_subgraphs(graph, keep="largest_component", self_loops=False, max_nodes_
     Exact-size mode only: the call reads N' and E' once (one 16-byte copy, its only synchronisation when max_nodes_per_graph
     or n_node_host says how large the graphs are) and allocates exactly that.  A capacity / capture mode, as decode_graphs
     has one, is out of scope here (the two entry points take capacities; this wrapper does not)."""
-    from .graphs import Csr, GraphsTuple, csr_desc, csr_of, seed_csr_cache
-    lib = _abi.lib()
-    dev = graph.senders.device
-    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
-        raise _abi.GnfError("keep_subgraphs runs on a HIP device only (no CPU path)")
-    n = int(graph.nodes.shape[0])
-    b = int(graph.n_node.shape[0])
+    from .graphs import Csr, GraphsTuple, seed_csr_cache
+    batch = _Batch("keep_subgraphs", graph)
+    dev, n, b = batch.dev, batch.n, batch.b
     mask = None
     if isinstance(keep, torch.Tensor):
         if keep.dim() != 1 or int(keep.shape[0]) != n or keep.dtype not in (torch.bool, torch.uint8):
@@ -350,29 +327,23 @@ def keep_subgraphs(graph, keep="largest_component", self_loops=False, max_nodes_
         rule = _KEEP_RULES[keep]
     else:
         raise ValueError(f"keep={keep!r}: one of {sorted(_KEEP_RULES)} or a bool / uint8 tensor [N]")
-    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
+    cap = batch.bound(max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
     if n * (cap + 1) > 2 ** 31 - 1:
         raise ValueError(f"{n} nodes x (max_nodes_per_graph={cap} + 1) exceeds the int32 edge ids")
-    csr = csr_of(graph)
-    desc = csr_desc(graph, csr, node_offsets=True)
     new_id = torch.empty(n, dtype=torch.int32, device=dev)
     new_n_node = torch.zeros(b, dtype=torch.int32, device=dev)
     n_edge = torch.zeros(b, dtype=torch.int32, device=dev)
     rowptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
     totals = torch.zeros(2, dtype=torch.int64, device=dev)     # (an empty batch: the call writes nothing)
-    ws_bytes = lib.gnf_graph_subgraph_workspace_bytes(b, n, cap)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_graph_subgraph_count(C.byref(desc), cap, rule, _abi.ptr(mask), int(bool(self_loops)), _abi.ptr(new_id),
-                                                _abi.ptr(new_n_node), _abi.ptr(rowptr), _abi.ptr(n_edge), _abi.ptr(totals),
-                                                _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_graph_subgraph_count")
-        n_new, e_new = totals.tolist()
-        node_index = torch.empty(n_new, dtype=torch.int32, device=dev)
-        senders = torch.empty(e_new, dtype=torch.int32, device=dev)
-        receivers = torch.empty(e_new, dtype=torch.int32, device=dev)
-        _abi.check(lib.gnf_graph_subgraph_fill(b, n, cap, _abi.ptr(rowptr), n_new, e_new, _abi.ptr(node_index), _abi.ptr(senders),
-                                               _abi.ptr(receivers), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                   "gnf_graph_subgraph_fill")
+    ws = batch.call("gnf_graph_subgraph_count", rule, _abi.ptr(mask), int(bool(self_loops)), _abi.ptr(new_id), _abi.ptr(new_n_node),
+                    _abi.ptr(rowptr), _abi.ptr(n_edge), _abi.ptr(totals), query="gnf_graph_subgraph_workspace_bytes")
+    n_new, e_new = totals.tolist()
+    node_index = torch.empty(n_new, dtype=torch.int32, device=dev)
+    senders = torch.empty(e_new, dtype=torch.int32, device=dev)
+    receivers = torch.empty(e_new, dtype=torch.int32, device=dev)
+    _call(dev, "gnf_graph_subgraph_fill", (b, n, cap), (b, n, cap, _abi.ptr(rowptr), n_new, e_new, _abi.ptr(node_index),
+                                                        _abi.ptr(senders), _abi.ptr(receivers)),
+          query="gnf_graph_subgraph_workspace_bytes", ws=ws)
     rowptr = rowptr[:n_new + 1]
     kept = GraphsTuple(nodes=graph.nodes.index_select(0, node_index.to(graph.nodes.device)),
                        edges=torch.zeros(e_new, dtype=torch.float32, device=dev), receivers=receivers, senders=senders,
@@ -399,13 +370,8 @@ def graph_hashes(graph, iterations=3, labels=None, max_nodes_per_graph=None, n_n
     graph_stats, with max_nodes_per_graph (any upper bound on n_node, at most 65536) or n_node_host nothing is copied to the
     host and nothing synchronises, so the call can be captured; otherwise n_node is read once.  Up to WL_LDS_NODES columns
     one launch does all rounds; above, one launch per round.  Both give the same bits."""
-    from .graphs import csr_desc, csr_of
-    lib = _abi.lib()
-    dev = graph.senders.device
-    if dev.type != "cuda" or graph.n_node.device.type != "cuda":
-        raise _abi.GnfError("graph_hashes runs on a HIP device only (no CPU path)")
-    n = int(graph.nodes.shape[0])
-    b = int(graph.n_node.shape[0])
+    batch = _Batch("graph_hashes", graph)
+    dev, n, b = batch.dev, batch.n, batch.b
     iterations = int(iterations)
     if not 0 <= iterations <= WL_MAX_ITERATIONS:
         raise ValueError(f"iterations={iterations}: 0 .. {WL_MAX_ITERATIONS}")
@@ -415,18 +381,12 @@ def graph_hashes(graph, iterations=3, labels=None, max_nodes_per_graph=None, n_n
         if labels.device.type != "cuda":
             raise _abi.GnfError("graph_hashes runs on a HIP device only (no CPU path)")
         labels = labels.to(dev).contiguous()
-    cap = _node_bound(graph, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
-    csr = csr_of(graph)
-    desc = csr_desc(graph, csr, node_offsets=True)
+    batch.bound(max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
     out = {"hash": torch.empty(b, dtype=torch.int64, device=dev),
            "node_colour": torch.empty(n, dtype=torch.int64, device=dev),
            "n_edges": torch.empty(b, dtype=torch.int64, device=dev)}
-    ws_bytes = lib.gnf_graph_hashes_workspace_bytes(b, n, cap)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_graph_hashes(C.byref(desc), cap, iterations, _abi.ptr(labels), _abi.ptr(out["hash"]),
-                                        _abi.ptr(out["node_colour"]), _abi.ptr(out["n_edges"]), _abi.ptr(ws), ws_bytes,
-                                        _abi.stream_ptr(dev)), "gnf_graph_hashes")
+    batch.call("gnf_graph_hashes", iterations, _abi.ptr(labels), _abi.ptr(out["hash"]), _abi.ptr(out["node_colour"]),
+               _abi.ptr(out["n_edges"]))
     out["n_node"] = graph.n_node.to(torch.int32)
     return out
 
@@ -461,7 +421,6 @@ def uniqueness_novelty(generated, training, iterations=3):
       "counts"              int64 [4]: valid, distinct, novel, distinct and novel
     An empty training set is allowed: everything is novel.  Raises ValueError when no generated graph has a node: reading the
     counts for that check is the call's only copy to the host when both arguments are graph_hashes results."""
-    lib = _abi.lib()
     ha, ca = _hash_set(generated, iterations)
     dev = ha.device
     hb, cb = _hash_set(training, iterations, dev)
@@ -469,12 +428,8 @@ def uniqueness_novelty(generated, training, iterations=3):
     first = torch.empty(a, dtype=torch.int32, device=dev)
     match = torch.empty(a, dtype=torch.int32, device=dev)
     counts = torch.empty(4, dtype=torch.int64, device=dev)
-    ws_bytes = lib.gnf_graph_hash_match_workspace_bytes(a, b)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(lib.gnf_graph_hash_match(_abi.ptr(ha), _abi.ptr(ca), a, _abi.ptr(hb), _abi.ptr(cb), b, _abi.ptr(first),
-                                            _abi.ptr(match), _abi.ptr(counts), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                   "gnf_graph_hash_match")
+    _call(dev, "gnf_graph_hash_match", (a, b), (_abi.ptr(ha), _abi.ptr(ca), a, _abi.ptr(hb), _abi.ptr(cb), b, _abi.ptr(first),
+                                                _abi.ptr(match), _abi.ptr(counts)))
     if counts[0].item() < 1:
         raise ValueError("uniqueness_novelty: no generated graph has a node")
     valid = counts[0].to(torch.float64)

@@ -193,6 +193,60 @@ def test_graph_stats_validation_without_a_gpu():
                   ws_bytes=0) == 0
 
 
+# ---- one single-fault table for the six batch entry points on the adjacency bitmap -----------------------------------------
+OUT = object()   # an output pointer: non-null in a fault row, null in the empty batch
+_BATCH = {       # entry point: (largest max_nodes_per_graph, the arguments between max_nodes_per_graph and the workspace)
+    "gnf_graph_stats": (65536, (100, OUT, OUT, OUT, OUT, OUT, OUT)),
+    "gnf_graph_orbits": (8192, (OUT, 15, OUT)),
+    "gnf_graph_spectra": (2048, (OUT, OUT, 200, -1e-5, 2.0)),
+    "gnf_graph_components": (65536, (OUT,) * 6),
+    "gnf_graph_subgraph_count": (65536, (_abi.GNF_KEEP_LARGEST_COMPONENT, None, 0, OUT, OUT, OUT, OUT, OUT)),
+    "gnf_graph_hashes": (65536, (3, None, OUT, OUT, OUT)),
+}
+_FAULTS = {      # row: (GnfCsr fields that differ from the valid batch, None = a null csr; max_nodes_per_graph; the code)
+    "null_csr": (None, 20, EINVAL),
+    "node_offsets_null_with_graphs": (dict(off=None), 20, EINVAL),
+    "node_offsets_null_without_graphs": (dict(off=None, b=0), 20, EINVAL),
+    "node_offsets_null_with_graphs_without_nodes": (dict(off=None, n=0, e=0), 20, EINVAL),
+    "no_graphs_with_nodes": (dict(b=0), 20, EINVAL),
+    "rowptr_null": (dict(rowptr=None), 20, EINVAL),
+    "col_null_with_edges": (dict(col=None), 20, EINVAL),
+    "negative_n_nodes": (dict(n=-1), 20, ESHAPE),
+    "negative_n_edges": (dict(e=-1), 20, ESHAPE),
+    "negative_n_graphs": (dict(b=-1), 20, ESHAPE),
+    "n_graphs_2_31": (dict(b=2 ** 31), 20, ESHAPE),
+    "cap_negative": ({}, -1, ESHAPE),
+    "cap_above_the_limit": ({}, "limit + 1", ESHAPE),
+    "cap_zero_with_nodes": ({}, 0, ESHAPE),
+    # components, hashes and the extraction hold node ids in int32; stats, orbits and spectra get past the CSR checks and as
+    # far as the workspace size (ws_bytes = 0: the call returns before any device work)
+    "n_nodes_2_31": (dict(n=2 ** 31), 20, {"gnf_graph_stats": EWORKSPACE, "gnf_graph_orbits": EWORKSPACE,
+                                          "gnf_graph_spectra": EWORKSPACE, "gnf_graph_components": ESHAPE,
+                                          "gnf_graph_subgraph_count": ESHAPE, "gnf_graph_hashes": ESHAPE}),
+    "empty_batch_with_null_outputs": (dict(n=0, e=0, b=0, off=None, rowptr=None, col=None), 0, 0),
+}
+
+
+@pytest.mark.parametrize("fault", list(_FAULTS))
+@pytest.mark.parametrize("entry", list(_BATCH))
+def test_batch_entry_points_share_one_fault_table(entry, fault):
+    """A call with exactly one fault returns the same code from gnf_graph_stats, _orbits, _spectra, _components,
+    _subgraph_count and _hashes - before any device work, so without a GPU."""
+    limit, middle = _BATCH[entry]
+    fields, cap, code = _FAULTS[fault]
+    code = code[entry] if isinstance(code, dict) else code
+    cap = limit + 1 if cap == "limit + 1" else cap
+    empty = fault == "empty_batch_with_null_outputs"
+    csr = None
+    if fields is not None:
+        f = dict(dict(rowptr=P, col=P, n=40, e=100, off=P, b=3), **fields)
+        csr = C.byref(_abi.GnfCsr(f["rowptr"], f["col"], f["n"], f["e"], f["off"], f["b"]))
+    out = None if empty else P
+    ws_bytes = 0 if empty or fault == "n_nodes_2_31" else 1 << 20
+    fn = getattr(_abi.lib(), entry)
+    assert fn(csr, cap, *(out if a is OUT else a for a in middle), out, ws_bytes, None) == code
+
+
 def test_hist_mmd_validation_without_a_gpu():
     assert _mmd(la=11) == ESHAPE and _mmd(lb=13) == ESHAPE
     assert _mmd(a=-1) == ESHAPE and _mmd(b=-1) == ESHAPE and _mmd(la=-1) == ESHAPE

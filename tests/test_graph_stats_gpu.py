@@ -116,6 +116,24 @@ def test_more_neighbours_than_a_workgroup_has_lanes():
     assert (got["clustering"] == 1.0).all()
 
 
+def test_a_hub_whose_neighbours_drain_the_queue_twice_with_a_remainder():
+    """The 131-node star with six extra edges next to K70: the hub's 130 neighbours pass through the 128-entry queue as 64 + 64 +
+    2 and its row spans three words that are almost empty in every other row; against the host reference and against the
+    degree and triangle columns of graph_orbits, which shares the walk."""
+    import graph_orbits_ref as OR
+    from gnf_amd.graph_stats import graph_orbits, graph_stats
+    graphs = [(131, OR.big_star()), (70, R.complete(70))]
+    g = _spell(graphs, "one_direction", None)
+    n_node, s, r = R.batch(graphs)
+    want = R.graph_stats(n_node, s, r)
+    assert want["degree"][0] == 130 and want["triangles"][0] == 6 and want["n_triangles"].tolist() == [6, math.comb(70, 3)]
+    got = _host(graph_stats(g))
+    _assert_stats(got, want)
+    orbits = graph_orbits(g)["orbits"].cpu().numpy()
+    np.testing.assert_array_equal(got["degree"], orbits[:, 0])
+    np.testing.assert_array_equal(got["triangles"], orbits[:, 3])
+
+
 def test_decoded_graph_needs_no_csr_build(decoded, monkeypatch):
     from gnf_amd import graphs as G
     from gnf_amd.graph_stats import graph_stats
