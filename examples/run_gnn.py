@@ -8,7 +8,10 @@ Batches come from datasets.GraphDataset (random Gaussian node features on the da
 train.EncoderTrainer.step (train-forward, binary_loss, backward, Adam); every --eval_every_n_steps a random test batch goes
 through encoder.evaluate, and the figures run_gnn.py:441-465 logs are printed.  --binary_dist_fn picks the decoder's distance
 function and --tune_sigmoid (with sigmoid_l2) trains its temp and shift from 10 and 1 (run_gnn.py:146-165); the function, with
-the trained values, is saved with the encoder.  The message-passing --attn_type values train;
+the trained values, is saved with the encoder.  --loss_type triplet trains on the sampled triplet loss instead (run_gnn.py:82-91,
+249-252: --triplet_dist_fn scores the pairs, --triplet_loss_fn margin | relative forms the terms, --num_sampling_loops rounds per
+node; the loss is summed over the nodes, the samples of iteration k are those of --random_seed + k); the edge-error figures and
+the evaluation then use --triplet_adj_dist_fn, which is also what is saved.  The message-passing --attn_type values train;
 the attention ones exit with the library's GNF_EUNSUPPORTED text (their encoder backward is not built).
 
 As in the reference, a pair whose logit lies inside Keras' clip gets no gradient: unit-scale random
@@ -27,12 +30,19 @@ sys.path.insert(0, ROOT)
 from gnf_amd import _abi, adj_loss, datasets as D, encoder as E, gnn   # noqa: E402
 from gnf_amd.flow import scaled_hacky_sigmoid_l2                        # noqa: E402
 from gnf_amd.train import EncoderTrainer                                # noqa: E402
+from gnf_amd.triplet_loss import (dot, exp_l2, hacky_cauchy_l2, l2, margin_loss, relative_loss,   # noqa: E402
+                                  sigmoid_dot)
 
+# DIST_FN_MAP / TRIPLET_LOSS_FN_MAP of run_gnn.py:155-166 (sigmoid_l2 at run_gnn.py:146-147's temp 10, shift 1)
+DIST_FNS = {"scaled_hacky_sigmoid_l2": scaled_hacky_sigmoid_l2, "hacky_sigmoid_l2": adj_loss.hacky_sigmoid_l2,
+            "sigmoid_l2": adj_loss.sigmoid_l2(10.0, 1.0)}
+TRIPLET_DIST_FNS = dict(DIST_FNS, l2=l2, dot=dot, exp_l2=exp_l2, hacky_cauchy_l2=hacky_cauchy_l2, sigmoid_dot=sigmoid_dot)
+TRIPLET_LOSS_FNS = {"margin": margin_loss(), "relative": relative_loss}
 MESSAGE_PASSING = {"avg_then_mlp": ("mean", "agg"), "sum_then_mlp": ("sum", "agg"), "sum_concat_then_mlp": ("sum", "concat"),
                    "avg_concat_then_mlp": ("mean", "concat")}
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", default="graph_rnn_community_small")
     ap.add_argument("--attn_type", default="avg_then_mlp", choices=list(MESSAGE_PASSING) + ["dm_attn"])
@@ -52,6 +62,11 @@ def main():
     ap.add_argument("--binary_dist_fn", default="scaled_hacky_sigmoid_l2",
                     choices=["scaled_hacky_sigmoid_l2", "hacky_sigmoid_l2", "sigmoid_l2"])
     ap.add_argument("--tune_sigmoid", action="store_true")
+    ap.add_argument("--loss_type", default="binary", choices=list(EncoderTrainer.LOSS_TYPES))
+    ap.add_argument("--triplet_dist_fn", default="l2", choices=list(TRIPLET_DIST_FNS))
+    ap.add_argument("--triplet_adj_dist_fn", default="hacky_sigmoid_l2", choices=list(DIST_FNS))
+    ap.add_argument("--triplet_loss_fn", default="margin", choices=list(TRIPLET_LOSS_FNS))
+    ap.add_argument("--num_sampling_loops", type=int, default=8)
     ap.add_argument("--train_batch_size", type=int, default=8)
     ap.add_argument("--num_train_iters", type=int, default=200000)
     ap.add_argument("--log_every_n_steps", type=int, default=100)
@@ -67,9 +82,17 @@ def main():
     ap.add_argument("--adam_epsilon", type=float, default=1e-8)
     ap.add_argument("--random_seed", type=int, default=12345)
     ap.add_argument("--save_path", default="encoder.npz")
+    return ap
+
+
+def main():
+    ap = make_parser()
     F = ap.parse_args()
     if F.tune_sigmoid and F.binary_dist_fn != "sigmoid_l2":
         ap.error("--tune_sigmoid trains the parameters of --binary_dist_fn sigmoid_l2")
+    if F.tune_sigmoid and F.loss_type == "triplet":
+        ap.error("--tune_sigmoid belongs to --loss_type binary")
+    triplet = F.loss_type == "triplet"
     random.seed(F.random_seed)
     np.random.seed(F.random_seed)
     torch.manual_seed(F.random_seed)
@@ -87,13 +110,17 @@ def main():
         hp.update(agg="sum", combine="agg", epsilon=0.0,
                   attn=dict(num_heads=8, kq_dim=10, v_dim=10, out_dim=80, concat=True, kq_dim_division=False, residual=False))
     enc = E.make_encoder(hp)
-    dist_fn = {"scaled_hacky_sigmoid_l2": scaled_hacky_sigmoid_l2, "hacky_sigmoid_l2": adj_loss.hacky_sigmoid_l2,
-               "sigmoid_l2": adj_loss.sigmoid_l2(10.0, 1.0)}[F.binary_dist_fn]   # run_gnn.py:146-147
+    dist_fn = DIST_FNS[F.binary_dist_fn]
     trainer = EncoderTrainer(enc, lr=F.lr, adam_beta1=F.adam_beta1, adam_beta2=F.adam_beta2, adam_epsilon=F.adam_epsilon,
                              lr_type=F.lr_type, num_train_iters=F.num_train_iters, lr_fixed_decay_steps=F.lr_fixed_decay_steps,
                              lr_fixed_decay_rate=F.lr_fixed_decay_rate, lr_fixed_decay_staircase=F.lr_fixed_decay_staircase,
-                             use_soft_labels=F.use_soft_labels, distance_fn=dist_fn, tune_sigmoid=F.tune_sigmoid)
-    dist_fn = trainer.distance_fn   # (with --tune_sigmoid: the token whose parameters the trainer moves)
+                             use_soft_labels=F.use_soft_labels, distance_fn=dist_fn, tune_sigmoid=F.tune_sigmoid,
+                             loss_type=F.loss_type, triplet_dist_fn=TRIPLET_DIST_FNS[F.triplet_dist_fn],
+                             triplet_adj_dist_fn=DIST_FNS[F.triplet_adj_dist_fn], triplet_loss_fn=TRIPLET_LOSS_FNS[F.triplet_loss_fn],
+                             num_sampling_loops=F.num_sampling_loops, seed=F.random_seed)
+    # the decoder's distance function: with --tune_sigmoid the token whose parameters the trainer moves, under the triplet
+    # loss the one its edge-error figures are counted with (pred_adj of loss.py:268)
+    dist_fn = trainer.triplet_adj_dist_fn if triplet else trainer.distance_fn
     dataset = D.GraphDataset(F.dataset, F.node_embedding_dim, F.gaussian_scale, seed=F.random_seed)
 
     def log(prefix, it, n_node, res, out_nodes=None):
@@ -105,6 +132,8 @@ def main():
         print(", ".join(f"{a}:{b}" for a, b in zip(n_node.cpu().numpy(), per_graph)))
         print(f"{prefix}sum loss: {float(res['sum_loss'])}")
         print(f"{prefix}mean loss: {float(res['mean_loss'])}")
+        if "skipped_terms" in res:
+            print(f"{prefix}triplet terms without a candidate: {int(res['skipped_terms'].sum())}")
         print(f"{prefix}total incorrect edges: {total}")
         print(f"{prefix}incorrect edges per node: {total / max(int(n_node.sum()), 1)}")
         print(f"{prefix}false positive edges: {float(adj_loss.false_positive_edges(res))}")

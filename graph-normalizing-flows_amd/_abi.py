@@ -76,6 +76,12 @@ class GnfAdjLossSpec(C.Structure):   # include/gnf_adj_loss.h
                 ("label_epsilon", C.c_float), ("abs_tol", C.c_float)]
 
 
+class GnfTripletSpec(C.Structure):   # include/gnf_triplet_loss.h
+    _fields_ = [("score", C.c_int32), ("temp", C.c_float), ("shift", C.c_float), ("scale_by_sqrt_dim", C.c_int32),
+                ("loss", C.c_int32), ("margin", C.c_float), ("num_sampling_loops", C.c_int32), ("self_loops", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class GnfDistance(C.Structure):      # include/gnf_distance.h
     _fields_ = [("temp", C.c_float), ("shift", C.c_float), ("scale_by_sqrt_dim", C.c_int32), ("params", C.c_void_p)]
 
@@ -260,6 +266,19 @@ _HASH_SIGNATURES = {
     "gnf_graph_hash_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+
+# include/gnf_triplet_loss.h (included by gnf.h, added within ABI v10): the sampled triplet loss of embeddings against a true
+# batch and its gradient.  A table of its own for the same reason.
+GNF_TRIPLET_L2, GNF_TRIPLET_DOT, GNF_TRIPLET_EXP_L2, GNF_TRIPLET_SIGMOID_L2, GNF_TRIPLET_HACKY_CAUCHY_L2, \
+    GNF_TRIPLET_SIGMOID_DOT = range(6)
+GNF_TRIPLET_MARGIN, GNF_TRIPLET_RELATIVE = 0, 1
+GNF_TRIPLET_SELF_KEEP, GNF_TRIPLET_SELF_SKIP = 0, 1
+_TRIPLET_SIGNATURES = {
+    "gnf_triplet_loss_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_triplet_loss_f32": (C.c_int, [C.POINTER(GnfCsr), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(GnfTripletSpec),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -275,6 +294,7 @@ DISTANCE_SYMBOLS = tuple(_DISTANCE_SIGNATURES)
 SPECTRA_SYMBOLS = tuple(_SPECTRA_SIGNATURES)
 COMPONENT_SYMBOLS = tuple(_COMPONENT_SIGNATURES)
 HASH_SYMBOLS = tuple(_HASH_SIGNATURES)
+TRIPLET_SYMBOLS = tuple(_TRIPLET_SIGNATURES)
 
 _lib = None
 
@@ -291,7 +311,7 @@ def lib():
         for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES,
                                   **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
                                   **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
-                                  **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES}.items():
+                                  **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES, **_TRIPLET_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

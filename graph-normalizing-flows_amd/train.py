@@ -408,18 +408,44 @@ class EncoderTrainer:
     adj_loss.TunedSigmoidL2 token (its values are where training starts); the two floats are the LAST two entries of theta,
     self.distance_fn is a TunedSigmoidL2 whose .params is a view of them, binary_loss writes their gradient into the last two
     entries of grad (gnf_adj_loss_dist_f32) and the one Adam launch moves them with everything else.  The kernels read them
-    from the device at run time, so a captured loss_and_grads replayed after a step computes what the eager call computes."""
+    from the device at run time, so a captured loss_and_grads replayed after a step computes what the eager call computes.
+    loss_type "triplet" (run_gnn.py:249-252) puts triplet_loss.triplet_loss in binary_loss' place: total_loss is the sum of the
+    node losses (run_gnn.py:270 adds a sum_loss its triplet branch never defines), the scores are triplet_dist_fn's (l2), the
+    terms triplet_loss_fn's (margin_loss()), the edge-error counts come from one binary_loss call without a gradient under
+    triplet_adj_dist_fn (hacky_sigmoid_l2).  The samples of a step are those of seed + global_step, a host scalar: a captured
+    loss_and_grads replays the same samples; for fresh ones under capture pass `draws` (uint32 [L, 2, N] on the device) and
+    refill it between replays.  tune_sigmoid with "triplet" is a ValueError."""
 
     LR_TYPES = ("constant", "fixed_decay", "polynomial_decay")
+    LOSS_TYPES = ("binary", "triplet")
 
     def __init__(self, encoder, lr=1e-4, adam_beta1=0.9, adam_beta2=0.999, adam_epsilon=1e-8, lr_type="polynomial_decay",
                  num_train_iters=200000, lr_fixed_decay_steps=1000, lr_fixed_decay_rate=0.99, lr_fixed_decay_staircase=False,
-                 distance_fn=None, use_soft_labels=False, max_nodes_per_graph=None, tune_sigmoid=False):
-        from .adj_loss import TunedSigmoidL2, sigmoid_l2
+                 distance_fn=None, use_soft_labels=False, max_nodes_per_graph=None, tune_sigmoid=False, loss_type="binary",
+                 triplet_dist_fn=None, triplet_adj_dist_fn=None, triplet_loss_fn=None, num_sampling_loops=8, seed=0, draws=None):
+        from .adj_loss import TunedSigmoidL2, check_token, hacky_sigmoid_l2, sigmoid_l2
         from .flow import scaled_hacky_sigmoid_l2
+        from .triplet_loss import MAX_SAMPLING_LOOPS, l2, loss_params, margin_loss, score_params
         if lr_type not in self.LR_TYPES:
             raise ValueError(f"lr_type={lr_type!r}: one of {self.LR_TYPES} ('schedule' is not built)")
+        if loss_type not in self.LOSS_TYPES:
+            raise ValueError(f"loss_type={loss_type!r}: one of {self.LOSS_TYPES}")
+        self.loss_type = loss_type
         self.tune_sigmoid = bool(tune_sigmoid)
+        if loss_type == "triplet":
+            if self.tune_sigmoid:
+                raise ValueError("tune_sigmoid trains the parameters of binary_loss' distance function: no parameter gradient is "
+                                 "built under loss_type='triplet'")
+            self.triplet_dist_fn = l2 if triplet_dist_fn is None else triplet_dist_fn
+            self.triplet_loss_fn = margin_loss() if triplet_loss_fn is None else triplet_loss_fn
+            self.triplet_adj_dist_fn = hacky_sigmoid_l2 if triplet_adj_dist_fn is None else triplet_adj_dist_fn
+            score_params(self.triplet_dist_fn), loss_params(self.triplet_loss_fn)   # NotImplementedError now, not at step 1
+            if isinstance(self.triplet_adj_dist_fn, TunedSigmoidL2):
+                raise NotImplementedError("triplet_adj_dist_fn: one of the three sigmoid tokens with constant parameters")
+            check_token(self.triplet_adj_dist_fn, "triplet_adj_dist_fn")
+            if not 1 <= int(num_sampling_loops) <= MAX_SAMPLING_LOOPS:
+                raise ValueError(f"num_sampling_loops={num_sampling_loops}: 1 to {MAX_SAMPLING_LOOPS}")
+        self.num_sampling_loops, self.seed, self.draws = int(num_sampling_loops), int(seed), draws
         if self.tune_sigmoid:
             if isinstance(distance_fn, sigmoid_l2):
                 distance_fn = TunedSigmoidL2(distance_fn.temp, distance_fn.shift)
@@ -480,11 +506,30 @@ class EncoderTrainer:
             raise _abi.GnfError("training runs on a HIP device only (no CPU path)")
         self._ensure_arena(int(x.shape[1]), x.device)
         out, stash = self.net.forward_train(graph)
+        if self.loss_type == "triplet":
+            return self._triplet_loss_and_grads(graph, graph if true_graph is None else true_graph, out, stash)
         res = adj_loss.binary_loss(out, graph if true_graph is None else true_graph, distance_fn=self.distance_fn,
                                    use_soft_labels=self.use_soft_labels, grad="sum",
                                    max_nodes_per_graph=self.max_nodes_per_graph,
                                    grad_params=self.grad[-2:] if self.tune_sigmoid else False)
         self.net.backward(graph, stash, res["grad_nodes"], self._grads)
+        res["gnn_output"], res["total_loss"] = out, res["sum_loss"]
+        return res
+
+    def _triplet_loss_and_grads(self, graph, true_graph, out, stash):
+        """loss_type "triplet" behind the training forward: triplet_loss with grad="sum" on the samples of seed + global_step (or
+        of self.draws), one binary_loss call without a gradient under triplet_adj_dist_fn for the edge-error counts, backward.
+        The result holds triplet_loss' keys ("sum_loss" and "mean_loss" are the triplet loss'), the two count tensors of
+        binary_loss, "gnn_output" and "total_loss" = the summed node losses."""
+        from . import adj_loss
+        from .triplet_loss import triplet_loss
+        res = triplet_loss(out, true_graph, distance_fn=self.triplet_dist_fn, triplet_loss_fn=self.triplet_loss_fn,
+                              num_sampling_loops=self.num_sampling_loops, seed=self.seed + self.global_step, draws=self.draws,
+                              grad="sum", max_nodes_per_graph=self.max_nodes_per_graph)
+        counts = adj_loss.binary_loss(out, true_graph, distance_fn=self.triplet_adj_dist_fn, grad=None,
+                                      max_nodes_per_graph=self.max_nodes_per_graph)
+        self.net.backward(graph, stash, res["grad_nodes"], self._grads)
+        res["false_positive_pairs"], res["false_negative_pairs"] = counts["false_positive_pairs"], counts["false_negative_pairs"]
         res["gnn_output"], res["total_loss"] = out, res["sum_loss"]
         return res
 

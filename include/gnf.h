@@ -526,6 +526,8 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 #include "gnf_graph_components.h"
 /* Added within ABI v10: Weisfeiler-Lehman hashes of a batch of graphs and the matching of two hash sets (gnf_graph_hashes.h) - likewise. */
 #include "gnf_graph_hashes.h"
+/* Added within ABI v10: the sampled triplet loss of embeddings against a true batch and its gradient (gnf_triplet_loss.h) - likewise. */
+#include "gnf_triplet_loss.h"
 
 #ifdef __cplusplus
 }
