@@ -355,3 +355,15 @@ def stream_ptr(device=None):
 def ptr(t):
     """Device pointer of a torch tensor (or None)."""
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def embeddings(nodes, what):
+    """(z, n, d, ld) of an [N, D >= 1] embedding tensor as the pair entry points take it: float32, unit inner stride, row
+    stride ld >= D (torch reports any stride, 0 included, for a dimension of 0 or 1 rows)"""
+    z = nodes.float()
+    if z.dim() != 2 or z.shape[1] < 1:
+        raise ValueError(f"{what} takes [N, D] embeddings with D >= 1, got shape {tuple(z.shape)}")
+    if z.stride(1) != 1:
+        z = z.contiguous()
+    n, d = int(z.shape[0]), int(z.shape[1])
+    return z, n, d, (int(z.stride(0)) if n > 1 else max(int(z.stride(0)), d))

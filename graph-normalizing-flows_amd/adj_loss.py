@@ -1,7 +1,7 @@
 """How well do embeddings reconstruct the graph they belong to: loss.py's binary_loss, its edge-error counts and the gradient
-of the loss with respect to the embeddings, on the device (gnf_adj_loss_f32, include/gnf_adj_loss.h) - and, for a sigmoid_l2
-whose temp and shift are trained with the encoder (run_gnn.py --tune_sigmoid), the gradient with respect to those two as well
-(TunedSigmoidL2, gnf_adj_loss_dist_f32, include/gnf_distance.h).
+of the loss with respect to the embeddings, on the device (gnf_adj_loss_dist_f32, include/gnf_distance.h and
+include/gnf_adj_loss.h) - and, for a sigmoid_l2 whose temp and shift are trained with the encoder (run_gnn.py --tune_sigmoid),
+the gradient with respect to those two as well (TunedSigmoidL2).
 
 The reference builds a dense [N, N] true adjacency, a dense distance_fn(nodes) and their element-wise cross-entropy
 (loss.py:162-188), counts wrong entries on those matrices (loss.py:88-116) and lets tf.gradients differentiate through
@@ -27,7 +27,7 @@ RESULT_KEYS = ("sum_loss", "mean_loss", "loss_per_graph", "false_positive_pairs"
 
 def hacky_sigmoid_l2(*_a, **_k):
     """Token for the distance function of loss.py:36-42, sigmoid(10 * (1 - ||z_i - z_j||^2)); the arithmetic runs inside
-    gnf_adj_loss_f32."""
+    the library."""
     raise NotImplementedError("token only: pass it as distance_fn to binary_loss")
 
 
@@ -83,11 +83,12 @@ class TunedSigmoidL2:
 
 
 def check_token(distance_fn, what):
-    """NotImplementedError unless distance_fn is one of the four tokens"""
+    """NotImplementedError unless distance_fn is one of the four tokens; a fixed token's _distance_params, None for a
+    TunedSigmoidL2"""
     if isinstance(distance_fn, TunedSigmoidL2):
-        return
+        return None
     try:
-        _distance_params(distance_fn)
+        return _distance_params(distance_fn)
     except NotImplementedError:
         raise NotImplementedError(f"{what} supports distance_fn = scaled_hacky_sigmoid_l2 (loss.py:45-53), hacky_sigmoid_l2 "
                                   "(loss.py:36-42), sigmoid_l2(temp, shift) (loss.py:56-62) or TunedSigmoidL2(temp, shift)") \
@@ -97,11 +98,10 @@ def check_token(distance_fn, what):
 def distance_desc(distance_fn, device, what="this call"):
     """_abi.GnfDistance of any of the four tokens (include/gnf_distance.h); the struct keeps no reference to a
     TunedSigmoidL2's tensor: hold the token while a launch may be pending"""
-    check_token(distance_fn, what)
-    if isinstance(distance_fn, TunedSigmoidL2):
+    fixed = check_token(distance_fn, what)
+    if fixed is None:
         return _abi.GnfDistance(10.0, 1.0, int(distance_fn.scale_by_sqrt_dim), distance_fn.on(device).data_ptr())
-    temp, shift, by_sqrt = _distance_params(distance_fn)
-    return _abi.GnfDistance(temp, shift, by_sqrt, None)
+    return _abi.GnfDistance(*fixed, None)
 
 
 def _distance_params(distance_fn):
@@ -129,8 +129,8 @@ def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_
       "grad_params"               float32 [2], with grad_params and a TunedSigmoidL2 token: d loss / d (temp, shift) of the
                                   loss `grad` names (sum_loss without grad).  grad_params=True allocates it; a device float32
                                   [2] tensor is written in place (a trainer's view of its gradient vector).  Any other token:
-                                  ValueError.  The call then goes through gnf_adj_loss_dist_f32, and so does every call with
-                                  a TunedSigmoidL2 token; the other tokens keep gnf_adj_loss_f32.
+                                  ValueError.
+    Every token goes through gnf_adj_loss_dist_f32 (a fixed token's bits are gnf_adj_loss_f32's: one kernel).
     The dense true_adj, pred_adj and ce_loss the reference also returns are NOT produced.  Per pair: p = sigmoid(u),
     ce = softplus(u_c) - t u_c with u_c = u clipped to +-log((1 - 1e-7) / 1e-7) - Keras' binary_crossentropy - and no gradient
     where the clip is active: a true edge whose endpoints lie far apart gets none, as in the reference.  t is the hard label,
@@ -140,10 +140,9 @@ def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_
     max_nodes_per_graph (any upper bound on n_node, at most 65536) or n_node_host (the sizes as a host sequence) nothing is
     copied to the host and nothing synchronises, so the call can be captured; otherwise n_node is read once."""
     from .graphs import csr_desc, csr_of
-    tuned = isinstance(distance_fn, TunedSigmoidL2)
-    temp, shift, by_sqrt = (10.0, 1.0, 1) if tuned else _distance_params(distance_fn)   # (tuned: the device values override)
+    check_token(distance_fn, "binary_loss")    # (anything else raises before the device is looked at)
     want_gp = grad_params is not None and grad_params is not False
-    if want_gp and not tuned:
+    if want_gp and not isinstance(distance_fn, TunedSigmoidL2):
         raise ValueError("grad_params needs distance_fn=TunedSigmoidL2(...): the other tokens' parameters are constants")
     if grad not in (None, "sum", "mean"):
         raise ValueError(f"grad={grad!r}: None, 'sum' or 'mean'")
@@ -161,16 +160,13 @@ def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_
         raise _abi.GnfError("binary_loss runs on a HIP device only (no CPU path)")
     b = int(graph_phs.n_node.shape[0])
     cap = _node_bound(graph_phs, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
-    z = z.to(torch.float32)
-    if z.dim() != 2 or z.shape[1] < 1:
-        raise ValueError(f"binary_loss takes [N, D] embeddings with D >= 1, got shape {tuple(z.shape)}")
-    if z.stride(1) != 1:
-        z = z.contiguous()
-    d = int(z.shape[1])
-    ld = z.stride(0) if n > 1 else max(int(z.stride(0)), d)   # (torch reports any stride for a dimension of 0 or 1 rows)
+    z, _, d, ld = _abi.embeddings(z, "binary_loss")
     csr = csr_of(graph_phs)
     desc = csr_desc(graph_phs, csr, node_offsets=True)
-    spec = _abi.GnfAdjLossSpec(temp, shift, by_sqrt, int(bool(use_soft_labels)), float(epsilon), float(abs_tol))
+    dist = distance_desc(distance_fn, dev, "binary_loss")
+    # (the spec's own temp / shift / scale are gnf_adj_loss_f32's; this entry point reads the distance from `dist`)
+    spec = _abi.GnfAdjLossSpec(dist.temp, dist.shift, dist.scale_by_sqrt_dim, int(bool(use_soft_labels)), float(epsilon),
+                               float(abs_tol))
     sums2 = torch.empty(2, dtype=torch.float64, device=dev)
     out = {"loss_per_graph": torch.empty(b, dtype=torch.float64, device=dev),
            "false_positive_pairs": torch.empty(b, dtype=torch.int64, device=dev),
@@ -178,37 +174,24 @@ def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_
     g = torch.empty((n, d), dtype=torch.float32, device=dev) if grad else None
     pairs = float(n) * float(n) - float(n)
     grad_scale = 1.0 if grad != "mean" else (1.0 / pairs if n >= 2 else 0.0)
-    if tuned:
-        dist = distance_desc(distance_fn, dev)
-        gp = None
-        if want_gp:
-            gp = torch.empty(2, dtype=torch.float32, device=dev) if grad_params is True else grad_params
-            if gp.device != dev or gp.dtype != torch.float32 or tuple(gp.shape) != (2,) or not gp.is_contiguous():
-                raise ValueError("grad_params: True or a contiguous float32 [2] tensor on the embeddings' device")
-        ws_bytes = lib.gnf_adj_loss_dist_workspace_bytes(b, n, cap)
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _abi.check(lib.gnf_adj_loss_dist_f32(C.byref(desc), _abi.ptr(z), ld, d, cap, C.byref(spec), C.byref(dist),
-                                                 _abi.ptr(out["loss_per_graph"]), _abi.ptr(sums2),
-                                                 _abi.ptr(out["false_positive_pairs"]), _abi.ptr(out["false_negative_pairs"]),
-                                                 _abi.ptr(g), d, grad_scale, _abi.ptr(gp), _abi.ptr(ws), ws_bytes,
-                                                 _abi.stream_ptr(dev)), "gnf_adj_loss_dist_f32")
-        out["sum_loss"], out["mean_loss"] = sums2[0], sums2[1]
-        if grad:
-            out["grad_nodes"] = g
-        if want_gp:
-            out["grad_params"] = gp
-        return out
-    ws_bytes = lib.gnf_adj_loss_workspace_bytes(b, n, cap)
+    gp = None
+    if want_gp:
+        gp = torch.empty(2, dtype=torch.float32, device=dev) if grad_params is True else grad_params
+        if gp.device != dev or gp.dtype != torch.float32 or tuple(gp.shape) != (2,) or not gp.is_contiguous():
+            raise ValueError("grad_params: True or a contiguous float32 [2] tensor on the embeddings' device")
+    ws_bytes = lib.gnf_adj_loss_dist_workspace_bytes(b, n, cap)
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _abi.check(lib.gnf_adj_loss_f32(C.byref(desc), _abi.ptr(z), ld, d, cap, C.byref(spec), _abi.ptr(out["loss_per_graph"]),
-                                        _abi.ptr(sums2), _abi.ptr(out["false_positive_pairs"]),
-                                        _abi.ptr(out["false_negative_pairs"]), _abi.ptr(g), d, grad_scale, _abi.ptr(ws),
-                                        ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_loss_f32")
+        _abi.check(lib.gnf_adj_loss_dist_f32(C.byref(desc), _abi.ptr(z), ld, d, cap, C.byref(spec), C.byref(dist),
+                                             _abi.ptr(out["loss_per_graph"]), _abi.ptr(sums2),
+                                             _abi.ptr(out["false_positive_pairs"]), _abi.ptr(out["false_negative_pairs"]),
+                                             _abi.ptr(g), d, grad_scale, _abi.ptr(gp), _abi.ptr(ws), ws_bytes,
+                                             _abi.stream_ptr(dev)), "gnf_adj_loss_dist_f32")
     out["sum_loss"], out["mean_loss"] = sums2[0], sums2[1]
     if grad:
         out["grad_nodes"] = g
+    if want_gp:
+        out["grad_params"] = gp
     return out
 
 

@@ -8,8 +8,9 @@
 // senders ascending within a receiver - (rowptr, senders) IS the receiver-sorted CSR of the edge list, and because
 // d2(i, j) and d2(j, i) are the same fp32 number the edge set is symmetric, so it is the by-sender CSR as well.
 // No atomics: every word, count and edge has exactly one writer.
-// gnf_adj_edges_count_dist_f32 (include/gnf_distance.h) is pass 1 over another logit (gnf_distance_dev.h).
+// gnf_adj_edges_count_dist_f32 (include/gnf_distance.h) is pass 1 with another DistSigmoid (gnf_distance_dev.h).
 #include "gnf_distance_dev.h"
+#include "gnf_graph_bitmap.h"
 
 namespace gnf {
 
@@ -32,65 +33,30 @@ static EdgeWs edge_ws(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes) {
     return L;
 }
 
-__global__ __launch_bounds__(256) void k_edge_node_offsets(const int32_t* __restrict__ n_node, int64_t n_graphs,
-                                                           int64_t* __restrict__ node_off) {
-    __shared__ int64_t sh[257];
-    const int64_t chunk = (n_graphs + 255) / 256;
-    const int64_t beg = (int64_t)threadIdx.x * chunk;
-    int64_t end = beg + chunk;
-    if (end > n_graphs) end = n_graphs;
-    int64_t l = 0;
-    for (int64_t i = beg; i < end; ++i) l += n_node[i];
-    sh[threadIdx.x + 1] = l;
-    if (threadIdx.x == 0) sh[0] = 0;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int i = 1; i <= 256; ++i) sh[i] += sh[i - 1];
-    __syncthreads();
-    int64_t r = sh[threadIdx.x];
-    if (threadIdx.x == 0) node_off[0] = 0;
-    for (int64_t i = beg; i < end; ++i) {
-        r += n_node[i];
-        node_off[i + 1] = r;
-    }
-}
-
-// graph g's rows [n0, n0 + ng), cut to the node buffer and to the `max_nodes` columns the bitmap holds: counts that do not
-// describe the batch (or a bound below the largest graph) lose edges, they never reach outside the arrays
-__device__ __forceinline__ void edge_graph_range(const int64_t* __restrict__ node_off, int g, int64_t n_nodes, int max_nodes,
-                                                 int64_t& n0, int& ng) {
-    n0 = node_off[g];
-    int64_t n1 = node_off[g + 1];
-    if (n0 < 0) n0 = 0;
-    if (n1 > n_nodes) n1 = n_nodes;
-    int64_t c = n1 - n0;
-    if (c > max_nodes) c = max_nodes;
-    ng = c > 0 ? (int)c : 0;
-}
+// A graph's rows come from stats_graph_range (gnf_graph_bitmap.h), cut to the node buffer and to the `max_nodes` columns the
+// bitmap holds: counts that do not describe the batch (or a bound below the largest graph) lose edges, they never reach
+// outside the arrays.
 
 // pass 1.  One workgroup per (graph, 16-row tile), the tile's rows in LDS as in k_pred_adj; wave w owns rows 4 w .. 4 w + 3
 // of the tile and walks the graph's columns 64 at a time (lane = column): one read of z_j serves its four rows, one ballot
 // per row is the bitmap word, and the wave adds up its rows' popcounts in registers.
-template <bool LDS_ROWS, class Dist>
+template <bool LDS_ROWS>
 __global__ __launch_bounds__(256) void k_edge_count(const float* __restrict__ z, int64_t ld, int D,
                                                     const int64_t* __restrict__ node_off, int64_t n_nodes, int max_nodes,
-                                                    int64_t W, float threshold, int self_loops, Dist dist_arg,
+                                                    int64_t W, float threshold, int self_loops, DistSigmoid dist_arg,
                                                     unsigned long long* __restrict__ bitmap, int32_t* __restrict__ rowcnt) {
     extern __shared__ float zi[];  // [kEdgeTile][D]
     int64_t n0;
     int ng;
-    edge_graph_range(node_off, blockIdx.x, n_nodes, max_nodes, n0, ng);
+    stats_graph_range(node_off, blockIdx.x, n_nodes, max_nodes, n0, ng);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int words = (ng + 63) / 64;
-    const Dist dist = dist_arg.load();   // (device-resident parameters: once per workgroup)
+    const DistSigmoid dist = dist_arg.load();   // (device-resident parameters: once per workgroup)
     for (int i0 = blockIdx.y * kEdgeTile; i0 < ng; i0 += gridDim.y * kEdgeTile) {   // (uniform over the workgroup)
         const int rows = ng - i0 < kEdgeTile ? ng - i0 : kEdgeTile;
         if constexpr (LDS_ROWS) {
             __syncthreads();   // the previous tile's readers are done
-            for (int i = threadIdx.x; i < rows * D; i += 256) {
-                const int rl = i / D, f = i - rl * D;
-                zi[i] = z[(n0 + i0 + rl) * ld + f];
-            }
+            stage_row_tile(zi, z, ld, D, n0 + i0, rows);
             __syncthreads();
         }
         const int r0 = wave * kEdgeWaveRows;
@@ -106,15 +72,8 @@ __global__ __launch_bounds__(256) void k_edge_count(const float* __restrict__ z,
             const int j = w * 64 + lane;
             const bool col = j < ng;
             const float* zj = z + (n0 + (col ? j : ng - 1)) * ld;
-            float d2[kEdgeWaveRows] = {0.f, 0.f, 0.f, 0.f};
-            for (int f = 0; f < D; ++f) {
-                const float zjf = zj[f];
-#pragma unroll
-                for (int q = 0; q < kEdgeWaveRows; ++q) {
-                    const float df = zr[q][f] - zjf;
-                    d2[q] = fmaf(df, df, d2[q]);
-                }
-            }
+            float d2[kEdgeWaveRows];
+            pair_d2(zr, zj, D, d2);
             for (int q = 0; q < kEdgeWaveRows; ++q) {
                 const int i = i0 + r0 + q;
                 const float a = dist.logit(d2[q]);
@@ -178,7 +137,7 @@ __global__ __launch_bounds__(256) void k_edge_fill(const int64_t* __restrict__ n
                                                    int32_t* __restrict__ senders, int32_t* __restrict__ receivers) {
     int64_t n0;
     int ng;
-    edge_graph_range(node_off, blockIdx.x, n_nodes, max_nodes, n0, ng);
+    stats_graph_range(node_off, blockIdx.x, n_nodes, max_nodes, n0, ng);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int words = (ng + 63) / 64;
     for (int i0 = blockIdx.y * kEdgeTile; i0 < ng; i0 += gridDim.y * kEdgeTile) {
@@ -221,9 +180,8 @@ static dim3 edge_grid(int64_t n_graphs, int32_t max_nodes) {
     return dim3((unsigned)n_graphs, (unsigned)tiles);
 }
 
-// the two counting entry points: same checks, same launches, the logit's type apart
-template <class Dist>
-static int edges_count(const char* what, Dist dist, const float* z, int64_t ld, int32_t D, const int32_t* n_node,
+// the two counting entry points: same checks, same launches
+static int edges_count(const char* what, DistSigmoid dist, const float* z, int64_t ld, int32_t D, const int32_t* n_node,
                        int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph, float threshold, int32_t self_loops,
                        int32_t* rowptr, int32_t* n_edge, int64_t* total, void* ws, size_t ws_bytes, gnf_stream_t stream) {
     if (D < 1 || ld < D) {
@@ -248,16 +206,15 @@ static int edges_count(const char* what, Dist dist, const float* z, int64_t ld, 
     int64_t* node_off = (int64_t*)((char*)ws + L.node_off);
     unsigned long long* bitmap = (unsigned long long*)((char*)ws + L.bitmap);
     int32_t* rowcnt = (int32_t*)((char*)ws + L.rowcnt);
-    hipLaunchKernelGGL(k_edge_node_offsets, dim3(1), dim3(256), 0, st, n_node, n_graphs, node_off);
-    GNF_LAUNCH_CHECK("k_edge_node_offsets");
+    if (int rc = launch_node_offsets(n_node, n_graphs, node_off, nullptr, st)) return rc;
     if (n_graphs > 0 && n_nodes > 0) {
         const dim3 grid = edge_grid(n_graphs, max_nodes_per_graph);
         const size_t row_tile = (size_t)kEdgeTile * D * sizeof(float);
         if (row_tile <= 64 * 1024)
-            hipLaunchKernelGGL((k_edge_count<true, Dist>), grid, dim3(256), row_tile, st, z, ld, D, node_off, n_nodes,
+            hipLaunchKernelGGL(k_edge_count<true>, grid, dim3(256), row_tile, st, z, ld, D, node_off, n_nodes,
                                max_nodes_per_graph, L.W, threshold, self_loops, dist, bitmap, rowcnt);
         else
-            hipLaunchKernelGGL((k_edge_count<false, Dist>), grid, dim3(256), 0, st, z, ld, D, node_off, n_nodes,
+            hipLaunchKernelGGL(k_edge_count<false>, grid, dim3(256), 0, st, z, ld, D, node_off, n_nodes,
                                max_nodes_per_graph, L.W, threshold, self_loops, dist, bitmap, rowcnt);
         GNF_LAUNCH_CHECK("k_edge_count");
     }
@@ -281,7 +238,7 @@ size_t gnf_adj_edges_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t 
 int gnf_adj_edges_count_f32(const float* z, int64_t ld, int32_t D, const int32_t* n_node, int64_t n_graphs, int64_t n_nodes,
                             int32_t max_nodes_per_graph, float threshold, int32_t self_loops, int32_t* rowptr,
                             int32_t* n_edge, int64_t* total, void* ws, size_t ws_bytes, gnf_stream_t stream) {
-    return edges_count("gnf_adj_edges_count_f32", DistScaledHacky{D >= 1 ? 1.f / sqrtf((float)D) : 0.f}, z, ld, D, n_node,
+    return edges_count("gnf_adj_edges_count_f32", dist_scaled_hacky(D), z, ld, D, n_node,
                        n_graphs, n_nodes, max_nodes_per_graph, threshold, self_loops, rowptr, n_edge, total, ws, ws_bytes,
                        stream);
 }
@@ -294,7 +251,7 @@ int gnf_adj_edges_count_dist_f32(const GnfDistance* dist, const float* z, int64_
         set_error("gnf_adj_edges_count_dist_f32: null dist");
         return GNF_EINVAL;
     }
-    return edges_count("gnf_adj_edges_count_dist_f32", dist_sigmoid(*dist, D >= 1 ? D : 1), z, ld, D, n_node, n_graphs,
+    return edges_count("gnf_adj_edges_count_dist_f32", dist_sigmoid(*dist, D), z, ld, D, n_node, n_graphs,
                        n_nodes, max_nodes_per_graph, threshold, self_loops, rowptr, n_edge, total, ws, ws_bytes, stream);
 }
 

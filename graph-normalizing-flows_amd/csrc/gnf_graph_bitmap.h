@@ -39,7 +39,8 @@ __device__ __forceinline__ int stats_graph_of(const int32_t* __restrict__ off, i
     const int64_t g = lo - 1;
     return (g >= 0 && g < n_graphs) ? (int)g : -1;
 }
-__device__ __forceinline__ void stats_graph_range(const int32_t* __restrict__ off, int g, int64_t n_nodes, int max_nodes,
+template <class Off>   // int32 node_offsets of a GnfCsr, or the int64 ones the decoders scan
+__device__ __forceinline__ void stats_graph_range(const Off* __restrict__ off, int g, int64_t n_nodes, int max_nodes,
                                                   int64_t& n0, int& ng) {
     n0 = off[g];
     int64_t n1 = off[g + 1];

@@ -11,6 +11,7 @@ import math
 import torch
 
 from . import _abi
+from .graph_stats import _node_bound
 
 LN_2PI = math.log(2.0 * math.pi)
 
@@ -157,7 +158,7 @@ def inverse_per_graph(grevnet, z_graph):
 
 def scaled_hacky_sigmoid_l2(*_a, **_k):
     """Token for the distance function of loss.py:45-53 (the only one pred_adj is used with on this
-    path); the arithmetic runs inside gnf_pred_adj_f32."""
+    path); the arithmetic runs inside gnf_pred_adj_dist_f32."""
     raise NotImplementedError("token only: pass it as distance_fn to pred_adj")
 
 
@@ -168,18 +169,14 @@ def pred_adj(gnn_output, distance_fn=scaled_hacky_sigmoid_l2, max_nodes_per_grap
     [n_g, n_g] blocks (views of one device buffer), which is what its consumer slices out
     (train_grevnet_with_data.py:538-540).  `adjacency = block > 0.5` gives the sampled graphs.
     distance_fn: the default, or one of adj_loss' tokens - hacky_sigmoid_l2, sigmoid_l2(temp, shift), TunedSigmoidL2 - whose
-    probabilities have the bits binary_loss scores (gnf_pred_adj_dist_f32); the default keeps gnf_pred_adj_f32."""
-    default = distance_fn is scaled_hacky_sigmoid_l2
-    if not default:
-        from .adj_loss import check_token, distance_desc
-        check_token(distance_fn, "pred_adj")   # (anything else raises before the device is looked at)
+    probabilities have the bits binary_loss scores.  Every token goes through gnf_pred_adj_dist_f32 (the default's bits are
+    gnf_pred_adj_f32's: one kernel)."""
+    from .adj_loss import check_token, distance_desc
+    check_token(distance_fn, "pred_adj")   # (anything else raises before the device is looked at)
     lib = _abi.lib()
-    z = gnn_output.nodes
-    if z.device.type != "cuda":
+    if gnn_output.nodes.device.type != "cuda":
         raise _abi.GnfError("pred_adj runs on a HIP device only (no CPU path)")
-    z = z.to(torch.float32)
-    if z.stride(1) != 1:
-        z = z.contiguous()
+    z, _, d, ld = _abi.embeddings(gnn_output.nodes, "pred_adj")
     n_node_host = gnn_output.n_node.cpu().tolist()          # sizes the output (the reference syncs here too)
     b = len(n_node_host)
     total = sum(n * n for n in n_node_host)
@@ -193,16 +190,11 @@ def pred_adj(gnn_output, distance_fn=scaled_hacky_sigmoid_l2, max_nodes_per_grap
     ws_bytes = lib.gnf_pred_adj_workspace_bytes(b)
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
     nn = gnn_output.n_node.to(torch.int32).contiguous()
+    dist = distance_desc(distance_fn, dev, "pred_adj")
     with torch.cuda.device(dev):
-        if default:
-            _abi.check(lib.gnf_pred_adj_f32(_abi.ptr(z), z.stride(0), z.shape[1], _abi.ptr(nn), b, cap, _abi.ptr(out),
-                                            _abi.ptr(off), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                       "gnf_pred_adj_f32")
-        else:
-            dist = distance_desc(distance_fn, dev, "pred_adj")
-            _abi.check(lib.gnf_pred_adj_dist_f32(C.byref(dist), _abi.ptr(z), z.stride(0), z.shape[1], _abi.ptr(nn), b, cap,
-                                                 _abi.ptr(out), _abi.ptr(off), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                       "gnf_pred_adj_dist_f32")
+        _abi.check(lib.gnf_pred_adj_dist_f32(C.byref(dist), _abi.ptr(z), ld, d, _abi.ptr(nn), b, cap, _abi.ptr(out),
+                                             _abi.ptr(off), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                   "gnf_pred_adj_dist_f32")
     blocks, o = [], 0
     for n in n_node_host:
         blocks.append(out[o:o + n * n].view(n, n))
@@ -215,8 +207,8 @@ def decode_graphs(gnn_output, threshold=0.5, self_loops=False, edge_capacity=Non
     """The graphs the sampling path generates (generate_graphs.py:68-78, train_grevnet_with_data.py:532-540: `pred_adj >
     0.5`, one graph per block), as device edge lists: edge (sender = j, receiver = i) of graph g exists iff
     pred_adj(gnn_output)[g][i, j] > threshold - the same fp32 arithmetic, bit for bit, without the dense blocks
-    (gnf_adj_edges_count_f32 / gnf_adj_edges_fill).  The diagonal is no edge unless self_loops=True; then every node has its
-    self loop whatever the threshold (the convention of the flow's datasets).  Returns a dict:
+    (gnf_adj_edges_count_dist_f32 / gnf_adj_edges_fill).  The diagonal is no edge unless self_loops=True; then every node
+    has its self loop whatever the threshold (the convention of the flow's datasets).  Returns a dict:
       "graph"        GraphsTuple: the input's nodes and n_node, int32 senders / receivers (batch-wide node ids, receivers
                      ascending, senders ascending within a receiver) and n_edge, zero edges / globals as
                      data_dicts_to_graphs_tuple makes them
@@ -232,52 +224,29 @@ def decode_graphs(gnn_output, threshold=0.5, self_loops=False, edge_capacity=Non
     then have edge_capacity entries of which only the first min(total_edges, edge_capacity) are valid - the rest is
     unspecified - and rowptr / n_edge / "csr" describe the untruncated edge list: check total_edges <= edge_capacity before
     using them.  The CSR cache is not seeded in this mode.
-    distance_fn: as for pred_adj (gnf_adj_edges_count_dist_f32; the default keeps gnf_adj_edges_count_f32)."""
-    default = distance_fn is scaled_hacky_sigmoid_l2
-    if not default:
-        from .adj_loss import check_token, distance_desc
-        check_token(distance_fn, "decode_graphs")   # (anything else raises before the device is looked at)
+    distance_fn: as for pred_adj."""
+    from .adj_loss import check_token, distance_desc
     from .graphs import Csr, GraphsTuple, seed_csr_cache
+    check_token(distance_fn, "decode_graphs")   # (anything else raises before the device is looked at)
     lib = _abi.lib()
-    z = gnn_output.nodes
-    if z.device.type != "cuda":
+    dev = gnn_output.nodes.device
+    if dev.type != "cuda":
         raise _abi.GnfError("decode_graphs runs on a HIP device only (no CPU path)")
-    dev = z.device
-    z = z.to(torch.float32)
-    if z.stride(1) != 1:
-        z = z.contiguous()
-    n, d = int(z.shape[0]), int(z.shape[1])
-    ld = z.stride(0) if n > 1 else max(int(z.stride(0)), d)   # (torch reports any stride, 0 included, for a dimension of 0 or 1 rows)
+    z, n, d, ld = _abi.embeddings(gnn_output.nodes, "decode_graphs")
     b = int(gnn_output.n_node.shape[0])
-    if n_node_host is not None:
-        sizes = [int(v) for v in n_node_host]
-        if len(sizes) != b or sum(sizes) != n:
-            raise ValueError(f"n_node_host describes {len(sizes)} graphs / {sum(sizes)} nodes, the batch has {b} / {n}")
-    elif max_nodes_per_graph is None:
-        sizes = gnn_output.n_node.cpu().tolist()
-    else:
-        sizes = None
-    largest = (max(sizes) if sizes else 0) if sizes is not None else None
-    cap = int(max_nodes_per_graph) if max_nodes_per_graph is not None else largest
-    if largest is not None and cap < largest:   # the bitmap holds `cap` columns per row: a smaller bound would drop edges
-        raise ValueError(f"max_nodes_per_graph={cap} is below the largest graph of the batch ({largest} nodes)")
+    cap = _node_bound(gnn_output, max_nodes_per_graph, n_node_host, 2 ** 31 - 1)
     nn = gnn_output.n_node.to(device=dev, dtype=torch.int32).contiguous()
     rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
     n_edge = torch.empty(b, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
     ws_bytes = lib.gnf_adj_edges_workspace_bytes(b, n, cap)
     ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    dist = distance_desc(distance_fn, dev, "decode_graphs")
     with torch.cuda.device(dev):
-        if default:
-            _abi.check(lib.gnf_adj_edges_count_f32(_abi.ptr(z), ld, d, _abi.ptr(nn), b, n, cap, float(threshold),
-                                                   int(bool(self_loops)), _abi.ptr(rowptr), _abi.ptr(n_edge), _abi.ptr(total),
-                                                   _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_edges_count_f32")
-        else:
-            dist = distance_desc(distance_fn, dev, "decode_graphs")
-            _abi.check(lib.gnf_adj_edges_count_dist_f32(C.byref(dist), _abi.ptr(z), ld, d, _abi.ptr(nn), b, n, cap,
-                                                        float(threshold), int(bool(self_loops)), _abi.ptr(rowptr),
-                                                        _abi.ptr(n_edge), _abi.ptr(total), _abi.ptr(ws), ws_bytes,
-                                                        _abi.stream_ptr(dev)), "gnf_adj_edges_count_dist_f32")
+        _abi.check(lib.gnf_adj_edges_count_dist_f32(C.byref(dist), _abi.ptr(z), ld, d, _abi.ptr(nn), b, n, cap,
+                                                    float(threshold), int(bool(self_loops)), _abi.ptr(rowptr),
+                                                    _abi.ptr(n_edge), _abi.ptr(total), _abi.ptr(ws), ws_bytes,
+                                                    _abi.stream_ptr(dev)), "gnf_adj_edges_count_dist_f32")
         exact = edge_capacity is None
         e = int(total.item()) if exact else int(edge_capacity)
         senders = torch.empty(e, dtype=torch.int32, device=dev)

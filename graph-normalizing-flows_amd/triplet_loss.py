@@ -132,13 +132,7 @@ def triplet_loss(gnn_output, graph_phs, distance_fn=l2, triplet_loss_fn=None, nu
         raise ValueError(f"{n} nodes with num_sampling_loops={loops}: N * 2 L must fit int32")
     b = int(graph_phs.n_node.shape[0])
     cap = _node_bound(graph_phs, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
-    z = z.to(torch.float32)
-    if z.dim() != 2 or z.shape[1] < 1:
-        raise ValueError(f"triplet_loss takes [N, D] embeddings with D >= 1, got shape {tuple(z.shape)}")
-    if z.stride(1) != 1:
-        z = z.contiguous()
-    d = int(z.shape[1])
-    ld = z.stride(0) if n > 1 else max(int(z.stride(0)), d)   # (torch reports any stride for a dimension of 0 or 1 rows)
+    z, _, d, ld = _abi.embeddings(z, "triplet_loss")
     if draws is not None:
         if draws.device != dev or tuple(draws.shape) != (loops, 2, n):
             raise ValueError(f"draws: a [{loops}, 2, {n}] tensor on the embeddings' device, got {tuple(draws.shape)} on {draws.device}")

@@ -13,8 +13,10 @@
  *
  * The distance function: p_ij = sigmoid(u_ij), u_ij = temp * (shift - d2_ij * scale), d2_ij the fp32 fmaf chain over the
  * features in ascending order of (z_i[f] - z_j[f])^2 and scale = 1 / sqrtf((float)D) (scale_by_sqrt_dim != 0) or 1 -
- * written and evaluated as gnf_pred_adj_f32 does, so for temp = 10, shift = 1, scale_by_sqrt_dim = 1 p_ij has the bits of
- * gnf_pred_adj_f32's block entry and of the value gnf_adj_edges_count_f32 thresholds.
+ * evaluated by the code gnf_pred_adj_f32 evaluates it with (u = temp * fmaf(-d2, scale, shift), the product rounded on its
+ * own), so for temp = 10, shift = 1, scale_by_sqrt_dim = 1 p_ij has the bits of gnf_pred_adj_f32's block entry and of the
+ * value gnf_adj_edges_count_f32 thresholds.  This entry point is gnf_adj_loss_dist_f32 (gnf_distance.h) with the distance
+ * taken from spec, without grad_params and without the tail of that entry point's workspace.
  *   scaled_hacky_sigmoid_l2 (loss.py:45-53): 10, 1, on;  hacky_sigmoid_l2 (loss.py:36-42): 10, 1, off;
  *   sigmoid_l2(temp, shift) (loss.py:56-62): temp, shift, on.  The other distance functions of loss.py are not covered. */
 typedef struct GnfAdjLossSpec {
@@ -50,6 +52,7 @@ typedef struct GnfAdjLossSpec {
  * ws: gnf_adj_loss_workspace_bytes (a host computation): with W = ceil(max_nodes_per_graph / 64),
  *   senders into row i   uint64 [n_nodes][W]  (bit j - n0: a_ji)  |  receivers out of row i  uint64 [n_nodes][W]  (a_ij)  |
  *   row loss fp64 [n_nodes]  |  row fp count int32 [n_nodes]  |  row fn count int32 [n_nodes]      (rounded up to 8 bytes)
+ * zeroed by a kernel (a memset node of a replayed capture is not reliably ordered before the kernels behind it).
  * GNF_EINVAL: null pointers (csr, spec, sums2, z, ws, the per-graph outputs, the CSR arrays), missing node_offsets;
  * GNF_ESHAPE: D < 1, ld < D, ld_grad < D (with grad), negative sizes, max_nodes_per_graph < 0 or > 65536 (or 0 with nodes),
  * label_epsilon outside [0, 0.5], abs_tol < 0; GNF_EWORKSPACE: short workspace - all before any launch.

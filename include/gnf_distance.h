@@ -12,9 +12,9 @@
  * run_gnn.py chooses the decoder's distance function with --binary_dist_fn and, with --tune_sigmoid, makes temp and shift of
  * sigmoid_l2 trainable variables (run_gnn.py:146-165).  The entry points below take the distance function as an argument -
  * p_ij = sigmoid(u_ij), u_ij = temp * (shift - d2_ij * scale), the arithmetic gnf_adj_loss.h documents, spelled out as
- * u = temp * fmaf(-d2, scale, shift) with the product rounded on its own (what the compiler's contraction makes of the older
- * entry points' expression): the three of them give the same bits for the same (temp, shift, scale), and for (10, 1,
- * 1 / sqrtf(D)) the bits of gnf_pred_adj_f32, gnf_adj_edges_count_f32 and gnf_adj_loss_f32.
+ * u = temp * fmaf(-d2, scale, shift) with the product rounded on its own: the three of them give the same bits for the same
+ * (temp, shift, scale).  gnf_pred_adj_f32, gnf_adj_edges_count_f32 and gnf_adj_loss_f32 are the same code paths with
+ * {10, 1, 1, NULL}, {10, 1, 1, NULL} and spec's {temp, shift, scale_by_sqrt_dim, NULL}: the same kernels, the same bits.
  *   scaled_hacky_sigmoid_l2: {10, 1, 1, NULL};  hacky_sigmoid_l2: {10, 1, 0, NULL};  sigmoid_l2(temp, shift): {temp, shift, 1,
  *   NULL};  trainable: params = device {temp, shift}, which every workgroup of the pair kernels loads once, at run time, with
  *   an ordinary load - nothing of them is read on the host or passed by value. */
@@ -50,7 +50,7 @@ int gnf_adj_edges_count_dist_f32(const GnfDistance* dist, const float* z, int64_
  *                the same (temp, shift, scale).
  * ws: gnf_adj_loss_dist_workspace_bytes (a host computation): gnf_adj_loss_f32's layout, then, from its (8-byte rounded) end,
  *   row dtemp fp64 [n_nodes]  |  row dshift fp64 [n_nodes]  |  graph dtemp fp64 [n_graphs]  |  graph dshift fp64 [n_graphs]
- * Checks and codes are gnf_adj_loss_f32's, plus GNF_EINVAL for a null dist.  n_nodes == 0 or n_graphs == 0: the outputs,
+ * (the tail is touched with grad_params only).  Checks and codes are gnf_adj_loss_f32's, plus GNF_EINVAL for a null dist.  n_nodes == 0 or n_graphs == 0: the outputs,
  * grad_params included, are zeroed.  Asynchronous on `stream`, nothing is read from the host after launch, capturable. */
 size_t gnf_adj_loss_dist_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes_per_graph);
 int gnf_adj_loss_dist_f32(const GnfCsr* csr, const float* z, int64_t ld, int32_t D, int32_t max_nodes_per_graph,

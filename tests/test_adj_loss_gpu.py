@@ -237,7 +237,7 @@ def test_captured_call_replays_on_new_embeddings():
     cg = torch.cuda.CUDAGraph()
     with torch.cuda.graph(cg):
         captured = binary_loss(emb, true, grad="sum", max_nodes_per_graph=65)
-    for seed in (11, 12):
+    for seed in (11, 12, 13, 14):   # (a workspace zeroed by a memset node lost rows from the second replay on)
         emb.nodes.copy_(torch.as_tensor(R.embeddings(R.SIZES, 64, seed)).to(DEV))
         for v in captured.values():
             v.zero_()

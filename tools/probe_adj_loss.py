@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer probe: the adjacency reconstruction loss, the device route against the dense route a user has without it.
-  device  adj_loss.binary_loss (gnf_adj_loss_f32): loss, per-graph loss, pair counts and (second timing) dL/dnodes from the
-          embeddings and the true batch's CSR; nothing reaches the host
+  device  adj_loss.binary_loss (gnf_adj_loss_dist_f32, as every token): loss, per-graph loss, pair counts and (second timing)
+          dL/dnodes from the embeddings and the true batch's CSR; nothing reaches the host
   dense   flow.pred_adj for the per-graph probability blocks, put on one [N, N] matrix (torch.block_diag) and compared with the
           dense true adjacency in ONE masked comparison per count, summed per graph with index_add; and a torch restatement
           of loss.py's binary_loss on the device - dense [N, N] true adjacency, dense logits in the reference's matmul
@@ -14,9 +14,11 @@ on
                8 .. 19 nodes, D = 200, against symmetric G(n, 0.3) graphs with a self loop per node - both routes are
                launch-bound here
 Embeddings: N(0, 1) * 0.5 * D^-1/4 with one row in eight stretched by 4 (the tests' distribution: every branch sees pairs).
-Beside the device route, the same call through gnf_adj_loss_dist_f32 (adj_loss.TunedSigmoidL2(10, 1): temp and shift read
-from device memory) without a gradient, with dL/dnodes, and with dL/dnodes and dL/d(temp, shift) - its outputs are asserted
-bit-equal to the device route's first, so the three timings price the run-time parameter load and the two extra fp64 sums.
+Beside the device route, the same call with adj_loss.TunedSigmoidL2(10, 1) (temp and shift read from device memory) without
+a gradient, with dL/dnodes, and with dL/dnodes and dL/d(temp, shift) - its outputs are asserted bit-equal to the device
+route's first.  Since the two library paths were merged the `device` and `dist` columns time the same kernels through the same
+entry point: they differ by the run-time parameter load, and `dist_grad_params` adds the stores and sums of the two extra fp64
+row sums.  The columns are kept so that figures stay comparable with earlier records.
 Both routes run on one machine, after a warm-up, as repeated timed regions (20 calls each) that end in a device synchronise;
 the routes are alternated inside every repeat and median, min and max over the repeats go out as one JSON line per workload,
 with dense_over_device for the call without and with the gradient.  Before anything is timed the two routes are compared
