@@ -178,10 +178,15 @@ static HalfStep half_step(const GnfCsr* csr, const GnfGnnSpec& gnn, const GnfMlp
     hs.s_net = s_net, hs.t_net = t_net;
     return hs;
 }
-// ... of a flow on x [n, 2 H]: half 0 conditions on columns [0, H) and updates [H, 2 H), half 1 the other way round
+// (i, half) of a flow on x [n, 2 H], each written once: the first column of the half that half-step `half` conditions on and its
+// bijector normalises (half 0 conditions on columns [0, H) and updates [H, 2 H), half 1 the other way round); its slot in what
+// the walk keeps per half-step (stashes, row sums, bn_c, (scale, shift) pairs); its bijector (GnfFlow.bns: half * T + i)
+static int cond_col(int32_t H, int half) { return half == 0 ? 0 : H; }
+static int half_slot(int i, int half) { return 2 * i + half; }
+static const GnfBatchNorm* flow_bn(const GnfFlow* flow, int half, int i) { return &flow->bns[half * flow->num_timesteps + i]; }
 static HalfStep half_step(const GnfCsr* csr, const GnfFlow* flow, float* x, int64_t ld, int32_t H, int32_t direction, int half, int i) {
     return half_step(csr, flow->gnn, flow_net(flow, flow->s_nets, half, i), flow_net(flow, flow->t_nets, half, i),
-                     x + (half == 0 ? 0 : H), x + (half == 0 ? H : 0), ld, H, direction);
+                     x + cond_col(H, half), x + cond_col(H, 1 - half), ld, H, direction);
 }
 
 // Argument checks shared by the whole-flow entry points (forward / inverse / backward).
@@ -410,20 +415,17 @@ int gnf_grevnet_f32(const GnfCsr* csr, const GnfFlow* flow, float* x, int64_t ld
     return gnf_grevnet_from_f32(csr, flow, nullptr, 0, x, ld, D, direction, sums, ws, ws_bytes, stream);
 }
 
-// The walk over the flow's half-steps behind gnf_grevnet_from_f32, gnf_grevnet_per_graph_f32 and
-// gnf_grevnet_inverse_per_graph_f32.  row_ld (NULL for the first): 2T slots of n doubles - half-step idx = 2 i + half, in
-// either direction, leaves + sum_j s[r, j] of the s its coupling used for every row in slot idx, through the ROWLD instance
-// of whichever kernel runs it; bn_c: 2T doubles, bijector idx's per-node log-det term - forward: written by the pass that
-// takes the batch moments; inverse: constants of the flow (the moving statistics), one launch in front of the walk.  With
-// both NULL the launch sequence of either direction is the one it always was.
-static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
-                       int32_t D, int32_t direction, double* sums, void* ws, size_t ws_bytes, gnf_stream_t stream,
-                       double* row_ld, double* bn_c) {
-    g_route = 0;
-    int rc = validate_flow_call(csr, flow, ld, D, "gnf_grevnet_f32");
+static WorkspacePlan walk_plan(const GnfCsr* csr, const GnfFlow* flow, int32_t D) {
+    return plan_workspace(csr->n_nodes, D / 2, flow_net_count(flow) ? &flow->s_nets[0] : nullptr, flow->gnn.combine,
+                          2 * (int64_t)(flow->num_timesteps > 0 ? flow->num_timesteps : 1));
+}
+
+// What a call of the walk (grevnet_walk) is checked for.  flow_checked: the caller has run validate_flow_call under its own name.
+static int validate_walk_call(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, const float* x, int64_t ld,
+                              int32_t D, int32_t direction, const double* sums, const void* ws, size_t ws_bytes, bool flow_checked) {
+    int rc = flow_checked ? GNF_OK : validate_flow_call(csr, flow, ld, D, "gnf_grevnet_f32");
     if (rc) return rc;
-    if (x_src == x) x_src = nullptr;
-    if (x_src && ld_src < D) {
+    if (x_src && x_src != x && ld_src < D) {
         set_error("gnf_grevnet_from_f32: ld_src=%lld < D=%d", (long long)ld_src, D);
         return GNF_ESHAPE;
     }
@@ -431,55 +433,62 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
         set_error("gnf_grevnet_f32: direction=%d", direction);
         return GNF_EINVAL;
     }
-    const int H = D / 2;
-    const int T = flow->num_timesteps;
-    const int n_nets = flow_net_count(flow);
     if (direction == GNF_FORWARD && !sums) {
         set_error("gnf_grevnet_f32: FORWARD needs a device sums[2] buffer");
         return GNF_EINVAL;
     }
     if (flow->bns)
-        for (int q = 0; q < 2 * T; ++q) {
+        for (int q = 0; q < 2 * flow->num_timesteps; ++q) {
             rc = validate_bn(&flow->bns[q], direction, "gnf_grevnet_f32", q);
             if (rc) return rc;
         }
-    const int64_t n = csr->n_nodes;
-    if (n > 0 && (!x || !ws)) {
+    if (csr->n_nodes > 0 && (!x || !ws)) {
         set_error("gnf_grevnet_f32: null x/ws");
         return GNF_EINVAL;
     }
-    const WorkspacePlan p = plan_workspace(n, H, n_nets ? &flow->s_nets[0] : nullptr,
-                                           flow->gnn.combine, 2 * (int64_t)(T > 0 ? T : 1));
-    if (n > 0 && ws_bytes < p.total_bytes) {
-        set_error("gnf_grevnet_f32: workspace %zu < %zu bytes", ws_bytes, p.total_bytes);
+    const size_t need = walk_plan(csr, flow, D).total_bytes;
+    if (csr->n_nodes > 0 && ws_bytes < need) {
+        set_error("gnf_grevnet_f32: workspace %zu < %zu bytes", ws_bytes, need);
         return GNF_EWORKSPACE;
     }
+    return GNF_OK;
+}
+
+// The walk over the flow's half-steps behind gnf_grevnet_from_f32, gnf_grevnet_per_graph_f32 and gnf_grevnet_inverse_per_graph_f32,
+// on a call that passed validate_walk_call (or the caller's own checks).  row_ld (NULL for the first): 2T slots of n doubles -
+// half-step idx = 2 i + half, in either direction, leaves + sum_j s[r, j] of the s its coupling used for every row in slot idx,
+// through the ROWLD instance of whichever kernel runs it; bn_c: 2T doubles, bijector idx's per-node log-det term - forward:
+// written by the pass that takes the batch moments; inverse: constants of the flow (the moving statistics), one launch in
+// front of the walk.  With both NULL the launch sequence of either direction is the one it always was.
+static int grevnet_walk(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
+                        int32_t D, int32_t direction, double* sums, void* ws, gnf_stream_t stream, double* row_ld, double* bn_c) {
+    const int H = D / 2;
+    const int T = flow->num_timesteps;
+    const int n_nets = flow_net_count(flow);
+    const int64_t n = csr->n_nodes;
+    const WorkspacePlan p = walk_plan(csr, flow, D);
+    int rc;
+    if (x_src == x) x_src = nullptr;
     hipStream_t st = (hipStream_t)stream;
     double* partials = (double*)ws;
     float* scratch = (float*)((char*)ws + p.partial_bytes);
-    float* half0 = x;       // columns [0, H)
-    float* half1 = x + H;   // columns [H, D)
     int64_t used = 0;       // partial slots written so far (packed densely, fixed order)
     // Out of place (x_src -> x): the first half-step of the walk reads the source buffer and writes the destination
     // (its conditioning rows copied on the way) when the fused both-nets kernel runs it; otherwise one copy pass
     // up front and the in-place walk.  A batch-norm bijector in front of the first half-step rewrites the
     // conditioning half in place, so such flows copy first too.
-    bool first_oop = false;
-    if (x_src && n > 0) {
-        if (T > 0 && ld_src == ld && !(direction == GNF_FORWARD && flow->bns)) {
-            const int h0_ = direction == GNF_FORWARD ? 0 : 1, i0_ = direction == GNF_FORWARD ? 0 : T - 1;
-            first_oop = fused_supports_oop(half_step(csr, flow, x, ld, H, direction, h0_, i0_));
-        }
-        if (!first_oop) {
-            rc = launch_copy_rows(x_src, ld_src, x, ld, n, D, st);
-            if (rc) return rc;
-        }
+    const bool fwd = direction == GNF_FORWARD;
+    const int half_first = fwd ? 0 : 1, i_first = fwd ? 0 : T - 1;
+    const bool first_oop = x_src && n > 0 && T > 0 && ld_src == ld && !(fwd && flow->bns) &&
+                           fused_supports_oop(half_step(csr, flow, x, ld, H, direction, half_first, i_first));
+    if (x_src && n > 0 && !first_oop) {
+        rc = launch_copy_rows(x_src, ld_src, x, ld, n, D, st);
+        if (rc) return rc;
     }
     // attention nets on a sparse batch: the weights of every net go into fragment order ONCE per call (one small launch)
     // and the one-launch front-end of gnf_attn_front.hip runs per half-step (the attn_kernel option keeps the two-launch
     // kernels)
     const float* attn_pack = nullptr;
-    const int32_t* attn_tiles = nullptr;
     if (n > 0 && n_nets > 0 && flow->s_nets[0].attn && csr->n_edges > 0 && csr->n_edges < 24 * n &&
         !opt(OPT_ATTN_KERNEL) && attn_front_fused_ok(flow->s_nets[0].attn, H)) {
         const GnfAttn* all[2 * 64];
@@ -494,59 +503,31 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
             // ... and every tile's sender window, once for the 2 T half-steps of the call
             rc = launch_attn_tiles(csr->rowptr, csr->col, n, reinterpret_cast<int32_t*>(scratch + p.attn_tile_offset), st);
             if (rc) return rc;
-            attn_tiles = reinterpret_cast<const int32_t*>(scratch + p.attn_tile_offset);
         }
     }
-    auto mark_attn = [&](HalfStep& hs, int half, int i) {
-        if (!attn_pack) return;
-        const int q = flow->weight_sharing ? half : half * T + i;
-        hs.attn_packed[0] = attn_pack + (size_t)q * p.attn_pack_per_net;
-        hs.attn_packed[1] = attn_pack + (size_t)(n_nets + q) * p.attn_pack_per_net;
-        hs.attn_tiles = attn_tiles;
-    };
     // split row tiles of the large-batch kernel (message-passing nets, batches of more than two row tiles per CU): their
     // flags are zeroed once per call, every half-step launch gets a value of its own
-    int32_t split_epoch = 0;
+    bool split = false;
     if (n_nets > 0 && !flow->s_nets[0].attn && n > (int64_t)32 * big_cu_count()) {
         const HalfScratch hsl = half_scratch(n, flow->s_nets[0].dims[0], hidden_max(&flow->s_nets[0]), H);
         if (hsl.split_fits()) {
             GNF_HIP_TRY(hipMemsetAsync(scratch + hsl.split_flags, 0, kBigSplitMax * sizeof(int), st));
-            split_epoch = 1;
+            split = true;
         }
     }
-    bool first = true;
-    auto mark_first = [&](HalfStep& hs, int half) {
-        if (!first) return;
-        first = false;
-        if (first_oop) {
-            const int co = half == 0 ? 0 : H, uo = half == 0 ? H : 0;
-            hs.x_cond = x_src + co;
-            hs.x_upd_src = x_src + uo;
-            hs.cond_copy = x + co;
-        }
-    };
     // the forward pass leaves every half-step's attention front-end in the caller's stash for the backward pass
-    const size_t stash_slot = attn_stash_slot_floats(flow, n);
-    float* stash = nullptr;
-    if (direction == GNF_FORWARD && flow->attn_stash && stash_slot > 0) {
-        if (flow->attn_stash_bytes < (size_t)2 * T * stash_slot * sizeof(float)) {
-            set_error("gnf_grevnet_f32: attn_stash %zu < %zu bytes", flow->attn_stash_bytes,
-                      (size_t)2 * T * stash_slot * sizeof(float));
-            return GNF_EWORKSPACE;
-        }
-        stash = flow->attn_stash;
-    }
     // ... and, for message-passing nets on small batches, every row its MLP kernels would recompute (ABI v8)
-    float* mstash = nullptr;
-    size_t mstash_slot = 0;
-    if (direction == GNF_FORWARD && flow->mlp_stash && n > 0 && mlp_stash_supported(flow, n, H)) {
-        mstash_slot = mlp_stash_layout(&flow->s_nets[0], n, H).slot;
-        if (flow->mlp_stash_bytes < (size_t)2 * T * mstash_slot * sizeof(float)) {
-            set_error("gnf_grevnet_f32: mlp_stash %zu < %zu bytes", flow->mlp_stash_bytes,
-                      (size_t)2 * T * mstash_slot * sizeof(float));
-            return GNF_EWORKSPACE;
-        }
-        mstash = flow->mlp_stash;
+    const size_t stash_slot = attn_stash_slot_floats(flow, n);
+    const size_t mstash_slot = fwd && flow->mlp_stash && n > 0 && mlp_stash_supported(flow, n, H) ? mlp_stash_layout(&flow->s_nets[0], n, H).slot : 0;
+    float* const stash = fwd && stash_slot > 0 ? flow->attn_stash : nullptr;
+    float* const mstash = mstash_slot > 0 ? flow->mlp_stash : nullptr;
+    if (stash && flow->attn_stash_bytes < (size_t)2 * T * stash_slot * sizeof(float)) {
+        set_error("gnf_grevnet_f32: attn_stash %zu < %zu bytes", flow->attn_stash_bytes, (size_t)2 * T * stash_slot * sizeof(float));
+        return GNF_EWORKSPACE;
+    }
+    if (mstash && flow->mlp_stash_bytes < (size_t)2 * T * mstash_slot * sizeof(float)) {
+        set_error("gnf_grevnet_f32: mlp_stash %zu < %zu bytes", flow->mlp_stash_bytes, (size_t)2 * T * mstash_slot * sizeof(float));
+        return GNF_EWORKSPACE;
     }
 
     // sum(z^2): per-workgroup partials out of the coupling epilogues of the last two half-steps instead of a k_gauss
@@ -555,119 +536,127 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
     double* const gpart = partials + 2 * (int64_t)(T > 0 ? T : 1) * p.partial_stride;
     int32_t nsq[2] = {0, 0};
     int32_t bn_pre = 0;  // partial rows the previous half-step's kernel left for the next bijector's moments (0: none)
-    bool bn_on_load = false;  // the bijectors are applied by the half-step kernels themselves (decided at the walk's first half-step)
-    const GnfBatchNorm* inv_pending = nullptr;  // inverse pass: the bijector the next half-step of the walk applies on load
-    const bool sq_ok = direction == GNF_FORWARD && !flow->bns && T > 0 && 2 * ((n + 15) / 16) <= kMaxGaussBlocks;
-    if (n > 0) {
-        if (direction == GNF_FORWARD) {
-            for (int i = 0; i < T; ++i) {  // gnn.py:309-338
-                for (int half = 0; half < 2; ++half) {
-                    // gnn.py:310-313, 325-328: the bijector normalises the conditioning half first - as a pass of its own, or
-                    // (attention nets through the fused kernel's attention instance, fused_bn_on_load_ok) where that kernel
-                    // reads the rows, the rows in memory staying raw until the NEXT half-step's kernel rewrites them
-                    double* bn_slot = nullptr;
-                    if (flow->bns) bn_slot = partials + used, used += 1;
-                    int32_t np_ = 0;
-                    HalfStep hs = half_step(csr, flow, x, ld, H, GNF_FORWARD, half, i);
-                    hs.partials = partials + used, hs.n_partials = &np_;
-                    if (stash) hs.attn_region = stash + (size_t)(2 * i + half) * stash_slot;
-                    mark_first(hs, half);
-                    mark_attn(hs, half, i);
-                    if (split_epoch) hs.split_epoch = split_epoch++;
-                    if (mstash) hs.mlp_stash = mstash + (size_t)(2 * i + half) * mstash_slot;
-                    const int idx = 2 * i + half;
-                    if (row_ld) hs.row_logdet = row_ld + (size_t)idx * (size_t)n;
-                    if (flow->bns && idx == 0) {
-                        // decided once, for every half-step of the walk: ALL net pairs must fit the attention instance (a
-                        // C-ABI caller's nets may differ from pair to pair when weight_sharing = 0), else the separate passes
-                        bn_on_load = !flow->bn_allreduce;
-                        for (int i2 = 0; i2 < T && bn_on_load; ++i2)
-                            for (int h2 = 0; h2 < 2 && bn_on_load; ++h2) {
-                                HalfStep probe = hs;
-                                probe.s_net = flow_net(flow, flow->s_nets, h2, i2), probe.t_net = flow_net(flow, flow->t_nets, h2, i2);
-                                mark_attn(probe, h2, i2);
-                                bn_on_load = fused_bn_on_load_ok(probe);
-                            }
-                    }
-                    double* const bn_rows_in = partials + ((idx & 1) && bn_on_load ? p.bn_offset2 : p.bn_offset);
-                    double* const bn_rows_out = partials + (!(idx & 1) && bn_on_load ? p.bn_offset2 : p.bn_offset);
-                    if (flow->bns && !bn_on_load) {
-                        rc = launch_bn_normalize(flow, &flow->bns[half * T + i], half == 0 ? half0 : half1, ld, n, H,
-                                                 partials + p.bn_offset, bn_slot, st, bn_pre, bn_c ? bn_c + idx : nullptr);
-                        if (rc) return rc;
-                        bn_pre = 0;
-                    } else if (flow->bns) {
-                        int rows = bn_pre;
-                        if (rows == 0) {  // (the first bijector, or a predecessor that left no column sums)
-                            rc = launch_bn_stats(half == 0 ? half0 : half1, ld, n, H, bn_rows_in, st, &rows);
-                            if (rc) return rc;
-                        }
-                        float* consts = reinterpret_cast<float*>(partials + p.bn_const_offset);
-                        hs.bnc = &flow->bns[half * T + i];
-                        hs.bnc_part = bn_rows_in, hs.bnc_nparts = rows;
-                        hs.bnc_logdet = bn_slot;
-                        hs.bnc_c = bn_c ? bn_c + idx : nullptr;
-                        hs.bnc_const = consts + (size_t)idx * 2 * H;
-                        hs.bnu_const = idx > 0 ? consts + (size_t)(idx - 1) * 2 * H : nullptr;
-                        bn_pre = 0;
-                    }
+    bool bn_on_load = false;  // the bijectors are applied by the half-step kernels themselves (decided in front of the walk's first half-step)
+    const bool sq_ok = fwd && !flow->bns && T > 0 && 2 * ((n + 15) / 16) <= kMaxGaussBlocks;
+    const int bn_slots = fwd && flow->bns ? 1 : 0;  // forward: the bijector's log-det partial sits in front of the half-step's own
+    int32_t np_ = 0;  // partials the last half-step wrote
+    // The single place that turns (i, half) into a HalfStep of this call: nets and columns, where its partials and row sums
+    // go, the source buffer for the walk's first half-step when that one runs out of place, the packed attention weights and
+    // tile plan, the split epoch, the stash slots (forward only).  What rides along from one half-step to the next is the walks'.
+    auto resolve_half = [&](int i, int half) {
+        const size_t slot = half_slot(i, half);
+        const int launched = fwd ? (int)slot : 2 * T - 1 - (int)slot;  // half-steps of the walk in front of this one
+        HalfStep hs = half_step(csr, flow, x, ld, H, direction, half, i);
+        np_ = 0;
+        hs.partials = partials + used + bn_slots, hs.n_partials = &np_;
+        if (row_ld) hs.row_logdet = row_ld + slot * (size_t)n;
+        if (first_oop && launched == 0) {
+            hs.x_cond = x_src + cond_col(H, half);
+            hs.x_upd_src = x_src + cond_col(H, 1 - half);
+            hs.cond_copy = x + cond_col(H, half);
+        }
+        if (attn_pack) {
+            const size_t q = flow_net(flow, flow->s_nets, half, i) - flow->s_nets;
+            hs.attn_packed[0] = attn_pack + q * p.attn_pack_per_net;
+            hs.attn_packed[1] = attn_pack + (n_nets + q) * p.attn_pack_per_net;
+            hs.attn_tiles = reinterpret_cast<const int32_t*>(scratch + p.attn_tile_offset);
+        }
+        if (split) hs.split_epoch = 1 + launched;
+        if (stash) hs.attn_region = stash + slot * stash_slot;
+        if (mstash) hs.mlp_stash = mstash + slot * mstash_slot;
+        return hs;
+    };
+    // gnn.py:309-338
+    auto forward_walk = [&]() -> int {
+        float* const consts = reinterpret_cast<float*>(partials + p.bn_const_offset);  // bijector idx's (scale, shift) pairs: [2][H] each
+        // bn_on_load alternates the moment rows between two buffers, by the parity of the bijector that reads them
+        auto bn_rows = [&](int idx) { return partials + ((idx & 1) && bn_on_load ? p.bn_offset2 : p.bn_offset); };
+        // gnn.py:310-313, 325-328: the bijector normalises the conditioning half first - as a pass of its own, or
+        // (attention nets through the fused kernel's attention instance, fused_bn_on_load_ok) where that kernel
+        // reads the rows, the rows in memory staying raw until the NEXT half-step's kernel rewrites them
+        auto bijector_in_front = [&](HalfStep& hs, int i, int half) -> int {
+            const int idx = half_slot(i, half);
+            double* const c = bn_c ? bn_c + idx : nullptr;
+            int rows = bn_pre;
+            bn_pre = 0;
+            if (!bn_on_load)
+                return launch_bn_normalize(flow, flow_bn(flow, half, i), x + cond_col(H, half), ld, n, H, partials + p.bn_offset,
+                                           partials + used, st, rows, c);
+            if (rows == 0) {  // (the first bijector, or a predecessor that left no column sums)
+                const int rc = launch_bn_stats(x + cond_col(H, half), ld, n, H, bn_rows(idx), st, &rows);
+                if (rc) return rc;
+            }
+            hs.bnc = flow_bn(flow, half, i);
+            hs.bnc_part = bn_rows(idx), hs.bnc_nparts = rows;
+            hs.bnc_logdet = partials + used;
+            hs.bnc_c = c;
+            hs.bnc_const = consts + (size_t)idx * 2 * H;
+            hs.bnu_const = idx > 0 ? consts + (size_t)(idx - 1) * 2 * H : nullptr;
+            return GNF_OK;
+        };
+        // decided once, for every half-step of the walk: ALL net pairs must fit the attention instance (a
+        // C-ABI caller's nets may differ from pair to pair when weight_sharing = 0), else the separate passes
+        bn_on_load = flow->bns && T > 0 && !flow->bn_allreduce;
+        for (int i = 0; i < T && bn_on_load; ++i)
+            for (int half = 0; half < 2 && bn_on_load; ++half) bn_on_load = fused_bn_on_load_ok(resolve_half(i, half));
+        for (int i = 0; i < T; ++i) {
+            for (int half = 0; half < 2; ++half) {
+                HalfStep hs = resolve_half(i, half);
+                if (flow->bns) {
+                    rc = bijector_in_front(hs, i, half);
+                    if (rc) return rc;
                     // the half this half-step updates is what the NEXT bijector normalises: its column sums ride along
-                    if (flow->bns && !(i == T - 1 && half == 1) && (n + 15) / 16 <= kBnPartRowsMax) {
-                        hs.bn_part = bn_rows_out;
+                    if (!(i == T - 1 && half == 1) && (n + 15) / 16 <= kBnPartRowsMax) {
+                        hs.bn_part = bn_rows(half_slot(i, half) + 1);
                         hs.n_bn = &bn_pre;
                     }
-                    if (sq_ok && i == T - 1) {  // the outputs of the flow's last two half-steps are z: sum(z^2) rides along
-                        hs.sq_partials = gpart + (half == 0 ? 0 : nsq[0]);
-                        hs.n_sq = &nsq[half];
-                    }
-                    rc = run_half(hs, scratch, st);
-                    if (rc) return rc;
-                    used += np_;
                 }
-            }
-            if (bn_on_load && T > 0) {  // the last bijector's conditioning half (columns [H, D)) is still raw in memory
-                rc = launch_bn_affine(half1, ld, n, H, reinterpret_cast<const float*>(partials + p.bn_const_offset) + (size_t)(2 * T - 1) * 2 * H, st);
-                if (rc) return rc;
-            }
-        } else {
-            if (bn_c && flow->bns) {
-                rc = launch_bn_inverse_terms(flow, H, bn_c, st);
-                if (rc) return rc;
-            }
-            for (int i = T - 1; i >= 0; --i) {  // gnn.py:347-372
-                for (int half = 1; half >= 0; --half) {
-                    int32_t np_ = 0;
-                    HalfStep hs = half_step(csr, flow, x, ld, H, GNF_INVERSE, half, i);
-                    hs.partials = partials + used, hs.n_partials = &np_;
-                    // (the s the coupling uses comes from the conditioning half as it is BEFORE its bijector below)
-                    if (row_ld) hs.row_logdet = row_ld + (size_t)(2 * i + half) * (size_t)n;
-                    mark_first(hs, half);
-                    mark_attn(hs, half, i);
-                    if (split_epoch) hs.split_epoch = split_epoch++;
-                    // gnn.py:356-358, 369-371: bn.forward (moving statistics) on the conditioning half AFTER the half-step - a
-                    // pass of its own, or (fused attention instance) left for the next half-step of the walk, which rewrites
-                    // exactly that half, to apply where it reads the old value
-                    if (flow->bns && i == T - 1 && half == 1) bn_on_load = fused_bn_on_load_ok(hs);
-                    if (bn_on_load) hs.bnu_inv = inv_pending;
-                    rc = run_half(hs, scratch, st);
-                    if (rc) return rc;
-                    // partial slots are reused: the inverse pass has no batch log-det (gnn.py:343-373; the per-graph entry
-                    // point takes it from the row sums)
-                    if (flow->bns && bn_on_load) {
-                        inv_pending = &flow->bns[half * T + i];
-                    } else if (flow->bns) {
-                        rc = launch_bn_denormalize(&flow->bns[half * T + i], half == 0 ? half0 : half1, ld, n, H, st);
-                        if (rc) return rc;
-                    }
+                if (sq_ok && i == T - 1) {  // the outputs of the flow's last two half-steps are z: sum(z^2) rides along
+                    hs.sq_partials = gpart + (half == 0 ? 0 : nsq[0]);
+                    hs.n_sq = &nsq[half];
                 }
-            }
-            if (inv_pending) {  // the walk's last half-step (i = 0, half = 0): its conditioning half is columns [0, H)
-                rc = launch_bn_denormalize(inv_pending, half0, ld, n, H, st);
+                rc = run_half(hs, scratch, st);
                 if (rc) return rc;
+                used += bn_slots + np_;
             }
         }
-    }
-    if (direction == GNF_FORWARD) {
+        // bn_on_load: the last bijector's conditioning half (columns [H, D)) is still raw in memory
+        return bn_on_load ? launch_bn_affine(x + cond_col(H, 1), ld, n, H, consts + (size_t)half_slot(T - 1, 1) * 2 * H, st) : GNF_OK;
+    };
+    // gnn.py:347-372
+    auto inverse_walk = [&]() -> int {
+        if (bn_c && flow->bns) {
+            rc = launch_bn_inverse_terms(flow, H, bn_c, st);
+            if (rc) return rc;
+        }
+        // gnn.py:356-358, 369-371: bn.forward (moving statistics) on the conditioning half AFTER the half-step - a
+        // pass of its own, or (fused attention instance: the walk's first half-step decides) left for the next half-step
+        // of the walk, which rewrites exactly that half, to apply where it reads the old value
+        const GnfBatchNorm* inv_pending = nullptr;  // the bijector the next half-step of the walk applies on load
+        bn_on_load = flow->bns && T > 0 && fused_bn_on_load_ok(resolve_half(i_first, half_first));
+        for (int i = T - 1; i >= 0; --i) {
+            for (int half = 1; half >= 0; --half) {
+                // (the s the coupling uses, and its row sums, come from the conditioning half as it is BEFORE its bijector below)
+                HalfStep hs = resolve_half(i, half);
+                hs.bnu_inv = inv_pending;
+                rc = run_half(hs, scratch, st);
+                if (rc) return rc;
+                // partial slots are reused: the inverse pass has no batch log-det (gnn.py:343-373; the per-graph entry
+                // point takes it from the row sums)
+                if (bn_on_load) {
+                    inv_pending = flow_bn(flow, half, i);
+                } else if (flow->bns) {
+                    rc = launch_bn_denormalize(flow_bn(flow, half, i), x + cond_col(H, half), ld, n, H, st);
+                    if (rc) return rc;
+                }
+            }
+        }
+        // the walk's last half-step (i = 0, half = 0): its conditioning half is columns [0, H)
+        return inv_pending ? launch_bn_denormalize(inv_pending, x + cond_col(H, 0), ld, n, H, st) : GNF_OK;
+    };
+    rc = n == 0 ? GNF_OK : fwd ? forward_walk() : inverse_walk();
+    if (rc) return rc;
+    if (fwd) {
         // (measured and dropped, tools/ab_options.py: k_gauss + k_finalize merged into one launch whose last-arriving
         // workgroup runs the final reduction - the release / ticket / acquire hand-off costs 1 us more than the launch
         // boundary it removes, CHANGELOG.md section 4.4)
@@ -685,7 +674,10 @@ static int grevnet_run(const GnfCsr* csr, const GnfFlow* flow, const float* x_sr
 
 int gnf_grevnet_from_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
                          int32_t D, int32_t direction, double* sums, void* ws, size_t ws_bytes, gnf_stream_t stream) {
-    return grevnet_run(csr, flow, x_src, ld_src, x, ld, D, direction, sums, ws, ws_bytes, stream, nullptr, nullptr);
+    g_route = 0;
+    const int rc = validate_walk_call(csr, flow, x_src, ld_src, x, ld, D, direction, sums, ws, ws_bytes, false);
+    if (rc) return rc;
+    return grevnet_walk(csr, flow, x_src, ld_src, x, ld, D, direction, sums, ws, stream, nullptr, nullptr);
 }
 
 // workspace of the per-graph entry points, forward and inverse (PerGraphLayout, gnf_layout.h)
@@ -698,58 +690,12 @@ size_t gnf_per_graph_workspace_bytes(int64_t n_nodes, int64_t n_graphs, int32_t 
     return per_graph_ws(n_nodes, D, flow).total;
 }
 
-int gnf_grevnet_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
-                              int32_t D, double* sums, double* graph_out, void* ws, size_t ws_bytes, gnf_stream_t stream) {
-    int rc = validate_flow_call(csr, flow, ld, D, "gnf_grevnet_per_graph_f32");
-    if (rc) return rc;
-    const int64_t n = csr->n_nodes, B = csr->n_graphs;
-    // every GNN family needs the graph boundaries here, not only graph-scope attention
-    if (B < 0 || B >= INT32_MAX || (n > 0 && B < 1) || ((n > 0 || B > 0) && !csr->node_offsets)) {
-        set_error("gnf_grevnet_per_graph_f32: needs GnfCsr.node_offsets (device int32 [n_graphs + 1]) and n_graphs >= 1; got node_offsets=%p n_graphs=%lld", (const void*)csr->node_offsets, (long long)B);
-        return GNF_EINVAL;
-    }
-    if (!sums || (B > 0 && !graph_out)) {
-        set_error("gnf_grevnet_per_graph_f32: null sums / graph_out");
-        return GNF_EINVAL;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 0) {  // nothing to transform: zeros in sums and in every graph's entries (no graphs: no device work at all)
-        if (B > 0) {
-            GNF_HIP_TRY(hipMemsetAsync(sums, 0, 2 * sizeof(double), st));
-            GNF_HIP_TRY(hipMemsetAsync(graph_out, 0, (size_t)B * 2 * sizeof(double), st));
-        }
-        return GNF_OK;
-    }
-    const size_t need = gnf_per_graph_workspace_bytes(n, B, D, flow);
-    if (!ws || ws_bytes < need) {
-        set_error("gnf_grevnet_per_graph_f32: workspace %zu < %zu bytes (gnf_per_graph_workspace_bytes)", ws_bytes, need);
-        return ws ? GNF_EWORKSPACE : GNF_EINVAL;
-    }
-    const int T = flow->num_timesteps;
-    const PerGraphLayout L = per_graph_ws(n, D, flow);
-    const size_t base = L.base;
-    double* row_ld = reinterpret_cast<double*>((char*)ws + L.row_ld);
-    double* bn_c = reinterpret_cast<double*>((char*)ws + L.bn_c);
-    // the inference walk: the training stashes are not written by this entry point
-    GnfFlow fl = *flow;
-    fl.attn_stash = nullptr, fl.attn_stash_bytes = 0, fl.mlp_stash = nullptr, fl.mlp_stash_bytes = 0;
-    rc = grevnet_run(csr, &fl, x_src, ld_src, x, ld, D, GNF_FORWARD, sums, ws, base, stream, row_ld, flow->bns ? bn_c : nullptr);
-    if (rc) return rc;
-    return launch_per_graph(row_ld, 2 * T, n, bn_c, flow->bns ? 2 * T : 0, x, ld, D, csr->node_offsets, B, graph_out, st);
-}
-
 size_t gnf_inverse_per_graph_workspace_bytes(int64_t n_nodes, int64_t n_graphs, int32_t D, const GnfFlow* flow) {
-    if (n_nodes < 0 || n_graphs < 0 || D < 2 || !flow || !flow->s_nets) return 0;
-    return per_graph_ws(n_nodes, D, flow).total;
+    return gnf_per_graph_workspace_bytes(n_nodes, n_graphs, D, flow);
 }
 
-int gnf_grevnet_inverse_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const float* z_src, int64_t ld_src, float* x,
-                                      int64_t ld, int32_t D, double* sums, double* graph_out, void* ws, size_t ws_bytes,
-                                      gnf_stream_t stream) {
-    const char* const what = "gnf_grevnet_inverse_per_graph_f32";
-    g_route = 0;
-    int rc = validate_flow_call(csr, flow, ld, D, what);
-    if (rc) return rc;
+// What both per-graph entry points ask of the batch and of their outputs, after validate_flow_call under their own name.
+static int validate_per_graph_call(const char* what, const GnfCsr* csr, const double* sums, const double* graph_out) {
     const int64_t n = csr->n_nodes, B = csr->n_graphs;
     // every GNN family needs the graph boundaries here, not only graph-scope attention
     // (a batch without nodes and without graphs is the one call that has no boundaries to give)
@@ -761,6 +707,60 @@ int gnf_grevnet_inverse_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, co
         set_error("%s: null sums / graph_out", what);
         return GNF_EINVAL;
     }
+    return GNF_OK;
+}
+
+// The inference walk: these entry points write no training stash; keep_allreduce = false: nothing of the call crosses ranks.
+static GnfFlow inference_flow(const GnfFlow* flow, bool keep_allreduce) {
+    GnfFlow fl = *flow;
+    fl.attn_stash = nullptr, fl.attn_stash_bytes = 0, fl.mlp_stash = nullptr, fl.mlp_stash_bytes = 0;
+    if (!keep_allreduce) fl.bn_allreduce = nullptr;
+    return fl;
+}
+
+int gnf_grevnet_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const float* x_src, int64_t ld_src, float* x, int64_t ld,
+                              int32_t D, double* sums, double* graph_out, void* ws, size_t ws_bytes, gnf_stream_t stream) {
+    int rc = validate_flow_call(csr, flow, ld, D, "gnf_grevnet_per_graph_f32");
+    if (rc) return rc;
+    rc = validate_per_graph_call("gnf_grevnet_per_graph_f32", csr, sums, graph_out);
+    if (rc) return rc;
+    const int64_t n = csr->n_nodes, B = csr->n_graphs;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {  // nothing to transform: zeros in sums and in every graph's entries (no graphs: no device work at all)
+        if (B > 0) {
+            GNF_HIP_TRY(hipMemsetAsync(sums, 0, 2 * sizeof(double), st));
+            GNF_HIP_TRY(hipMemsetAsync(graph_out, 0, (size_t)B * 2 * sizeof(double), st));
+        }
+        return GNF_OK;
+    }
+    const PerGraphLayout L = per_graph_ws(n, D, flow);
+    if (!ws || ws_bytes < L.total) {
+        set_error("gnf_grevnet_per_graph_f32: workspace %zu < %zu bytes (gnf_per_graph_workspace_bytes)", ws_bytes, L.total);
+        return ws ? GNF_EWORKSPACE : GNF_EINVAL;
+    }
+    const int T = flow->num_timesteps;
+    double* row_ld = reinterpret_cast<double*>((char*)ws + L.row_ld);
+    double* bn_c = reinterpret_cast<double*>((char*)ws + L.bn_c);
+    // what the walk itself asks: ld_src, the bijectors, x (the flow is checked above, and L.base covers the walk's plan)
+    g_route = 0;
+    rc = validate_walk_call(csr, flow, x_src, ld_src, x, ld, D, GNF_FORWARD, sums, ws, L.base, true);
+    if (rc) return rc;
+    const GnfFlow fl = inference_flow(flow, true);
+    rc = grevnet_walk(csr, &fl, x_src, ld_src, x, ld, D, GNF_FORWARD, sums, ws, stream, row_ld, flow->bns ? bn_c : nullptr);
+    if (rc) return rc;
+    return launch_per_graph(row_ld, 2 * T, n, bn_c, flow->bns ? 2 * T : 0, x, ld, D, csr->node_offsets, B, graph_out, st);
+}
+
+int gnf_grevnet_inverse_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, const float* z_src, int64_t ld_src, float* x,
+                                      int64_t ld, int32_t D, double* sums, double* graph_out, void* ws, size_t ws_bytes,
+                                      gnf_stream_t stream) {
+    const char* const what = "gnf_grevnet_inverse_per_graph_f32";
+    g_route = 0;
+    int rc = validate_flow_call(csr, flow, ld, D, what);
+    if (rc) return rc;
+    rc = validate_per_graph_call(what, csr, sums, graph_out);
+    if (rc) return rc;
+    const int64_t n = csr->n_nodes, B = csr->n_graphs;
     if (z_src == x) z_src = nullptr;
     if (z_src && ld_src < D) {
         set_error("%s: ld_src=%lld < D=%d", what, (long long)ld_src, D);
@@ -789,18 +789,15 @@ int gnf_grevnet_inverse_per_graph_f32(const GnfCsr* csr, const GnfFlow* flow, co
     }
     double* row_ld = reinterpret_cast<double*>((char*)ws + L.row_ld);
     double* bn_c = reinterpret_cast<double*>((char*)ws + L.bn_c);
-    // the inference walk: nothing of g is stashed, and nothing of it crosses ranks
-    GnfFlow fl = *flow;
-    fl.attn_stash = nullptr, fl.attn_stash_bytes = 0, fl.mlp_stash = nullptr, fl.mlp_stash_bytes = 0;
-    fl.bn_allreduce = nullptr;
+    const GnfFlow fl = inference_flow(flow, false);
     const int n_c = flow->bns ? 2 * T : 0;
-    // Everything grevnet_run checks for an inverse call (the flow, ld_src, the bijectors, x / ws, the workspace size: L.base
-    // covers its plan) has been checked above, so what follows fails only where a launch itself fails.
+    // Everything validate_walk_call checks for an inverse call (the flow, ld_src, the bijectors, x / ws, the workspace size:
+    // L.base covers the walk's plan) has been checked above, so what follows fails only where a launch itself fails.
     if (!z_src) {  // in place: sum z^2 of every graph's rows before the walk overwrites them
         rc = launch_per_graph(nullptr, 0, n, nullptr, 0, x, ld, D, csr->node_offsets, B, graph_out, st, true);
         if (rc) return rc;
     }
-    rc = grevnet_run(csr, &fl, z_src, ld_src, x, ld, D, GNF_INVERSE, nullptr, ws, L.base, stream, row_ld, flow->bns ? bn_c : nullptr);
+    rc = grevnet_walk(csr, &fl, z_src, ld_src, x, ld, D, GNF_INVERSE, nullptr, ws, stream, row_ld, flow->bns ? bn_c : nullptr);
     if (rc) return rc;
     rc = launch_per_graph(row_ld, T > 0 ? 2 * T : 0, n, bn_c, n_c, z_src, ld_src, D, csr->node_offsets, B, graph_out, st, true);
     if (rc) return rc;

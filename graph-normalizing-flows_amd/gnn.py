@@ -817,8 +817,9 @@ class GRevNet:
         comm = self.bn_rccl_comm
         return (self._bn_sync_world(), comm.handle if comm is not None and self.use_batch_norm and self.sync_batch_norm else 0)
 
-    def _run(self, graph, direction, sums_out=None):
-        lib = _abi.lib()
+    def _prepare(self, graph, node_offsets, shard_check=True):
+        """What the library calls of the walk share: the checked nodes as float32 rows `src`, the new buffer `out`, the flow
+        and the batch's CSR descriptor -> (n, d, dev, src, out, flow, csr)."""
         x = graph.nodes
         if x.device.type != "cuda":
             raise _abi.GnfError("GRevNet runs on a HIP device only (no CPU path)")
@@ -833,10 +834,14 @@ class GRevNet:
             src = src.contiguous()
         out = torch.empty((n, d), dtype=torch.float32, device=dev)
         flow = self._flow(d // 2, dev)
-        if n == 0 and self._bn_sync_world() > 1:
+        if shard_check and n == 0 and self._bn_sync_world() > 1:
             raise ValueError("sync_batch_norm: a rank with an empty shard cannot take part in the cross-rank moments "
                              "(every rank must make the same sequence of all-reduce calls)")
-        csr = csr_desc(graph, csr_of(graph), self.graph_scope())
+        return n, d, dev, src, out, flow, csr_desc(graph, csr_of(graph), node_offsets)
+
+    def _run(self, graph, direction, sums_out=None):
+        lib = _abi.lib()
+        n, d, dev, src, out, flow, csr = self._prepare(graph, self.graph_scope())
         with torch.cuda.device(dev):   # (the planners read the CURRENT device's CU count: size and launch on the same one)
             ws_bytes = lib.gnf_workspace_bytes(n, d, C.byref(flow))
         ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
@@ -849,6 +854,26 @@ class GRevNet:
                                                 _abi.ptr(out), d, d, direction, _abi.ptr(sums), _abi.ptr(ws), ws_bytes,
                                                 _abi.stream_ptr(dev)), "gnf_grevnet_from_f32")
         return out, sums
+
+    def _run_per_graph(self, graph, sums_out, size_fn, call_fn, shard_check):
+        """f_per_graph / g_per_graph: the library call `call_fn` on a workspace of `size_fn` bytes; leaves `last_sums` and
+        `last_graph_sums` and returns the new nodes."""
+        lib = _abi.lib()
+        # (node_offsets for every GNN family: the per-graph reduction reads the graph boundaries)
+        n, d, dev, src, out, flow, csr = self._prepare(graph, True, shard_check)
+        b = int(graph.n_node.shape[0])
+        with torch.cuda.device(dev):
+            ws_bytes = getattr(lib, size_fn)(n, b, d, C.byref(flow))
+        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+        sums = sums_out if sums_out is not None else torch.zeros(2, dtype=torch.float64, device=dev)
+        graph_sums = torch.zeros((b, 2), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _abi.check(getattr(lib, call_fn)(C.byref(csr), C.byref(flow), _abi.ptr(src), src.stride(0) if n else d, _abi.ptr(out),
+                                             d, d, _abi.ptr(sums), _abi.ptr(graph_sums), _abi.ptr(ws), ws_bytes,
+                                             _abi.stream_ptr(dev)), call_fn)
+        self.last_sums = sums
+        self.last_graph_sums = graph_sums
+        return out
 
     # ---- the reference's methods --------------------------------------------------------------
     def f(self, x, sums_out=None):
@@ -863,37 +888,9 @@ class GRevNet:
         and the same batch sums as f, bit for bit.  Returns (GraphsTuple with nodes = z, logdet [B] device fp64);
         `last_graph_sums` holds the [B, 2] buffer (logdet_g, sum z^2 of graph g), `last_sums` what f leaves there.  With
         batch norm the bijectors' moments are those of the whole batch - what single-graph calls cannot reproduce."""
-        lib = _abi.lib()
-        nodes = x.nodes
-        if nodes.device.type != "cuda":
-            raise _abi.GnfError("GRevNet runs on a HIP device only (no CPU path)")
-        if nodes.ndim != 2 or nodes.shape[1] % 2:
-            raise ValueError(f"nodes must be [N, D] with even D (tf.split, gnn.py:306); got {tuple(nodes.shape)}")
-        n, d = nodes.shape
-        dev = nodes.device
-        b = int(x.n_node.shape[0])
-        src = nodes.to(torch.float32)
-        if n > 0 and (src.stride(1) != 1 or src.stride(0) < d):
-            src = src.contiguous()
-        out = torch.empty((n, d), dtype=torch.float32, device=dev)
-        flow = self._flow(d // 2, dev)
-        if n == 0 and self._bn_sync_world() > 1:
-            raise ValueError("sync_batch_norm: a rank with an empty shard cannot take part in the cross-rank moments "
-                             "(every rank must make the same sequence of all-reduce calls)")
-        csr = csr_desc(x, csr_of(x), True)   # every GNN family: the per-graph reduction reads the graph boundaries
-        with torch.cuda.device(dev):
-            ws_bytes = lib.gnf_per_graph_workspace_bytes(n, b, d, C.byref(flow))
-        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
-        sums = sums_out if sums_out is not None else torch.zeros(2, dtype=torch.float64, device=dev)
-        graph_sums = torch.zeros((b, 2), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _abi.check(lib.gnf_grevnet_per_graph_f32(C.byref(csr), C.byref(flow), _abi.ptr(src), src.stride(0) if n else d,
-                                                     _abi.ptr(out), d, d, _abi.ptr(sums), _abi.ptr(graph_sums), _abi.ptr(ws),
-                                                     ws_bytes, _abi.stream_ptr(dev)), "gnf_grevnet_per_graph_f32")
-        self.last_sums = sums
-        self.last_graph_sums = graph_sums
+        out = self._run_per_graph(x, sums_out, "gnf_per_graph_workspace_bytes", "gnf_grevnet_per_graph_f32", True)
         self._last_z = out
-        return x.replace(nodes=out), graph_sums[:, 0]
+        return x.replace(nodes=out), self.last_graph_sums[:, 0]
 
     def log_prob_per_graph(self, x):
         """log p(G_g) of every graph of the batch, [B] device fp64, from one forward pass (standard-normal prior)."""
@@ -911,34 +908,8 @@ class GRevNet:
         device fp64: log|det dg/dz| of each graph's block); `last_graph_sums` holds the [B, 2] buffer (logdet_g, sum z^2 of
         graph g's INPUT rows), `last_sums` their sums over the graphs, [2].  The bijectors of g use the moving statistics, so
         the graphs of a batch are independent even with batch norm: log p(x_g) = log N(z_g) - logdet_g[g]."""
-        lib = _abi.lib()
-        nodes = z.nodes
-        if nodes.device.type != "cuda":
-            raise _abi.GnfError("GRevNet runs on a HIP device only (no CPU path)")
-        if nodes.ndim != 2 or nodes.shape[1] % 2:
-            raise ValueError(f"nodes must be [N, D] with even D (tf.split, gnn.py:306); got {tuple(nodes.shape)}")
-        n, d = nodes.shape
-        dev = nodes.device
-        b = int(z.n_node.shape[0])
-        src = nodes.to(torch.float32)
-        if n > 0 and (src.stride(1) != 1 or src.stride(0) < d):
-            src = src.contiguous()
-        out = torch.empty((n, d), dtype=torch.float32, device=dev)
-        flow = self._flow(d // 2, dev)
-        csr = csr_desc(z, csr_of(z), True)   # every GNN family: the per-graph reduction reads the graph boundaries
-        with torch.cuda.device(dev):
-            ws_bytes = lib.gnf_inverse_per_graph_workspace_bytes(n, b, d, C.byref(flow))
-        ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
-        sums = sums_out if sums_out is not None else torch.zeros(2, dtype=torch.float64, device=dev)
-        graph_sums = torch.zeros((b, 2), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _abi.check(lib.gnf_grevnet_inverse_per_graph_f32(C.byref(csr), C.byref(flow), _abi.ptr(src), src.stride(0) if n else d,
-                                                             _abi.ptr(out), d, d, _abi.ptr(sums), _abi.ptr(graph_sums),
-                                                             _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
-                       "gnf_grevnet_inverse_per_graph_f32")
-        self.last_sums = sums
-        self.last_graph_sums = graph_sums
-        return z.replace(nodes=out), graph_sums[:, 0]
+        out = self._run_per_graph(z, sums_out, "gnf_inverse_per_graph_workspace_bytes", "gnf_grevnet_inverse_per_graph_f32", False)
+        return z.replace(nodes=out), self.last_graph_sums[:, 0]
 
     def log_prob(self, x):
         """gnn.py:375-377 with the prior the drivers use (standard normal, run_grevnet.py:292-294)."""

@@ -101,6 +101,35 @@ def test_argument_validation_without_a_gpu():
     assert lib.gnf_build_csr(None, None, None, None, 1, 4, 4, 0x1000, 0x1000, 0x1000, 1 << 20, None) == -1
 
 
+def test_flow_call_refusals_in_order_with_their_texts():
+    """gnf_grevnet_from_f32: what is checked after the flow itself, in the order it is checked - each call below is wrong in
+    everything the later ones are wrong in, and reports the first."""
+    lib = _abi.lib()
+    f = lib.gnf_grevnet_from_f32
+    csr = _abi.GnfCsr(0x1000, 0x1000, 10, 20)
+    nets = (_abi.GnfMlp * 2)(_mlp([4, 8, 4]), _mlp([4, 8, 4]))
+    bns = (_abi.GnfBatchNorm * 2)()
+    bns[0].gamma, bns[0].beta, bns[0].epsilon = 0x1000, 0x1000, 1e-3      # bijector 1: no gamma
+    flow = _abi.GnfFlow(1, 1, C.cast(nets, C.POINTER(_abi.GnfMlp)), C.cast(nets, C.POINTER(_abi.GnfMlp)),
+                        _abi.GnfGnnSpec(1, 0, 1.0, 1, 0.2), C.cast(bns, C.POINTER(_abi.GnfBatchNorm)))
+    assert f(C.byref(csr), C.byref(flow), 0x2000, 4, None, 8, 8, 5, None, None, 16, None) == -2
+    assert _err() == "gnf_grevnet_from_f32: ld_src=4 < D=8"
+    # (a source that is the destination is no source: its ld_src is not looked at)
+    assert f(C.byref(csr), C.byref(flow), 0x1000, 4, 0x1000, 8, 8, 5, None, None, 16, None) == -1
+    assert _err() == "gnf_grevnet_f32: direction=5"
+    assert f(C.byref(csr), C.byref(flow), 0x2000, 8, None, 8, 8, 0, None, None, 16, None) == -1
+    assert _err() == "gnf_grevnet_f32: FORWARD needs a device sums[2] buffer"
+    assert f(C.byref(csr), C.byref(flow), 0x2000, 8, None, 8, 8, 0, 0x1000, None, 16, None) == -1
+    assert _err() == "gnf_grevnet_f32: batch-norm 1 has null gamma / beta"
+    bns[1].gamma, bns[1].beta, bns[1].epsilon = 0x1000, 0x1000, 1e-3
+    assert f(C.byref(csr), C.byref(flow), 0x2000, 8, 0x1000, 8, 8, 1, None, 0x1000, 1 << 20, None) == -1
+    assert _err() == "gnf_grevnet_f32: batch-norm 0 has null gamma / beta / moving statistics"
+    assert f(C.byref(csr), C.byref(flow), 0x2000, 8, None, 8, 8, 0, 0x1000, None, 16, None) == -1
+    assert _err() == "gnf_grevnet_f32: null x/ws"
+    assert f(C.byref(csr), C.byref(flow), 0x2000, 8, 0x1000, 8, 8, 0, 0x1000, 0x1000, 16, None) == -3
+    assert _err() == f"gnf_grevnet_f32: workspace 16 < {lib.gnf_workspace_bytes(10, 8, C.byref(flow))} bytes"
+
+
 def test_empty_batch_is_a_no_op_success():
     """N = 0 returns GNF_OK without touching the device (validation only)."""
     lib = _abi.lib()

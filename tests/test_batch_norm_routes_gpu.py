@@ -4,7 +4,7 @@ The bijector's two-level fp64 reduction of [parts][H][2] partial rows exists man
 k_bn_apply, the column sums of the fused forward kernel and of k_coupling_rows, the bijector on load of the attention
 instance + k_bn_affine, k_bn_denorm and the deferred inverse of k_half_fused, k_bn_bwd_stats / k_bn_bwd_apply, the rows
 k_attn_bwd_dx_mfma leaves, the fold into the fused backward prologue, k_bn_post_step); which copy runs is decided in
-grevnet_run (gnf_abi.hip) and the backward walk (gnf_train.hip) from H, n, the net kind, net.fused and the number of
+grevnet_walk (gnf_abi.hip) and the backward walk (gnf_train.hip) from H, n, the net kind, net.fused and the number of
 partial rows the previous kernel left.  Each table below names, from that dispatch code, the route every shape takes.
 
 Reference: oracle/gnf_oracle.py in float64 (loss_and_grads; Fp64Dense.f's last_bn_moments; Fp64Dense.g).  Inputs carry
@@ -131,7 +131,7 @@ LIMIT_CASES = [mp(4, 16384), mp(4, 16385)]
 @PATHS
 @pytest.mark.parametrize("c", LIMIT_CASES, ids=[B.case_id(c) for c in LIMIT_CASES])
 def test_partial_row_limit(c, fused):
-    """D = 4, n = 16384 / 16385: (n + 15) / 16 = 1024 / 1025 against kBnPartRowsMax = 1024 in grevnet_run.
+    """D = 4, n = 16384 / 16385: (n + 15) / 16 = 1024 / 1025 against kBnPartRowsMax = 1024 in grevnet_walk.
     layered: 1024 workgroups of k_coupling_rows fill the moment buffer to its last row and k_bn_apply walks them grouped
     (H = 2: G = 128 thread groups, eight rows each, one round of sixteen slots); at 1025 hs.bn_part stays NULL, k_coupling
     runs and every bijector takes k_bn_stats (bn_blocks: 16 chunks of 1025 rows, the last one 1010).
@@ -165,7 +165,7 @@ def test_tiny_batches(c, fused):
 def test_attention_routes(c, fused):
     """8 heads, kq = v = 10, out 80, no layer norm, sparse edges (ring + random: fewer than 24 per node); D = 2, 34, 64
     (H = 1, 17, 32) x n = 17, 513, 528 (2, 33, 33 sixteen-row tiles).
-    fused, forward: grevnet_run asks fused_bn_on_load_ok once per call.  front_fold_ok wants the layer-0 width and, with
+    fused, forward: grevnet_walk asks fused_bn_on_load_ok once per call.  front_fold_ok wants the layer-0 width and, with
     concat, H itself to be multiples of 16: of the drivers' concat nets only H = 32 folds - there every bijector is
     applied on load (gnf_attn_front_dev.h, bnf block: kFrThreads / H thread groups over the rows k_bn_stats (first
     bijector) or the fused kernel's a.bn_part block (the others) left, ping-ponging between two row buffers) and

@@ -149,6 +149,38 @@ def test_per_graph_argument_validation_without_a_gpu():
     assert f(C.byref(with_off), None, None, 0, 0x1000, 8, 8, 0x1000, 0x1000, 0x1000, big, None) == -1
 
 
+def test_per_graph_refusals_of_the_walk_without_a_gpu():
+    """What the entry point checks only through the walk behind it, after its own checks (node_offsets, sums / graph_out,
+    the workspace): a source with ld_src < D, a bijector without gamma / with epsilon 0, a null x - each with the code and
+    the text the plain flow entry point gives."""
+    lib = _abi.lib()
+    f = lib.gnf_grevnet_per_graph_f32
+    big = 1 << 24
+    csr = _abi.GnfCsr(0x1000, 0x1000, 10, 20, 0x1000, 3)
+    flow = _flow()
+    assert f(C.byref(csr), C.byref(flow), 0x2000, 4, 0x1000, 8, 8, 0x1000, 0x1000, 0x1000, big, None) == -2
+    assert _err() == "gnf_grevnet_from_f32: ld_src=4 < D=8"
+    assert f(C.byref(csr), C.byref(flow), None, 0, None, 8, 8, 0x1000, 0x1000, 0x1000, big, None) == -1
+    assert _err() == "gnf_grevnet_f32: null x/ws"
+    bns = (_abi.GnfBatchNorm * 2)()
+    for q in range(2):
+        bns[q].gamma, bns[q].beta, bns[q].epsilon = 0x1000, 0x1000, 1e-3
+    flow.bns = C.cast(bns, C.POINTER(_abi.GnfBatchNorm))
+    bns[1].gamma = None
+    assert f(C.byref(csr), C.byref(flow), None, 0, 0x1000, 8, 8, 0x1000, 0x1000, 0x1000, big, None) == -1
+    assert _err() == "gnf_grevnet_f32: batch-norm 1 has null gamma / beta"
+    bns[1].gamma, bns[0].epsilon = 0x1000, 0.0
+    assert f(C.byref(csr), C.byref(flow), None, 0, 0x1000, 8, 8, 0x1000, 0x1000, 0x1000, big, None) == -1
+    assert _err() == "gnf_grevnet_f32: batch-norm 0 epsilon must be > 0"
+    # the entry point's own checks come first: without node_offsets the bad bijector is not reached
+    no_off = _abi.GnfCsr(0x1000, 0x1000, 10, 20)
+    assert f(C.byref(no_off), C.byref(flow), None, 0, 0x1000, 8, 8, 0x1000, 0x1000, 0x1000, big, None) == -1
+    assert _err().startswith("gnf_grevnet_per_graph_f32: needs GnfCsr.node_offsets")
+    # ... and so does the empty batch's early return
+    empty = _abi.GnfCsr(0, 0, 0, 0)
+    assert f(C.byref(empty), C.byref(flow), None, 0, None, 8, 8, 0x1000, None, None, 0, None) == 0
+
+
 def test_per_graph_empty_batch_is_a_no_op_success():
     """no nodes and no graphs: GNF_OK after validation, without touching a device"""
     lib = _abi.lib()
