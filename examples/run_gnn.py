@@ -4,7 +4,8 @@ names, kept small) and save it where examples/train_grevnet_with_data.py --make_
     python examples/run_gnn.py --dataset graph_rnn_community_small --num_train_iters 200 --save_path encoder.npz
     python examples/train_grevnet_with_data.py --make_chunks --encoder_params encoder.npz --attn_type avg_then_mlp ...
 
-Batches come from datasets.GraphDataset (random Gaussian node features on the dataset's topologies); every iteration is
+Batches come from datasets.GraphDataset (random Gaussian node features on the dataset's topologies) or, with --device_batches,
+from datasets.DeviceGraphDataset (the dataset stays on the device; a batch and both of its CSRs are one call); every iteration is
 train.EncoderTrainer.step (train-forward, binary_loss, backward, Adam); every --eval_every_n_steps a random test batch goes
 through encoder.evaluate, and the figures run_gnn.py:441-465 logs are printed.  --binary_dist_fn picks the decoder's distance
 function and --tune_sigmoid (with sigmoid_l2) trains its temp and shift from 10 and 1 (run_gnn.py:146-165); the function, with
@@ -82,6 +83,9 @@ def make_parser():
     ap.add_argument("--adam_epsilon", type=float, default=1e-8)
     ap.add_argument("--random_seed", type=int, default=12345)
     ap.add_argument("--save_path", default="encoder.npz")
+    # keep the dataset on the device and assemble every batch, with both of its CSRs, there (datasets.DeviceGraphDataset);
+    # the node features then come from a device generator: same distribution, other numbers than the host route's
+    ap.add_argument("--device_batches", action="store_true")
     return ap
 
 
@@ -121,7 +125,10 @@ def main():
     # the decoder's distance function: with --tune_sigmoid the token whose parameters the trainer moves, under the triplet
     # loss the one its edge-error figures are counted with (pred_adj of loss.py:268)
     dist_fn = trainer.triplet_adj_dist_fn if triplet else trainer.distance_fn
-    dataset = D.GraphDataset(F.dataset, F.node_embedding_dim, F.gaussian_scale, seed=F.random_seed)
+    if F.device_batches:
+        dataset = D.DeviceGraphDataset(F.dataset, F.node_embedding_dim, F.gaussian_scale, seed=F.random_seed, device=dev)
+    else:
+        dataset = D.GraphDataset(F.dataset, F.node_embedding_dim, F.gaussian_scale, seed=F.random_seed)
 
     def log(prefix, it, n_node, res, out_nodes=None):
         per_graph = adj_loss.incorrect_edges_per_graph(res).cpu().numpy()

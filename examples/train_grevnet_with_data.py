@@ -4,7 +4,9 @@ MI355X kernels: node-embedding chunks on disk -> batches of complete graphs (tra
 driver's default GNN (dm_attn: one head, kq = v = 64, C = 64, kq_dim_division; :40-46, 303-310) around its wide relu
 MLPs (latent 2048 x 3 layers, D = 200, 10 coupling layers, batch norm) -> Adam (beta2 0.999, constant lr); then the
 sampling pipeline z ~ N(0, I) -> grevnet(., inverse=False) -> pred_adj(scaled_hacky_sigmoid_l2) -> threshold 0.5
-(flow.generate_graphs: the generated graphs come back as a GraphsTuple with its CSR).
+(flow.generate_graphs: the generated graphs come back as a GraphsTuple with its CSR).  --variable_dataset / --max_nodes are
+the reference's (batches of consecutive graphs holding fewer than max_nodes nodes); --device_batches keeps the chunks'
+embeddings on the device and writes every batch's topology and CSRs there (datasets.complete_batch).
 
 Training the encoder (run_gnn.py) is out of scope, so by default --make_chunks writes embedding chunks whose
 embeddings are synthetic (two well-separated clusters per graph, so that the decoder finds structure); point
@@ -89,6 +91,11 @@ def main():
     ap.add_argument("--keep_generated", default="all", choices=["all", "largest_component", "non_isolated"])
     # uniqueness and novelty of the sampled graphs against the training graphs of --dataset (graph_stats.uniqueness_novelty)
     ap.add_argument("--report_novelty", action="store_true")
+    # train_grevnet_with_data.py:60-61, 471-473: batches of consecutive graphs holding fewer than --max_nodes nodes
+    ap.add_argument("--variable_dataset", action="store_true")
+    ap.add_argument("--max_nodes", type=int, default=1500)
+    # keep the chunks' embeddings on the device and build every batch's topology there (datasets.complete_batch)
+    ap.add_argument("--device_batches", action="store_true")
     F = ap.parse_args()
     random.seed(F.random_seed)
     np.random.seed(F.random_seed)
@@ -118,7 +125,14 @@ def main():
             print(f"{len(paths)} embedding chunks from the encoder in {F.encoder_params} over {F.dataset}")
     # sort_files: the reference consumes the chunks in os.listdir order, which differs from one temporary directory
     # to the next (and with it the whole loss curve); sorted here so that a run of this demo is reproducible
-    data = D.GrevnetDatasetFixed(F.train_data_dir, F.train_batch_size, F.train_epochs, sort_files=True)
+    chunk_device = dev if F.device_batches else None
+    if F.variable_dataset:
+        data = D.GrevnetDatasetVariable(F.train_data_dir, F.max_nodes, sort_files=True, device=chunk_device)
+    else:
+        data = D.GrevnetDatasetFixed(F.train_data_dir, F.train_batch_size, F.train_epochs, sort_files=True, device=chunk_device)
+    # a (node_embeddings, n_node) batch -> GraphsTuple with the complete topology: assembled on the host and uploaded, or
+    # (--device_batches) written on the device next to both of its CSRs
+    to_graph = D.complete_batch if F.device_batches else D.transform_example
 
     make_mlp_fn = partial(gnn.make_mlp_model, F.latent_dim, F.node_embedding_dim / 2, F.num_layers,
                           activation=gnn.relu, l2_regularizer_weight=0.000001, bias_init_stddev=F.bias_init_stddev)
@@ -142,7 +156,7 @@ def main():
     t0 = time.perf_counter()
     for iteration in range(F.num_train_iters + 1):
         z, n_node = data.train_batch()
-        graph = D.transform_example(z, n_node, dev)
+        graph = to_graph(z, n_node, dev)
         v = trainer.step(graph)
         if iteration % F.log_every_n_steps == 0:
             print(f"iteration {iteration:5d} ({time.perf_counter() - t0:6.1f} s): total_loss {float(v['total_loss']):12.3f} "
@@ -153,12 +167,13 @@ def main():
     # held-out likelihood per GRAPH: one more batch, one forward pass (the moments of the batch-norm bijectors are the batch's)
     from gnf_amd.flow import log_prob_per_graph
     z, n_node = data.train_batch()
-    nll = -log_prob_per_graph(grevnet, D.transform_example(z, n_node, dev))["log_prob_xs_per_node"]
+    nll = -log_prob_per_graph(grevnet, to_graph(z, n_node, dev))["log_prob_xs_per_node"]
     print(f"per-node NLL over the {nll.shape[0]} graphs of one batch: min {float(nll.min()):.4f} mean {float(nll.mean()):.4f} "
           f"max {float(nll.max()):.4f}")
     # ---- sampling pipeline (train_grevnet_with_data.py:397-416, 526-540) ---------------------------------------
     n_node = np.asarray(random.sample(list(data.n_node) * F.sample_size, F.sample_size), np.int32)
-    shell = D.transform_example(np.zeros((int(n_node.sum()), F.node_embedding_dim), np.float32), n_node, dev)
+    shape = (int(n_node.sum()), F.node_embedding_dim)
+    shell = to_graph(torch.zeros(shape, device=dev) if F.device_batches else np.zeros(shape, np.float32), n_node, dev)
     # sample -> flow in reverse -> edge lists + CSR, all on the device (--sample_log_prob_xs: log p(x) of each graph from the same pass)
     keep = None if F.keep_generated == "all" else F.keep_generated
     out = generate_graphs(grevnet, shell, log_prob=F.sample_log_prob_xs, keep=keep, **decode_with)

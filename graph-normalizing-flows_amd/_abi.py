@@ -279,6 +279,27 @@ _TRIPLET_SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+
+# include/gnf_batches.h (included by gnf.h, added within ABI v10): a batch and both of its CSRs from graph ids into a device-resident
+# dataset, and the complete topology from node counts.  A table of its own for the same reason.
+GNF_BATCH_MAX_GRAPHS = 1 << 20
+
+
+class GnfBatchStore(C.Structure):    # include/gnf_batches.h
+    _fields_ = [("node_off", C.c_void_p), ("edge_off", C.c_void_p), ("senders", C.c_void_p), ("receivers", C.c_void_p),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("rowptr_t", C.c_void_p), ("col_t", C.c_void_p),
+                ("n_graphs", C.c_int64), ("n_nodes", C.c_int64), ("n_edges", C.c_int64)]
+
+
+_BATCH_SIGNATURES = {
+    "gnf_batch_assemble_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnf_batch_assemble": (C.c_int, [C.POINTER(GnfBatchStore), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_complete_batch_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnf_complete_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -295,6 +316,7 @@ SPECTRA_SYMBOLS = tuple(_SPECTRA_SIGNATURES)
 COMPONENT_SYMBOLS = tuple(_COMPONENT_SIGNATURES)
 HASH_SYMBOLS = tuple(_HASH_SIGNATURES)
 TRIPLET_SYMBOLS = tuple(_TRIPLET_SIGNATURES)
+BATCH_SYMBOLS = tuple(_BATCH_SIGNATURES)
 
 _lib = None
 
@@ -311,7 +333,8 @@ def lib():
         for name, (res, args) in {**_SIGNATURES, **_ORBIT_SIGNATURES, **_ADJ_LOSS_SIGNATURES, **_ENCODER_SIGNATURES,
                                   **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
                                   **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
-                                  **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES, **_TRIPLET_SIGNATURES}.items():
+                                  **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES, **_TRIPLET_SIGNATURES,
+                                  **_BATCH_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

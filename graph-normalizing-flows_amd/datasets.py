@@ -9,6 +9,8 @@
                          per batch (graph_data.py:24-27).
   * fully_connected_edges / senders_receivers - the complete-graph + self-loop topology of
                          grevnet_synthetic_data.py:17-21 and utils.py:164-183 (sender-major order).
+  * DeviceGraphDataset / complete_batch - the same batches assembled on the device (include/gnf_batches.h): the dataset is
+                         uploaded once, a batch and both of its CSRs come out of one gnf_batch_assemble / gnf_complete_batch.
   * synthetic stand-ins - protein / citeseer(ego) datasets are absent from the reference
                          (.MISSING_LARGE_BLOBS); BASELINE.md section 4 fixes the generators used instead.
 """
@@ -123,6 +125,132 @@ class OverfitGraphDataset(GraphDataset):
 
     def test_n_nodes(self):
         return self.train_n_nodes()
+
+
+def _int32_arena(sizes, device, zero=False):
+    """One int32 allocation cut into len(sizes) tensors, each starting on a 256-byte boundary."""
+    import torch
+    starts, total = [], 0
+    for n in sizes:
+        starts.append(total)
+        total += (int(n) + 63) // 64 * 64
+    buf = (torch.zeros if zero else torch.empty)(max(total, 1), dtype=torch.int32, device=device)
+    return [buf[a:a + int(n)] for a, n in zip(starts, sizes)]
+
+
+class DeviceGraphDataset:
+    """GraphDataset with the dataset resident on the device: the edge lists are uploaded once (dataset-wide node ids), the two
+    dataset-wide CSRs are built once by gnf_build_csr (graphs.build_csr_device), and every batch - n_node, n_edge, node
+    offsets, senders, receivers and BOTH CSRs - comes out of one gnf_batch_assemble (include/gnf_batches.h): no host loop over
+    the graphs, no index upload beyond the B graph ids, no sort.  n_node / n_edge stay on the host to size the outputs, so
+    nothing is read back.  Same split rule (train = the first int(0.8 G) graphs) and method names as GraphDataset; the ids are
+    drawn on the host from the same numpy stream as GraphDataset.sample_ids.
+    The node FEATURES are a different stream from GraphDataset's: torch.randn on the device from a torch.Generator seeded with
+    `seed`, times gaussian_scale (GraphDataset draws them with numpy on the host, interleaved with the ids) - same
+    distribution, other numbers.
+    `dataset`: a FILENAME_MAP name or an EdgeListDataset.  There is no CPU path: the device must be a HIP device."""
+
+    def __init__(self, dataset, node_embedding_dim, gaussian_scale=1.0, seed=12345, device=None):
+        import torch
+        from . import _abi
+        from .graphs import GraphsTuple, build_csr_device
+        self.all = EdgeListDataset.load(os.path.join(DATA_DIR, FILENAME_MAP[dataset])) if isinstance(dataset, str) else dataset
+        g = len(self.all)
+        self.train_ids = np.arange(0, int(0.8 * g))
+        self.test_ids = np.arange(int(0.8 * g), g)
+        self.dim = int(node_embedding_dim)
+        self.scale = float(gaussian_scale)
+        self.rng = np.random.default_rng(seed)
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.type != "cuda":
+            raise _abi.GnfError("DeviceGraphDataset needs a HIP device; there is no CPU path (GraphDataset is the host route)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.gen = torch.Generator(device=self.device).manual_seed(int(seed))
+        n_node = self.all.n_node.astype(np.int64)
+        n_edge = self.all.n_edge.astype(np.int64)
+        self._n_node, self._n_edge = n_node, n_edge
+        node_off = np.concatenate([[0], np.cumsum(n_node)])
+        if node_off[-1] >= 2 ** 31 - 1 or self.all.eoff[-1] > 2 ** 31 - 1:
+            raise ValueError("DeviceGraphDataset: the dataset-wide CSR is int32")
+        shift = np.repeat(node_off[:-1], n_edge)
+        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dt)).to(self.device)
+        self._node_off, self._edge_off = up(node_off, np.int32), up(self.all.eoff, np.int64)
+        big = GraphsTuple(nodes=torch.empty(int(node_off[-1]), 0, device=self.device), edges=None,
+                          receivers=up(self.all.receivers + shift, np.int32), senders=up(self.all.senders + shift, np.int32),
+                          globals=None, n_node=up(n_node, np.int32), n_edge=up(n_edge, np.int32))
+        self._big, self._csr, self._csr_t = big, build_csr_device(big), build_csr_device(big, by_sender=True)
+        e_all = int(self.all.eoff[-1])
+        edge_ptr = lambda t: t.data_ptr() if e_all else 0
+        self._store = _abi.GnfBatchStore(self._node_off.data_ptr(), self._edge_off.data_ptr(), edge_ptr(big.senders),
+                                         edge_ptr(big.receivers), self._csr.rowptr.data_ptr(), edge_ptr(self._csr.col),
+                                         self._csr_t.rowptr.data_ptr(), edge_ptr(self._csr_t.col), g, int(node_off[-1]), e_all)
+
+    def sample_ids(self, batch_size, split="train"):
+        ids = self.train_ids if split == "train" else self.test_ids
+        return self.rng.choice(ids, size=batch_size, replace=True)
+
+    def batch_of(self, graph_ids, nodes=None, split=None):
+        """The batch of the graphs `graph_ids` (host integers; repeats allowed, any order) as a GraphsTuple on the device whose
+        CSR cache is seeded for both orientations and whose node-offset cache is seeded: csr_of / node_offsets_of return what
+        this call made, no gnf_build_csr runs afterwards.  Deterministic in graph_ids.  nodes: [sum n_node, D] features to use
+        (a device tensor is used as it is); None draws them from the dataset's device generator.  split = "train" / "test":
+        the ids must lie in that split; None: anywhere in the dataset.  Ids outside raise ValueError."""
+        import ctypes as C
+        import torch
+        from . import _abi
+        from .graphs import Csr, GraphsTuple, seed_csr_cache, seed_node_offsets_cache
+        ids = np.asarray(graph_ids, np.int64).reshape(-1)
+        allowed = {None: (0, len(self.all)), "train": (0, len(self.train_ids)),
+                   "test": (len(self.train_ids), len(self.all))}[split]
+        if len(ids) and (ids.min() < allowed[0] or ids.max() >= allowed[1]):
+            raise ValueError(f"DeviceGraphDataset.batch_of: graph ids outside [{allowed[0]}, {allowed[1]})"
+                             + (f", the {split} split" if split else ""))
+        b, n, e = len(ids), int(self._n_node[ids].sum()), int(self._n_edge[ids].sum())
+        dev = self.device
+        lib = _abi.lib()
+        ws_bytes = lib.gnf_batch_assemble_workspace_bytes(b)
+        live = b > 0 and n > 0     # otherwise the call writes rowptr[0] only: the sizes and offsets are zeros
+        n_node, n_edge, offsets, snd, rcv, rowptr, col, rowptr_t, col_t, ws = _int32_arena(
+            [b, b, b + 1, e, e, n + 1, e, n + 1, e, (ws_bytes + 3) // 4 + 1], dev, zero=not live)
+        gid = torch.as_tensor(ids.astype(np.int32)).to(dev)
+        with torch.cuda.device(dev):
+            _abi.check(lib.gnf_batch_assemble(C.byref(self._store), _abi.ptr(gid), b, n, e, _abi.ptr(n_node), _abi.ptr(n_edge),
+                                              _abi.ptr(offsets), _abi.ptr(snd), _abi.ptr(rcv), _abi.ptr(rowptr), _abi.ptr(col),
+                                              _abi.ptr(rowptr_t), _abi.ptr(col_t), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                       "gnf_batch_assemble")
+        if nodes is None:
+            nodes = torch.randn((n, self.dim), generator=self.gen, device=dev, dtype=torch.float32) * self.scale
+        elif not isinstance(nodes, torch.Tensor):
+            nodes = torch.as_tensor(np.asarray(nodes, np.float32)).to(dev)
+        elif nodes.device != dev:
+            nodes = nodes.to(dev)
+        if nodes.shape[0] != n:
+            raise ValueError(f"DeviceGraphDataset.batch_of: {nodes.shape[0]} feature rows for {n} nodes")
+        graph = GraphsTuple(nodes=nodes, edges=torch.zeros(e, dtype=torch.float32, device=dev), receivers=rcv, senders=snd,
+                            globals=torch.zeros(b, dtype=torch.float32, device=dev), n_node=n_node, n_edge=n_edge)
+        seed_csr_cache(graph, Csr(rowptr, col, n, e))
+        seed_csr_cache(graph, Csr(rowptr_t, col_t, n, e), by_sender=True)
+        seed_node_offsets_cache(graph, offsets)
+        return graph
+
+    def get_next_train_batch(self, batch_size, device=None):
+        return self.batch_of(self.sample_ids(batch_size), split="train")
+
+    def get_next_test_batch(self, batch_size, device=None):
+        return self.batch_of(self.sample_ids(batch_size, "test"), split="test")
+
+    def get_random_test_batch(self, batch_size, device=None):
+        return self.get_next_test_batch(batch_size)
+
+    def full_n_nodes(self):
+        return [int(n) for n in self.all.n_node]
+
+    def train_n_nodes(self):
+        return [int(self.all.n_node[i]) for i in self.train_ids]
+
+    def test_n_nodes(self):
+        return [int(self.all.n_node[i]) for i in self.test_ids]
 
 
 def fully_connected_edges(n):
@@ -265,10 +393,14 @@ class _ChunkBatches:
     (train_grevnet_with_data.py:150-157, 188-195): an empty or unreadable directory, or a graph that can never fit under
     max_nodes, fails there and not in the middle of an epoch; `file_ind` exists from the start.
     One deliberate difference: the short LAST batch of the LAST file is handed out (the variable-size reader of the
-    reference loses it - it raises IndexError while opening the file after the last one, before returning the batch)."""
+    reference loses it - it raises IndexError while opening the file after the last one, before returning the batch).
+    device (not in the reference; None = the behaviour above): a chunk's embeddings are uploaded once, as float32, when the chunk
+    is opened, and a batch's embeddings are a row-range VIEW of that device tensor (the ranges are consecutive rows: no copy,
+    nothing crosses the bus per batch); n_node stays a host array."""
 
-    def __init__(self, directory, files, plan):
+    def __init__(self, directory, files, plan, device=None):
         import os
+        self.device = device
         self._paths = [os.path.join(directory, f) for f in files]
         self.files = list(files)
         self._plan = plan
@@ -280,6 +412,9 @@ class _ChunkBatches:
 
     def _cut(self, path):
         emb, n_node = _read_embedding_chunk(path)
+        if self.device is not None:
+            import torch
+            emb = torch.as_tensor(np.ascontiguousarray(emb, np.float32)).to(self.device)
         row_end = np.concatenate([[0], np.cumsum(n_node)])
         self.n_node = n_node      # the chunk just opened, like the reference readers' self.n_node = d[1] (:157, 172)
         return emb, n_node, row_end, self._plan(n_node)
@@ -290,7 +425,7 @@ class _ChunkBatches:
             emb, n_node, row_end, ranges = self._first if ind == 0 else self._cut(path)
             self._first = None
             for lo, hi in ranges:
-                yield emb[row_end[lo]:row_end[hi]], n_node[lo:hi]
+                yield emb[int(row_end[lo]):int(row_end[hi])], n_node[lo:hi]
 
     def train_batch(self):
         try:
@@ -310,19 +445,19 @@ class GrevnetDatasetFixed(_ChunkBatches):
     """train_grevnet_with_data.py:145-180: `train_batch_size` graphs per batch, chunk tails dropped;
     `train_epochs` is FLAGS.train_epochs (the file list is repeated that many times)."""
 
-    def __init__(self, train_data_dir, train_batch_size, train_epochs=1, sort_files=False):
+    def __init__(self, train_data_dir, train_batch_size, train_epochs=1, sort_files=False, device=None):
         self.train_batch_size = int(train_batch_size)
         super().__init__(train_data_dir, _chunk_files(train_data_dir, sort_files) * int(train_epochs),
-                         lambda n_node: plan_fixed_batches(n_node, self.train_batch_size))
+                         lambda n_node: plan_fixed_batches(n_node, self.train_batch_size), device=device)
 
 
 class GrevnetDatasetVariable(_ChunkBatches):
     """train_grevnet_with_data.py:183-234: consecutive graphs up to (not reaching) max_nodes per batch."""
 
-    def __init__(self, train_data_dir, max_nodes, sort_files=False):
+    def __init__(self, train_data_dir, max_nodes, sort_files=False, device=None):
         self.max_nodes = int(max_nodes)
         super().__init__(train_data_dir, _chunk_files(train_data_dir, sort_files),
-                         lambda n_node: plan_variable_batches(n_node, self.max_nodes))
+                         lambda n_node: plan_variable_batches(n_node, self.max_nodes), device=device)
 
 
 def transform_example(node_embeddings, n_node, device=None):
@@ -338,3 +473,48 @@ def transform_example(node_embeddings, n_node, device=None):
                     globals=torch.zeros(len(n_node), dtype=torch.float32),
                     n_node=torch.as_tensor(n_node), n_edge=torch.as_tensor(n_edge.astype(np.int32)))
     return g.to(device) if device is not None else g
+
+
+def complete_batch(node_embeddings, n_node, device):
+    """transform_example's GraphsTuple through gnf_complete_batch (include/gnf_batches.h): node offsets, n_edge = n_node**2,
+    senders and receivers in senders_receivers' sender-major order and the row pointers are written by one launch from the B
+    node counts - nothing of size sum(n_node**2) is built on the host or uploaded, and no gnf_build_csr runs: for this topology
+    the by-receiver col, the by-sender col and `receivers` are one array and the two rowptrs are equal, so both CSR cache entries
+    are seeded with col = the receivers tensor itself (and the node-offset cache with the offsets of the same launch).
+    node_embeddings: [sum(n_node), D]; a tensor already on `device` is used as it is.  n_node: host integers."""
+    import torch
+    from . import _abi
+    from .graphs import Csr, GraphsTuple, seed_csr_cache, seed_node_offsets_cache
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _abi.GnfError("complete_batch needs a HIP device; there is no CPU path (transform_example is the host route)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    counts = np.asarray(n_node, np.int64).reshape(-1)
+    if len(counts) and counts.min() < 0:
+        raise ValueError("complete_batch: negative n_node")
+    b, n, e = len(counts), int(counts.sum()), int((counts * counts).sum())
+    if isinstance(node_embeddings, torch.Tensor):
+        nodes = node_embeddings if node_embeddings.device == dev else node_embeddings.to(dev)
+    else:
+        nodes = torch.as_tensor(np.asarray(node_embeddings, np.float32)).to(dev)
+    if nodes.shape[0] != n:
+        raise ValueError(f"complete_batch: {nodes.shape[0]} embedding rows for {n} nodes")
+    lib = _abi.lib()
+    ws_bytes = lib.gnf_complete_batch_workspace_bytes(b)
+    live = b > 0 and n > 0
+    fits = e <= 2 ** 31 - 1        # beyond: the call refuses (GNF_ESHAPE) before it touches anything
+    offsets, n_edge, rowptr, snd, rcv, ws = _int32_arena([b + 1, b, n + 1, e if fits else 0, e if fits else 0,
+                                                          (ws_bytes + 3) // 4 + 1], dev, zero=not live)
+    n_dev = torch.as_tensor(counts.astype(np.int32)).to(dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_complete_batch(_abi.ptr(n_dev), b, n, e, _abi.ptr(offsets), _abi.ptr(n_edge), _abi.ptr(rowptr),
+                                          _abi.ptr(snd), _abi.ptr(rcv), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)),
+                   "gnf_complete_batch")
+    graph = GraphsTuple(nodes=nodes, edges=torch.zeros(e, dtype=torch.float32, device=dev), receivers=rcv, senders=snd,
+                        globals=torch.zeros(b, dtype=torch.float32, device=dev), n_node=n_dev, n_edge=n_edge)
+    csr = Csr(rowptr, rcv, n, e)
+    seed_csr_cache(graph, csr)
+    seed_csr_cache(graph, csr, by_sender=True)
+    seed_node_offsets_cache(graph, offsets)
+    return graph

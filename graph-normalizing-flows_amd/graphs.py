@@ -219,6 +219,19 @@ def node_offsets_of(graph):
     return off
 
 
+def seed_node_offsets_cache(graph, offsets):
+    """Store node offsets that already exist (datasets.DeviceGraphDataset.batch_of and datasets.complete_batch get them from
+    the launch that made the batch) under the key node_offsets_of(graph) looks up.  The caller vouches that `offsets` IS the
+    int32 [n_graphs + 1] exclusive prefix sum of graph.n_node on the nodes' device.  Returns offsets."""
+    nn = graph.n_node
+    key = (nn.data_ptr(), int(nn.shape[0]), str(nn.device), str(graph.nodes.device))
+    _OFFSETS_CACHE[key] = (offsets, nn)
+    _OFFSETS_CACHE.move_to_end(key)
+    while len(_OFFSETS_CACHE) > _OFFSETS_CACHE_MAX:
+        _OFFSETS_CACHE.popitem(last=False)
+    return offsets
+
+
 def csr_desc(graph, csr, node_offsets=False):
     """The GnfCsr handed to the library for `graph`: csr.desc itself, or (node_offsets=True: a net of the call has
     graph-scope attention) a copy of it with node_offsets / n_graphs filled in; the copy holds the offsets tensor."""

@@ -528,6 +528,9 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 #include "gnf_graph_hashes.h"
 /* Added within ABI v10: the sampled triplet loss of embeddings against a true batch and its gradient (gnf_triplet_loss.h) - likewise. */
 #include "gnf_triplet_loss.h"
+/* Added within ABI v10: batches and both of their CSRs assembled on the device from a resident dataset, and the complete
+ * topology from node counts alone (gnf_batches.h) - likewise. */
+#include "gnf_batches.h"
 
 #ifdef __cplusplus
 }
