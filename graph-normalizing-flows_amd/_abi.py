@@ -300,6 +300,14 @@ _BATCH_SIGNATURES = {
     "gnf_complete_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+
+# include/gnf_dw_plan.h (included by gnf.h, added within ABI v10): the backward walk's weight-gradient launch plan as a flat
+# int64 record - a debugging and test view with no stability promise.  A table of its own for the same reason.
+GNF_DW_ROUTE_STREAMS, GNF_DW_ROUTE_MERGED, GNF_DW_ROUTE_GENERIC = 0, 1, 2
+_DW_PLAN_SIGNATURES = {
+    "gnf_dw_plan_describe": (C.c_int64, [C.c_int64, C.c_int32, C.POINTER(GnfMlp), C.c_int32, C.c_int64, C.c_size_t, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int64]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -317,6 +325,7 @@ COMPONENT_SYMBOLS = tuple(_COMPONENT_SIGNATURES)
 HASH_SYMBOLS = tuple(_HASH_SIGNATURES)
 TRIPLET_SYMBOLS = tuple(_TRIPLET_SIGNATURES)
 BATCH_SYMBOLS = tuple(_BATCH_SIGNATURES)
+DW_PLAN_SYMBOLS = tuple(_DW_PLAN_SIGNATURES)
 
 _lib = None
 
@@ -334,7 +343,7 @@ def lib():
                                   **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
                                   **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
                                   **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES, **_TRIPLET_SIGNATURES,
-                                  **_BATCH_SIGNATURES}.items():
+                                  **_BATCH_SIGNATURES, **_DW_PLAN_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -18,6 +18,7 @@
 // is ever made.  Also here: the multi-tensor weight re-pack after an optimiser step, Adam
 // (tf.train.AdamOptimizer, run_grevnet.py:352-356) and the two gradient clippers (run_grevnet.py:363-373).
 #include "gnf_common.h"
+#include "gnf_dw_plan.h"   // the dW launch planner (host-only) and the tile constants it shares with the kernels below
 #include "gnf_fused_bwd_dev.h"
 
 #include <stdio.h>
@@ -29,9 +30,7 @@ namespace gnf {
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-
-static constexpr int TGM = 128, TGN = 64, TGK = 32;
-static constexpr int kGemmThreads = 512;
+static constexpr int kGemmThreads = 512;   // (the tile: TGM x TGN x TGK, gnf_dw_plan.h)
 
 // operand storage: KC = rows indexed by the GEMM's m (or n), k contiguous;  MC = rows indexed by k
 enum { OPND_KC = 0, OPND_MC = 1 };
@@ -309,7 +308,7 @@ static bool gemm_buf_ok(int ak, int bk, int64_t a_rows, int64_t lda, int64_t b_r
 
 // Grouped split-K launch: up to kMaxGroup GEMMs of different M x N (the dW of every layer of both nets of
 // a half-step) over the same K = node axis, in one grid.  blockIdx.z = job * chunks + chunk.
-static constexpr int kMaxGroup = 2 * (GNF_MAX_LAYERS + 4);  // per net: K layers (+ Wq, Wk, Wv, Wo of an attention block)
+static_assert(kMaxGroup == 2 * (GNF_MAX_LAYERS + 4), "per net: K layers (+ Wq, Wk, Wv, Wo of an attention block)");
 struct GroupedGemm {
     GemmJob job[kMaxGroup];
     int64_t lda[kMaxGroup], ldb[kMaxGroup];
@@ -350,8 +349,7 @@ __global__ __launch_bounds__(kGemmThreads) void k_gemm_dw_grouped(const GroupedG
 // ONE workgroup per CU: 128 x 128 output tile, 4 waves each owning 64 x 64 (4 x 4 MFMA tiles, 64 accumulator
 // registers), BK = 32 = 128 MFMAs per wave per step (~1.7 us) behind which the next step's eight float4 loads per
 // thread are in flight; two LDS stages, one barrier per step.  With few, long workgroups the launch can be sized to
-// the CUs the fused backward kernel leaves idle (see launch_weight_grads).
-static constexpr int WGM = 128, WGN = 128, WGK = 32;
+// the CUs the fused backward kernel leaves idle (see launch_weight_grads).  (WGM x WGN x WGK: gnf_dw_plan.h)
 static constexpr int kWideThreads = 512;  // 8 waves: two per SIMD, each fills the other's issue gaps
 static constexpr int kWideQ = WGK * 32 / kWideThreads;  // float4 per thread and operand tile
 static constexpr int kWidePieces = 4 * kWideQ;
@@ -390,9 +388,7 @@ struct WideGemmT {
     int32_t light_on_tiles;
 };
 using WideGemm = WideGemmT<kMaxGroup>;
-// what fits next to the backward kernel's arguments in one launch (4 KB of kernel arguments)
-static constexpr int kMergedGroup = 20;  // message-passing nets of up to 8 layers (16 jobs), attention nets of up to 6 (2 x (6 + 4))
-using WideGemmS = WideGemmT<kMergedGroup>;
+using WideGemmS = WideGemmT<kMergedGroup>;  // what fits next to the backward kernel's arguments in one launch
 
 // One BK = 32 step of a wave's MTW x NTW block of MFMA tiles.  A wave is alone on its SIMD here and issues in order,
 // so everything that is not an MFMA has to sit BETWEEN MFMAs to be free (an instruction placed behind a run of MFMAs
@@ -405,16 +401,6 @@ using WideGemmS = WideGemmT<kMergedGroup>;
 // (No software hazard here: an accumulator is touched again 16 MFMAs later, and read out only after the last barrier.)
 __device__ __forceinline__ void mfma_inplace(f32x4_t& c, float a, float b) {
     asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-
-struct WideLayout {
-    bool along_n, along_m;  // 1 x 8 waves of 32 x 16 along N / 8 x 1 of 16 x 32 along M / (neither) 4 x 2 waves of 32 x 64
-};
-__host__ __device__ inline WideLayout wide_layout(int m_left, int n_left) {  // extents of the tile inside the matrix
-    WideLayout l;
-    l.along_n = m_left <= 32;
-    l.along_m = !l.along_n && n_left <= 32;
-    return l;
 }
 
 template <int MTW, int NTW, typename Piece>
@@ -1012,7 +998,7 @@ __global__ __launch_bounds__(256) void k_aggregate_bwd(const int32_t* __restrict
 // ---- workspace ---------------------------------------------------------------------------------
 struct BwdPlan {
     int K, in0, lmax, H, chunks;
-    int slab_chunks;  // slabs there is room for per job (>= chunks: thin jobs of a merged walk are cut finer, see plan_weight_grads)
+    int slab_chunks;  // slabs there is room for per job (chunks, kchunk, slab_chunks: dw_slab_room, gnf_dw_plan.h)
     int64_t n, kchunk;
     int64_t wsum, osum;  // floats of dW / db slabs per chunk, both nets, attention weights included
     // attention geometry (0 when the nets are message-passing GNNs)
@@ -1040,8 +1026,6 @@ static inline size_t al64(size_t v) { return (v + 63) / 64 * 64; }  // keep ever
 // per half-step, i.e. no wait on the main stream at all, changed nothing in the step time (2.41 vs 2.38 ms), and a
 // captured-graph replay of the whole step is 2 % faster than eager launches: the gaps belong to the cross-queue
 // dependency itself, not to the host or to the wait packets.  The generic code below still takes any set count.)
-static constexpr int kTileLightChunks = 24;  // most pieces a thin job is cut into for the tile workgroups of a merged launch
-static constexpr int kMergedMaxTiles = 192;  // backward tiles of a launch that still leaves CUs for the dW GEMMs
 static constexpr int kLnBwdRows = 64;  // rows per workgroup of the layer-norm backward kernel
 static constexpr int kBwdMaxSets = 64;
 static constexpr int kBwdSetsDefault = 3;
@@ -1070,36 +1054,8 @@ static BwdPlan plan_backward(int64_t n, int32_t D, const GnfMlp* net, int n_sets
     p.wsum = 2 * wsum;
     p.osum = 2 * osum;
     p.lmax = lmax;
-    // split of the node axis for dW: every weight gradient of the half-step goes out in ONE grouped launch, so a
-    // few chunks already fill the chip; fewer chunks = fewer slabs to write and reduce
-    // (measured on the config-2 batch: chunks of 64 / 128 / 256 / 512 nodes give 3.11 / 2.94 / 2.94 / 2.99 ms per step)
-    int64_t chunks = (n + 255) / 256;
-    if (chunks > 64) chunks = 64;
-    {   // ... but no more than it takes to put ~4 workgroups on every CU: wide layers have the tiles already (2048-wide:
-        // 3072 tiles per chunk - a second chunk only added 200 MB of slab traffic per half-step)
-        int64_t tiles = 0;
-        for (int j = 0; j < p.K; ++j)
-            tiles += (int64_t)((net->dims[j] + TGM - 1) / TGM) * ((net->dims[j + 1] + TGN - 1) / TGN);
-        tiles *= 2;
-        int64_t enough = (1024 + tiles - 1) / (tiles > 0 ? tiles : 1);
-        // ... except that nets with wide hidden layers AND thin first / last layers need slab room for the thin layers' tiles:
-        // the wide kernel gives every CU one workgroup that takes whole hidden-layer tiles by stride (one chunk each: the slab
-        // is the gradient) and cuts the thin layers' tiles along the node axis so that they ride behind in equal pieces.  With
-        // ONE chunk planned they could not be cut: on the data driver's nets 64 of the 256 workgroups carried a third
-        // full-length tile (time stamps, round 6: 1 216 k cycles against 813 k for the other 192)
-        if (lmax >= 512 && enough < 4) enough = 4;
-        if (chunks > enough) chunks = enough;
-    }
-    if (chunks < 1) chunks = 1;
-    int64_t kchunk = (n + chunks - 1) / chunks;
-    kchunk = (kchunk + TGK - 1) / TGK * TGK;
-    if (kchunk < TGK) kchunk = TGK;
-    chunks = n > 0 ? (n + kchunk - 1) / kchunk : 1;
-    p.chunks = (int)chunks;
-    p.kchunk = kchunk;
-    // merged walk (few tiles, nets the fused kernels hold): room for one short unit of the thin jobs per tile workgroup
-    p.slab_chunks = p.chunks;
-    if ((n + 15) / 16 <= kMergedMaxTiles && lmax < 512 && p.slab_chunks < kTileLightChunks) p.slab_chunks = kTileLightChunks;
+    const DwSlabRoom room = dw_slab_room(n, p.K, net->dims, lmax);   // the dW launches' split of the node axis and its slabs
+    p.chunks = room.chunks, p.kchunk = room.kchunk, p.slab_chunks = room.slab_chunks;
     const size_t nk1 = (size_t)(p.K > 1 ? p.K - 1 : 0);
     size_t off = 0;
     p.g = off, off += al64((size_t)n * D);
@@ -1251,357 +1207,131 @@ struct WGJob {
     float* gb;
 };
 
-// How the dW launch is shaped.  max_units == 0: the 128 x 64 grouped kernel over the plan's chunks (many short
-// workgroups that share CUs with whatever else runs).  max_units > 0: the wide kernel in at most that many
-// workgroups, each asking for `lds` bytes of LDS - unless the cut this allows would take longer than `budget_us`,
-// in which case the grouped kernel runs after all.
-struct DwPolicy {
-    int max_units;
-    size_t lds;
-    double budget_us;
-    bool big_tiles_only = false;  // only the jobs with the most tiles count as "costliest" (see dw_policy, generic backward)
-    int tile_wgs = 0;  // > 0: the launch that carries this plan has that many backward-tile workgroups with time to spare
-                       // (merged walk with the MLP-row stash): a stream-K plan hands them the thin jobs (WideGemmT.light_on_tiles)
-};
-
-// The fused backward kernel of the NEXT half-step runs beside this half-step's dW GEMMs (one 16-node tile per
-// workgroup, one workgroup per CU by its LDS footprint).  While it leaves CUs idle (config-2 batch: 170 tiles on 256
-// CUs) the dW launch is sized to exactly those: long, equal workgroups, no more of them than there are idle CUs on
-// every XCD (workgroups are dealt round-robin to the 8 XCDs of 32 CUs), with enough LDS padding that none fits beside
-// a backward workgroup.  The backward kernel (the critical path) then runs undisturbed and the weight gradients
-// finish inside its shadow.  One workgroup too many is costly - a backward workgroup that finds no CU waits for a whole
-// dW workgroup - hence the strict cap.  Without enough idle CUs to finish in the backward kernel's time, the grouped
-// kernel's many short workgroups spread the contention evenly instead.
+// How the dW launch is shaped: DwPolicy, one constructor per route (gnf_dw_plan.h).  The three shape-forcing options are
+// read HERE and nowhere else.
+static DwOptions dw_options() {
+    return DwOptions{opt(OPT_DW_GROUPED),      // dw_grouped
+                     opt(OPT_DW_WIDE_UNITS),   // dw_wide_units
+                     opt(OPT_DW_THIN_ON_DW)};  // dw_thin_on_dw
+}
+// the stream-forking route: around the fused backward launch of the next half-step where there is one (bwd_tiles > 0)
 static DwPolicy dw_policy(const GnfMlp* net, int64_t bwd_tiles, size_t bwd_lds) {
-    const int64_t env_g = opt(OPT_DW_GROUPED), env_u = opt(OPT_DW_WIDE_UNITS);  // shape forcing for the parity tests (gnf_set_option)
-    DwPolicy pol{0, kWideLdsMin, 0.0};
-    if (env_g) return pol;
-    if (bwd_tiles > 0 && bwd_tiles <= 192 && bwd_lds > 80 * 1024) {
-        // workgroups are dealt round-robin to 32 shader engines of 8 CUs: no engine may get more exclusive workgroups
-        // (backward + dW) than it has CUs, or a backward workgroup waits for a whole dW workgroup (measured: the
-        // backward kernel then takes 150 instead of 84 us every other half-step)
-        pol.max_units = 32 * (8 - (int)((bwd_tiles + 31) / 32));
-        const size_t excl = (size_t)160 * 1024 - bwd_lds + 1024;
-        if (excl > pol.lds) pol.lds = excl;
-        // what the backward kernel takes: recompute + dP chain = 2 x 2 nets x 16 rows x sum(d_j d_j+1) MACs per tile at
-        // ~60 % of a CU's fp32 matrix rate (measured: 84 us at 5 x 256-wide layers)
-        double macs = 0.0;
-        for (int j = 0; j < net->num_layers; ++j) macs += (double)net->dims[j] * net->dims[j + 1];
-        // the alternative (grouped kernel sharing every CU) stretches the backward kernel by ~1.3 x
-        pol.budget_us = 1.4 * (2.0 * 2.0 * 16.0 * macs * 2.0) / (614e9 * 0.6) * 1e6 + 10.0;
-    }
-    if (bwd_tiles == 0) {
-        // generic backward (nets too wide for the fused kernels: the data driver's 2048 x 3 MLPs): a hidden layer's dW is
-        // hundreds of full 128 x 128 tiles over the whole node axis - the wide kernel with ONE chunk per tile (the slab IS
-        // the gradient: no reduce pass) where three workgroups per CU hold them all, against the grouped kernel's 128 x 64
-        // tiles + slabs + reduce: wide_fc_train 34.2 -> 29.8 ms per step (measured with dw_wide_units = 640 .. 4096)
-        // ONE workgroup per CU, each taking its share of the hidden layers' 2 x 256 full tiles by stride (one chunk per tile:
-        // the slab is the gradient) with the thin first / last layers' tiles cut into pieces that ride behind through slabs of
-        // their own.  The count hardly matters (measured 128 .. 512 workgroups: 29.56 .. 29.90 ms per wide_fc_train step,
-        // best at one per CU): the step is bound by the matrix cores under these kernels' efficiencies, and one workgroup per
-        // CU leaves the other LDS slot of every CU to the main stream's kernels
-        if (hidden_max(net) >= 512) pol.max_units = big_cu_count(), pol.budget_us = 1e30, pol.big_tiles_only = true;
-    }
-    if (env_u > 0) pol.max_units = (int)env_u, pol.budget_us = 1e30;
-    return pol;
+    return bwd_tiles > 0 ? dw_policy_streams(dw_options(), net->num_layers, net->dims, bwd_tiles, bwd_lds, kWideLdsMin)
+                         : dw_policy_generic(dw_options(), hidden_max(net), big_cu_count(), kWideLdsMin);
 }
 
 // Everything launch_weight_grads decides, kept so that the GEMM launch and the reduce launch can be issued apart (or
-// ride in another launch: the merged backward + dW kernel below).
+// ride in another launch: the merged backward + dW kernel below): the cut, and the jobs' pointers in list order.
 struct DwLaunch {
-    bool wide, buf, direct;
-    WideGemm wg;
-    GroupedGemm gg;
+    DwCut cut;
+    GroupedGemm gg;  // (the wide kernel's arguments are made of these at launch, in the cut's order: fill_wide)
     GroupedReduce gr;
-    int units, nj;
+    int nj;
     size_t lds;
-    int64_t maxred;
-    int gx, gy, nz, groups, rpg;  // grouped kernel geometry
-    unsigned blocks;
-    bool gbuf;
+    bool buf;  // the operands may go through the buffer path of the kernel the cut chose
 };
 
-// slab_set: which of the plan's slab sets (BwdPlan.slab_sets) the GEMM writes and the reduce reads
+// Three steps: lay out the jobs' slabs, cut (dw_cut: the pure decision, gnf_dw_plan.h), copy the cut into the grouped
+// kernel's and the reduce's arguments - plus what depends on the pointers: the in-place redirect, the reduce's index space
+// and whether the operands may go through the buffer path.  slab_set: which of the plan's slab sets (BwdPlan.slab_sets) the
+// GEMM writes and the reduce reads
 static int plan_weight_grads(const BwdPlan& p, const DwPolicy& pol, const WGJob* jobs, int nj, bool accumulate,
                              float* ws, int slab_set, DwLaunch* L) {
     GroupedGemm& gg = L->gg;
     GroupedReduce& gr = L->gr;
     memset(&gg, 0, sizeof(gg));
     memset(&gr, 0, sizeof(gr));
-    L->nj = nj;
-    L->lds = pol.lds;
-    L->direct = false;
     ws += (size_t)slab_set * p.slab_stride;
-    int maxM = 1, maxN = 1;
-    int64_t maxred = 1;
+    bool has_bias[kMaxGroup];
     int64_t woff = 0, boff = 0;
     for (int e = 0; e < nj; ++e) {
         const WGJob& j = jobs[e];
         float* wsl = ws + p.wslab + (size_t)p.slab_chunks * woff;
         float* bsl = j.gb ? ws + p.bslab + (size_t)p.slab_chunks * boff : nullptr;
         gg.job[e] = GemmJob{j.A, j.B, wsl, nullptr, bsl};
-        gg.lda[e] = j.lda;
-        gg.ldb[e] = j.ldb;
-        gg.M[e] = j.M;
-        gg.N[e] = j.N;
+        gg.lda[e] = j.lda, gg.ldb[e] = j.ldb;
+        gg.M[e] = j.M, gg.N[e] = j.N;
         gr.job[e] = ReduceJob{wsl, bsl, j.gw, j.gb};
         gr.nw[e] = (int64_t)j.M * j.N;
         gr.nb[e] = j.gb ? j.N : 0;
-        maxM = maxM > j.M ? maxM : j.M;
-        maxN = maxN > j.N ? maxN : j.N;
-        const int64_t red = (int64_t)j.M * j.N + (j.gb ? j.N : 0);
-        maxred = maxred > red ? maxred : red;
+        has_bias[e] = j.gb != nullptr;
         woff += (int64_t)j.M * j.N;
         if (j.gb) boff += j.N;
     }
-    gg.K = p.n;
-    gg.kchunk = p.kchunk;
-    gg.chunks = p.chunks;
-    for (int e = 0; e < nj; ++e) gr.chunks[e] = p.chunks;
+    const DwCut& c = L->cut = dw_cut(p.n, DwSlabRoom{p.chunks, p.kchunk, p.slab_chunks}, pol, nj, gg.M, gg.N, has_bias, accumulate);
+    L->nj = nj, L->lds = pol.lds, L->buf = true;
+    gg.K = p.n, gg.kchunk = p.kchunk, gg.chunks = p.chunks;
     gr.accumulate = accumulate ? 1 : 0;
-    // ---- wide kernel: cut every job along the node axis so that the workgroups carry about equal MFMA work --------
-    bool wide = pol.max_units > 0 && p.n > 0;
-    WideGemm& wg = L->wg;
-    int units = 0;
-    int64_t max_kchunk = WGK;
-    if (wide) {
-        memset(&wg, 0, sizeof(wg));
-        // MFMA tiles per k-slice of the busiest wave of a job's busiest tile (what one step of such a workgroup costs;
-        // 16 for a full 128 x 128 tile), rounded the way the kernel rounds (1 / 2 / 4 MFMA tiles per side)
-        auto side = [](int len) {
-            const int t16 = (len + 15) / 16;
-            return t16 > 2 ? 4 : t16;
-        };
-        int cost[kMaxGroup], tiles_of[kMaxGroup], order[kMaxGroup], cj[kMaxGroup];
-        for (int e = 0; e < nj; ++e) {
-            const int mt_ = jobs[e].M < WGM ? jobs[e].M : WGM, nt_ = jobs[e].N < WGN ? jobs[e].N : WGN;
-            const WideLayout l = wide_layout(mt_, nt_);
-            const int wext_m = l.along_m ? 16 : 32, wext_n = l.along_n ? 16 : (l.along_m ? 32 : 64);
-            cost[e] = 2 * side(mt_ < wext_m ? mt_ : wext_m) * side(nt_ < wext_n ? nt_ : wext_n);  // two waves per SIMD
-            tiles_of[e] = ((jobs[e].M + WGM - 1) / WGM) * ((jobs[e].N + WGN - 1) / WGN);
-            order[e] = e;
+    for (int q = 0; q < nj; ++q) {
+        const int e = c.order[q];
+        gr.chunks[e] = c.chunks[q];
+        if (c.in_place[q]) {  // the job's "slab" IS the gradient (a wide job so written leaves the reduce nothing to do)
+            gg.job[e].C = jobs[e].gw, gg.job[e].aux_out = jobs[e].gb;
+            if (c.wide) gr.nw[e] = 0, gr.nb[e] = 0;
         }
-        for (int a = 1; a < nj; ++a) {  // insertion sort, costliest tiles first (stable): they are dispatched first
-            const int v = order[a];
-            int b = a - 1;
-            while (b >= 0 && cost[order[b]] < cost[v]) order[b + 1] = order[b], --b;
-            order[b + 1] = v;
-        }
-        // The costliest jobs (the hidden-layer matrices) give the launch its grid: the smallest per-workgroup work T (in
-        // rows of a full tile) whose cut of THEM fits max_units; candidates n / k.  Cheaper jobs (thin first / last
-        // layers, attention projections) are cut into about as many units as there are workgroups and ride behind.
-        if (pol.big_tiles_only) {  // a job with under a quarter of the largest job's tiles is not among the costliest
-            int tmax = 1;
-            for (int e = 0; e < nj; ++e) tmax = tmax > tiles_of[e] ? tmax : tiles_of[e];
-            for (int e = 0; e < nj; ++e)
-                if (4 * tiles_of[e] < tmax && cost[e] > 1) cost[e] -= 1;
-            for (int a = 1; a < nj; ++a) {  // (re-sort: costliest first, stable)
-                const int v = order[a];
-                int b = a - 1;
-                while (b >= 0 && cost[order[b]] < cost[v]) order[b + 1] = order[b], --b;
-                order[b + 1] = v;
-            }
-        }
-        const int cmax = nj > 0 ? cost[order[0]] : 16;
-        int heavy_tiles = 0, light_tiles = 0;
-        for (int e = 0; e < nj; ++e) (cost[e] == cmax ? heavy_tiles : light_tiles) += tiles_of[e];
-        int c_heavy = 0;
-        for (int k = p.chunks; k >= 1; --k)
-            if ((int64_t)k * heavy_tiles <= pol.max_units) { c_heavy = k; break; }
-        // (generic backward of wide nets: more whole tiles than workgroups is fine - one chunk each, taken by stride)
-        if (c_heavy == 0 && pol.big_tiles_only && heavy_tiles > 0) c_heavy = 1;
-        int grid = 0, c_light = 1;
-        double est_us = 1e30;
-        if (c_heavy > 0) {
-            int64_t kc = (p.n + c_heavy - 1) / c_heavy;
-            kc = (kc + WGK - 1) / WGK * WGK;
-            c_heavy = (int)((p.n + kc - 1) / kc);
-            grid = c_heavy * heavy_tiles;
-            if (grid > pol.max_units) grid = pol.max_units;
-            bool light_own = false;  // room for the cheap units as workgroups of their own?
-            if (light_tiles > 0) {
-                light_own = grid + light_tiles <= pol.max_units;
-                c_light = light_own ? (pol.max_units - grid) / light_tiles : grid / light_tiles;
-                c_light = c_light < 1 ? 1 : (c_light > p.chunks ? p.chunks : c_light);
-            }
-            // a step of a full tile (32 rows) takes ~2.1 us at one workgroup per CU (measured); + launch, prologue and
-            // epilogue of every unit
-            const double heavy_us = (double)cmax / 16.0 * (double)kc / 32.0 * 2.1 + 6.0;
-            double light_us = 0.0;
-            for (int e = 0; e < nj; ++e)
-                if (cost[e] != cmax)
-                    light_us += tiles_of[e] * c_light * ((double)cost[e] / 16.0 * (double)p.n / c_light / 32.0 * 2.1 + 4.0);
-            est_us = light_own ? heavy_us : heavy_us + light_us / grid;
-            if (light_own) grid += light_tiles * c_light;  // an upper bound; the exact count follows below
-        }
-        // ---- stream-K for the costliest jobs: equal runs of k-steps across tile boundaries instead of whole chunks ----
-        // (24 tiles on 64 workgroups is 2.67 workgroups per tile: cut in whole chunks that is 2 per tile = 48 busy
-        // workgroups with 43 steps each; as one axis of 24 x 85 steps it is 64 workgroups with 32 steps each)
-        const int sk_steps = (int)((p.n + WGK - 1) / WGK);
-        int sk_q = 0, sk_grid = 0, sk_cmax = 0;
-        bool sk_on_tiles = false;
-        if (c_heavy > 0 && heavy_tiles > 0 && heavy_tiles <= pol.max_units && sk_steps >= 8) {
-            sk_grid = pol.max_units;
-            const int64_t total_steps = (int64_t)heavy_tiles * sk_steps;
-            sk_q = (int)((total_steps + sk_grid - 1) / sk_grid);
-            if (sk_q < 4) sk_q = 4;
-            sk_grid = (int)((total_steps + sk_q - 1) / sk_q);
-            for (int t = 0; t < heavy_tiles; ++t) {  // pieces of tile t = workgroups whose run touches it
-                const int c = (int)(((int64_t)(t + 1) * sk_steps - 1) / sk_q - ((int64_t)t * sk_steps) / sk_q + 1);
-                sk_cmax = sk_cmax > c ? sk_cmax : c;
-            }
-            const double sk_us = (double)cmax / 16.0 * sk_q * 2.0 + 2 * 4.0 + 2.0;
-            double light_us = 0.0;
-            // (the thin jobs go to the tile workgroups of the carrying launch where it has them: cut for their count)
-            const bool on_tiles = pol.tile_wgs > 0 && light_tiles > 0;
-                        // (0.6 / 0.8 / 1.0 / 1.2 units per tile workgroup: 1.874 / 1.862 / 1.858 / 1.903 ms per config2_train step)
-            int cl = light_tiles > 0 ? (on_tiles ? pol.tile_wgs : sk_grid) / light_tiles : 1;
-            const int cl_max = on_tiles ? p.slab_chunks : p.chunks;
-            cl = cl < 1 ? 1 : (cl > cl_max ? cl_max : cl);
-            for (int e = 0; e < nj; ++e)
-                if (cost[e] != cmax)
-                    light_us += tiles_of[e] * cl * ((double)cost[e] / 16.0 * (double)p.n / cl / 32.0 * 2.1 + 4.0);
-            const double sk_est = on_tiles ? sk_us : sk_us + light_us / sk_grid;
-            sk_on_tiles = on_tiles;
-            if (sk_q > sk_steps || sk_cmax > p.chunks || sk_est >= est_us) {
-                sk_q = 0;  // not better than whole chunks (or the slabs were not planned for that many pieces)
-                sk_on_tiles = false;
-            } else {
-                est_us = sk_est;
-                c_light = cl;
-                grid = sk_grid;
-            }
-        }
-        if (grid == 0 || est_us > pol.budget_us) wide = false;
-        int sk_jobs = 0;
-        for (int q = 0; q < nj && wide; ++q) {
-            const int e = order[q];
-            wg.job[q] = gg.job[e];
-            wg.lda[q] = gg.lda[e], wg.ldb[q] = gg.ldb[e];
-            wg.M[q] = gg.M[e], wg.N[q] = gg.N[e];
-            wg.gx[q] = (gg.N[e] + WGN - 1) / WGN;
-            if (sk_q > 0 && cost[e] == cmax) {  // stream-K job: unit_base counts its tiles, chunks = slabs to reduce
-                cj[e] = sk_cmax;
-                wg.chunks[q] = sk_cmax;
-                wg.kchunk[q] = (int32_t)((int64_t)sk_q * WGK);
-                max_kchunk = max_kchunk > (int64_t)sk_q * WGK ? max_kchunk : (int64_t)sk_q * WGK;
-                wg.unit_base[q] = units;
-                units += tiles_of[e];
-                sk_jobs = q + 1;
-                continue;
-            }
-            int64_t c = cost[e] == cmax ? c_heavy : c_light;
-            int64_t kc = (p.n + c - 1) / c;
-            kc = (kc + WGK - 1) / WGK * WGK;
-            c = (p.n + kc - 1) / kc;
-            cj[e] = (int)c;
-            wg.chunks[q] = (int32_t)c;
-            wg.kchunk[q] = (int32_t)kc;
-            max_kchunk = max_kchunk > kc ? max_kchunk : kc;
-            wg.unit_base[q] = units;
-            units += tiles_of[e] * (int)c;
-        }
-        if (wide) {
-            for (int e = 0; e < nj; ++e) gr.chunks[e] = cj[e];
-            // a job in ONE chunk with nothing to add to: its slab is the gradient itself - written in place, nothing for the
-            // reduce launch to do for it (every job so: no reduce launch)
-            bool all_one = !accumulate && sk_q == 0;
-            for (int q = 0; q < nj && !accumulate; ++q) {
-                const int e = order[q];
-                const bool sk_job = sk_q > 0 && cost[e] == cmax;
-                if (cj[e] == 1 && !sk_job) {
-                    wg.job[q].C = jobs[e].gw, wg.job[q].aux_out = jobs[e].gb;
-                    gr.nw[e] = 0, gr.nb[e] = 0;
-                } else {
-                    all_one = false;
-                }
-            }
-            if (all_one) L->direct = true;
-            if (pol.big_tiles_only && sk_q == 0) {  // XCD blocks for the leading whole-tile jobs (see WideGemmT.xcd_jobs)
-                int xj = 0;
-                while (xj < nj && cost[order[xj]] == cmax && cj[order[xj]] == 1 && tiles_of[order[xj]] % 8 == 0 &&
-                       wg.unit_base[xj] % 8 == 0)
-                    ++xj;
-                wg.xcd_jobs = (grid % 8 == 0) ? xj : 0;
-            }
-            wg.unit_base[nj] = units;
-            wg.K = p.n, wg.njobs = nj;
-            if (sk_q > 0) {
-                wg.sk_q = sk_q, wg.sk_steps = sk_steps, wg.sk_tiles = heavy_tiles, wg.sk_jobs = sk_jobs;
-                wg.sk_light_base = wg.unit_base[sk_jobs];
-                wg.light_on_tiles = sk_on_tiles ? 1 : 0;
-                units = grid;
-            } else {
-                units = grid < units ? grid : units;  // workgroups; units past the grid are picked up by stride
-            }
-        }
+        // buffer path: byte offsets inside a chunk (+ the two tiles the wide kernel fetches past its end) stay below 2^31.
+        // Rows need not be 16-byte aligned: buffer_load_dwordx4 only asks for dword alignment (the attention projections
+        // have 170-float rows)
+        const int64_t ld = jobs[e].lda > jobs[e].ldb ? jobs[e].lda : jobs[e].ldb;
+        L->buf = L->buf && (c.wide ? (c.max_kchunk + 4 * WGK) * ld * 4 < ((int64_t)1 << 31)
+                                   : gemm_buf_ok(OPND_MC, OPND_MC, p.kchunk, jobs[e].lda, p.kchunk, jobs[e].ldb, p.n));
     }
-    const bool wide_direct = wide && L->direct;
-    L->wide = wide;
-    L->units = units;
     if (!reduce_index_space(&gr, nj)) {
         set_error("weight gradients: %d jobs with more than 2^31 reduce items in one launch", nj);
         return GNF_EUNSUPPORTED;
     }
-    L->maxred = maxred;
-    L->direct = wide_direct;
-    L->buf = false;
-    if (wide) {
-        // buffer path: byte offsets inside a chunk (+ the two tiles fetched past its end) stay below 2^31.  Rows need
-        // not be 16-byte aligned: buffer_load_dwordx4 only asks for dword alignment (the attention projections have
-        // 170-float rows)
-        bool buf = true;
-        for (int e = 0; e < nj; ++e)
-            buf = buf && (max_kchunk + 4 * WGK) * (jobs[e].lda > jobs[e].ldb ? jobs[e].lda : jobs[e].ldb) * 4 < ((int64_t)1 << 31);
-        L->buf = buf;
-    } else {
-        const int gx = (maxN + TGN - 1) / TGN, gy = (maxM + TGM - 1) / TGM, nz = nj * p.chunks;
-        int groups = nz >= 32 ? 1 : (32 + nz - 1) / nz;   // enough bands that every XCD gets several
-        if (groups > gy) groups = gy;
-        const int rpg = (gy + groups - 1) / groups;
-        groups = (gy + rpg - 1) / rpg;
-        const int nv = nz * groups;
-        L->blocks = 8u * (unsigned)((nv + 7) / 8) * (unsigned)(gx * rpg);
-        L->gx = gx, L->gy = gy, L->nz = nz, L->groups = groups, L->rpg = rpg;
-        if (p.chunks == 1 && !accumulate) {  // one chunk: its "slab" IS the gradient - written in place, no reduce pass
-            for (int e = 0; e < nj; ++e) gg.job[e].C = jobs[e].gw, gg.job[e].aux_out = jobs[e].gb;
-            L->direct = true;
-        }
-        bool gbuf = true;
-        for (int e = 0; e < nj; ++e)
-            gbuf = gbuf && gemm_buf_ok(OPND_MC, OPND_MC, p.kchunk, jobs[e].lda, p.kchunk, jobs[e].ldb, p.n);
-        L->gbuf = gbuf;
-    }
     return GNF_OK;
 }
 
+// the wide kernel's arguments for a plan of at most G jobs (kMaxGroup: its own launch; kMergedGroup: the merged launch)
+template <int G>
+static void fill_wide(const DwLaunch& L, WideGemmT<G>* wg) {
+    const DwCut& c = L.cut;
+    const int nj = L.nj < G ? L.nj : G;
+    memset(wg, 0, sizeof(*wg));
+    for (int q = 0; q < nj; ++q) {  // launch order: costliest first
+        const int e = c.order[q];
+        wg->job[q] = L.gg.job[e];
+        wg->lda[q] = L.gg.lda[e], wg->ldb[q] = L.gg.ldb[e];
+        wg->M[q] = L.gg.M[e], wg->N[q] = L.gg.N[e];
+        wg->gx[q] = c.gx[q], wg->chunks[q] = c.chunks[q], wg->kchunk[q] = c.kchunk[q], wg->unit_base[q] = c.unit_base[q];
+    }
+    wg->unit_base[nj] = c.unit_base[nj];
+    wg->K = L.gg.K, wg->njobs = nj;
+    wg->sk_q = c.sk_q, wg->sk_steps = c.sk_steps, wg->sk_tiles = c.sk_tiles, wg->sk_jobs = c.sk_jobs;
+    wg->sk_light_base = c.sk_light_base, wg->xcd_jobs = c.xcd_jobs, wg->light_on_tiles = c.light_on_tiles;
+}
+
 static int run_weight_gemms(const DwLaunch& L, hipStream_t st) {
-    if (L.wide) {
+    const DwCut& c = L.cut;
+    if (c.wide) {
         GNF_ONCE_PER_DEVICE(
             GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_dw_wide<true>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             GNF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_dw_wide<false>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)));
+        WideGemm wg;
+        fill_wide(L, &wg);
         if (L.buf)
-            hipLaunchKernelGGL(k_gemm_dw_wide<true>, dim3((unsigned)L.units), dim3(kWideThreads), L.lds, st, L.wg);
+            hipLaunchKernelGGL(k_gemm_dw_wide<true>, dim3((unsigned)c.units), dim3(kWideThreads), L.lds, st, wg);
         else
-            hipLaunchKernelGGL(k_gemm_dw_wide<false>, dim3((unsigned)L.units), dim3(kWideThreads), L.lds, st, L.wg);
+            hipLaunchKernelGGL(k_gemm_dw_wide<false>, dim3((unsigned)c.units), dim3(kWideThreads), L.lds, st, wg);
         GNF_LAUNCH_CHECK("k_gemm_dw_wide");
     } else {
-        if (L.gbuf)
-            hipLaunchKernelGGL(k_gemm_dw_grouped<true>, dim3(L.blocks), dim3(kGemmThreads), 0, st, L.gg, L.gx, L.gy, L.nz,
-                               L.groups, L.rpg);
+        if (L.buf)
+            hipLaunchKernelGGL(k_gemm_dw_grouped<true>, dim3(c.g_blocks), dim3(kGemmThreads), 0, st, L.gg, c.g_gx, c.g_gy, c.g_nz,
+                               c.g_groups, c.g_rpg);
         else
-            hipLaunchKernelGGL(k_gemm_dw_grouped<false>, dim3(L.blocks), dim3(kGemmThreads), 0, st, L.gg, L.gx, L.gy, L.nz,
-                               L.groups, L.rpg);
+            hipLaunchKernelGGL(k_gemm_dw_grouped<false>, dim3(c.g_blocks), dim3(kGemmThreads), 0, st, L.gg, c.g_gx, c.g_gy, c.g_nz,
+                               c.g_groups, c.g_rpg);
         GNF_LAUNCH_CHECK("k_gemm_dw_grouped");
     }
     return GNF_OK;
 }
 
 static int run_weight_reduce(const DwLaunch& L, hipStream_t st) {
-    if (L.direct) return GNF_OK;
-    int64_t blocks = ((L.maxred + 3) / 4 * L.nj + 255) / 256;  // about one 16-byte quad per thread
+    if (L.cut.direct) return GNF_OK;
+    int64_t blocks = ((L.cut.maxred + 3) / 4 * L.nj + 255) / 256;  // about one 16-byte quad per thread
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
     hipLaunchKernelGGL(k_reduce_grouped, dim3((unsigned)blocks), dim3(256), 0, st, L.gr, (int)L.nj);
     GNF_LAUNCH_CHECK("k_reduce_grouped");
@@ -1660,30 +1390,16 @@ void k_half_bwd_dw(const BwdArgs a, const WideGemmS g, const GroupedReduceS r, c
 static_assert(kBwdThreads == kWideThreads, "the merged launch runs both bodies with one workgroup size");
 static_assert(sizeof(BwdArgs) + sizeof(WideGemmS) + sizeof(GroupedReduceS) + 16 <= 4096, "kernel arguments exceed 4 KB");
 
-static void narrow_wide(const WideGemm& w, WideGemmS* o) {
+// the reduce of a plan of nj <= G jobs at the width the merged launch's arguments have room for
+template <int G>
+static void narrow(const GroupedReduce& r, int nj, GroupedReduceT<G>* o) {
     memset(o, 0, sizeof(*o));
-    for (int q = 0; q < kMergedGroup && q < w.njobs; ++q) {
-        o->job[q] = w.job[q];
-        o->lda[q] = w.lda[q], o->ldb[q] = w.ldb[q];
-        o->M[q] = w.M[q], o->N[q] = w.N[q];
-        o->unit_base[q] = w.unit_base[q];
-        o->gx[q] = w.gx[q], o->chunks[q] = w.chunks[q], o->kchunk[q] = w.kchunk[q];
-    }
-    o->unit_base[w.njobs] = w.unit_base[w.njobs];
-    o->K = w.K, o->njobs = w.njobs;
-    o->sk_q = w.sk_q, o->sk_steps = w.sk_steps, o->sk_tiles = w.sk_tiles, o->sk_jobs = w.sk_jobs;
-    o->sk_light_base = w.sk_light_base;
-    o->xcd_jobs = 0;
-    o->light_on_tiles = w.light_on_tiles;
-}
-static void narrow_reduce(const GroupedReduce& r, int nj, GroupedReduceS* o) {
-    memset(o, 0, sizeof(*o));
-    for (int q = 0; q < kMergedGroup && q < nj; ++q) {
+    for (int q = 0; q < G && q < nj; ++q) {
         o->job[q] = r.job[q];
         o->nw[q] = r.nw[q], o->nb[q] = r.nb[q], o->chunks[q] = r.chunks[q];
     }
     o->accumulate = r.accumulate;
-    (void)reduce_index_space(o, nj < kMergedGroup ? nj : kMergedGroup);  // (a subset of a plan that fitted)
+    (void)reduce_index_space(o, nj < G ? nj : G);  // (a subset of a plan that fitted)
 }
 
 // bwd: the half-step to walk (NULL: none - the tail of the pipeline); dw: GEMMs to run beside it (NULL: none);
@@ -1696,8 +1412,8 @@ static int launch_half_bwd_dw(const BwdArgs* bwd, int64_t bwd_tiles, size_t bwd_
     memset(&g, 0, sizeof(g));
     memset(&r, 0, sizeof(r));
     int n_dw = 0, r_nj = 0;
-    if (dw) narrow_wide(dw->wg, &g), n_dw = dw->units;
-    if (red && !red->direct) narrow_reduce(red->gr, red->nj, &r), r_nj = red->nj;
+    if (dw) fill_wide(*dw, &g), n_dw = dw->cut.units;
+    if (red && !red->cut.direct) narrow(red->gr, red->nj, &r), r_nj = red->nj;
     const int n_bwd = bwd ? (int)bwd_tiles : 0;
     int grid = n_bwd + n_dw;
     if (r_nj > 0 && grid == n_bwd) grid += 64;  // reduce only: some workgroups to carry it
@@ -1718,7 +1434,7 @@ static int launch_half_bwd_dw(const BwdArgs* bwd, int64_t bwd_tiles, size_t bwd_
 
 // the backward half of the merged-launch / stash conditions (the forward half: fused_stash_shape)
 static bool merged_walk_ok(const GnfFlow* flow, int64_t n, int64_t* tiles_out, size_t* lds_out) {
-    if (opt(OPT_BWD_GENERIC) || opt(OPT_DW_GROUPED)) return false;
+    if (opt(OPT_BWD_GENERIC) || dw_options().grouped) return false;
     if (flow->s_nets[0].attn && 2 * (flow->s_nets[0].num_layers + 4) > kMergedGroup) return false;
     const int n_nets = flow_net_count(flow);
     for (int q = 0; q < n_nets; ++q)
@@ -2205,6 +1921,100 @@ size_t gnf_backward_workspace_bytes(int64_t n_nodes, int32_t D, const GnfFlow* f
     return plan_backward(n_nodes, D, &flow->s_nets[0], kBwdSetsDefault, flow_net_count(flow)).total * sizeof(float);
 }
 
+// The dW plan of one half-step as a flat record (include/gnf_dw_plan.h: a debugging and test view).  Plans on a synthetic
+// workspace base and synthetic gradient pointers - nothing is dereferenced, no device is touched.
+int64_t gnf_dw_plan_describe(int64_t n_nodes, int32_t D, const GnfMlp* net, int32_t route, int64_t bwd_tiles, size_t bwd_lds,
+                             int32_t stashed, int32_t last, int32_t slab_set, int32_t accumulate, int64_t* out, int64_t cap) {
+    if (!net || !out || cap < 0 || n_nodes < 0 || D < 2 || (D & 1) || net->num_layers < 1 || net->num_layers > GNF_MAX_LAYERS ||
+        route < GNF_DW_ROUTE_STREAMS || route > GNF_DW_ROUTE_GENERIC || bwd_tiles < 0 || slab_set < 0) {
+        set_error("gnf_dw_plan_describe: bad argument (n_nodes=%lld D=%d route=%d)", (long long)n_nodes, D, route);
+        return GNF_EINVAL;
+    }
+    const BwdPlan p = plan_backward(n_nodes, D, net, kBwdSetsDefault, 1);
+    if (slab_set >= p.slab_sets || (route == GNF_DW_ROUTE_MERGED && dw_options().grouped)) {
+        set_error("gnf_dw_plan_describe: slab_set %d of %d (or the merged route under dw_grouped, where the walk never takes it)",
+                  slab_set, p.slab_sets);
+        return GNF_EINVAL;
+    }
+    float* const ws = reinterpret_cast<float*>((uintptr_t)1 << 44);     // 256-byte aligned, never dereferenced
+    float* const grad0 = reinterpret_cast<float*>((uintptr_t)1 << 45);  // gradient buffers: 256 bytes apart
+    GnfMlp gm[2];
+    GnfAttn ga[2];
+    int slot = 0;
+    for (int q = 0; q < 2; ++q) {
+        gm[q] = *net;
+        for (int j = 0; j < net->num_layers; ++j) gm[q].W[j] = grad0 + 64 * slot++, gm[q].b[j] = grad0 + 64 * slot++;
+        if (net->attn) {
+            ga[q] = *net->attn;
+            ga[q].Wq = grad0 + 64 * slot++, ga[q].Wk = grad0 + 64 * slot++, ga[q].Wv = grad0 + 64 * slot++;
+            ga[q].Wo = grad0 + 64 * slot++;
+            gm[q].attn = &ga[q];
+        }
+    }
+    const GnfMlp* const nets[2] = {net, net};
+    const GnfMlp* const grads[2] = {&gm[0], &gm[1]};
+    const BwdOperands o = bwd_operands(p, ws, 0, net->attn != nullptr);
+    WGJob jobs[kMaxGroup];
+    const int nj = weight_grad_jobs(p, o, nets, grads, jobs);
+    const bool around = route == GNF_DW_ROUTE_STREAMS;   // (the policies, as half_merged and half_streams ask for them)
+    const DwPolicy pol = route == GNF_DW_ROUTE_MERGED
+                             ? dw_policy_merged(dw_options(), big_cu_count(), (int)bwd_tiles, bwd_lds, stashed != 0, last != 0)
+                             : dw_policy(net, around ? bwd_tiles : 0, around ? bwd_lds : 0);
+    static thread_local DwLaunch L;   // (kept off the stack)
+    memset(&L, 0, sizeof(L));
+    const int rc = plan_weight_grads(p, pol, jobs, nj, accumulate != 0, ws, slab_set, &L);
+    if (rc) return rc;
+    const int64_t need = 36 + (int64_t)nj * (13 + 7) + nj + 1;
+    if (cap < need) {
+        set_error("gnf_dw_plan_describe: the record has %lld fields, cap %lld", (long long)need, (long long)cap);
+        return GNF_EINVAL;
+    }
+    auto where = [&](const float* ptr) -> int64_t {   // offset from the workspace base | -1 NULL | the gradient's tag
+        if (!ptr) return -1;
+        if (ptr >= ws && ptr <= ws + p.total) return (int64_t)(ptr - ws);   // (an empty batch's operands sit at the end)
+        for (int e = 0; e < nj; ++e) {
+            if (ptr == jobs[e].gw) return -(2 + 2 * (int64_t)e);
+            if (ptr == jobs[e].gb) return -(3 + 2 * (int64_t)e);
+        }
+        return INT64_MIN;   // (never: every pointer of a plan is one of the above)
+    };
+    int64_t* w = out;
+    const DwCut& c = L.cut;
+    WideGemm wg;   // (what run_weight_gemms would launch; zeros for a grouped plan)
+    memset(&wg, 0, sizeof(wg));
+    if (c.wide) fill_wide(L, &wg);
+    *w++ = GNF_DW_PLAN_RECORD_VERSION, *w++ = p.n, *w++ = nj, *w++ = c.wide, *w++ = L.buf, *w++ = c.direct;
+    *w++ = c.units, *w++ = (int64_t)L.lds, *w++ = c.maxred;
+    *w++ = p.chunks, *w++ = p.kchunk, *w++ = p.slab_chunks, *w++ = p.slab_sets, *w++ = slab_set, *w++ = (int64_t)p.wslab;
+    *w++ = (int64_t)p.bslab, *w++ = (int64_t)p.slab_stride, *w++ = p.wsum, *w++ = p.osum;
+    *w++ = wg.sk_q, *w++ = wg.sk_steps, *w++ = wg.sk_tiles, *w++ = wg.sk_jobs, *w++ = wg.sk_light_base, *w++ = wg.xcd_jobs;
+    *w++ = wg.light_on_tiles, *w++ = wg.unit_base[nj];
+    *w++ = L.gr.accumulate, *w++ = L.gr.singles, *w++ = L.gr.qpre[nj];
+    *w++ = c.g_gx, *w++ = c.g_gy, *w++ = c.g_nz, *w++ = c.g_groups, *w++ = c.g_rpg, *w++ = c.g_blocks;
+    bool taken[kMaxGroup] = {};
+    for (int q = 0; q < nj; ++q) {
+        int e = q;   // the grouped kernel keeps the job list's order; the wide kernel's is found by the operands
+        for (int k = 0; c.wide && k < nj; ++k)
+            if (!taken[k] && wg.job[q].A == jobs[k].A && wg.job[q].B == jobs[k].B && wg.M[q] == jobs[k].M && wg.N[q] == jobs[k].N) {
+                e = k;
+                break;
+            }
+        taken[e] = true;
+        const GemmJob& gj = c.wide ? wg.job[q] : L.gg.job[q];
+        *w++ = e, *w++ = jobs[e].M, *w++ = jobs[e].N, *w++ = c.wide ? wg.gx[q] : 0;
+        *w++ = c.wide ? wg.chunks[q] : L.gg.chunks, *w++ = c.wide ? (int64_t)wg.kchunk[q] : L.gg.kchunk;
+        *w++ = c.wide ? wg.unit_base[q] : 0, *w++ = jobs[e].lda, *w++ = jobs[e].ldb;
+        *w++ = where(gj.A), *w++ = where(gj.B), *w++ = where(gj.C), *w++ = where(gj.aux_out);
+    }
+    for (int e = 0; e < nj; ++e) {
+        const ReduceJob& rj = L.gr.job[e];
+        *w++ = L.gr.nw[e], *w++ = L.gr.nb[e], *w++ = L.gr.chunks[e];
+        *w++ = where(rj.wslab), *w++ = where(rj.bslab), *w++ = where(rj.gw), *w++ = where(rj.gb);
+    }
+    for (int e = 0; e <= nj; ++e) *w++ = L.gr.qpre[e];
+    return (int64_t)(w - out);
+}
+
 // Validate, plan, then 2 T half-steps in reverse: resolve_half decides what the half-step reads, half_merged or
 // half_streams (one route per call) issues its launches.  The routes are local functions over this call's plan.
 int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFlow* flow, const GnfFlow* grad,
@@ -2462,14 +2272,10 @@ int gnf_grevnet_backward_f32(const GnfCsr* csr, const GnfCsr* csr_t, const GnfFl
         // this half-step's dW GEMMs ride in the next launch (the last one's get the whole chip)
         WGJob jobs[kMaxGroup];
         const int nj = weight_grad_jobs(p, o, h.nets, h.grads, jobs);
-        const int cus = big_cu_count();
-        int room = h.last ? cus : cus - (int)t.tiles;   // CUs the backward tiles of the NEXT launch leave
-        if (const int64_t force = opt(OPT_DW_WIDE_UNITS)) room = force < room ? (int)force : room;  // (shape forcing for the parity tests)
-        DwPolicy pol{room, t.lds, 1e30};
-        if (mstashed && !h.last && !opt(OPT_DW_THIN_ON_DW)) pol.tile_wgs = (int)t.tiles;  // (the launch that carries this plan walks the next half-step)
+        const DwPolicy pol = dw_policy_merged(dw_options(), big_cu_count(), (int)t.tiles, t.lds, mstashed, h.last);
         rc_ = plan_weight_grads(p, pol, jobs, nj, h.acc, wsf, cur, &pend[cur]);
         if (rc_) return rc_;
-        pend_ok[cur] = pend[cur].wide && pend[cur].buf && nj <= kMergedGroup;
+        pend_ok[cur] = pend[cur].cut.wide && pend[cur].buf && nj <= kMergedGroup;
         if (!pend_ok[cur]) {  // (a plan the merged launch cannot carry: run it here and now)
             rc_ = run_weight_gemms(pend[cur], st);
             if (rc_) return rc_;

@@ -531,6 +531,9 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 /* Added within ABI v10: batches and both of their CSRs assembled on the device from a resident dataset, and the complete
  * topology from node counts alone (gnf_batches.h) - likewise. */
 #include "gnf_batches.h"
+/* Added within ABI v10: a read-only view of the backward walk's weight-gradient launch plan, for debugging and the tests
+ * (gnf_dw_plan.h) - likewise, but with no stability promise. */
+#include "gnf_dw_plan.h"
 
 #ifdef __cplusplus
 }

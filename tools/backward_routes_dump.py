@@ -35,6 +35,8 @@ DM_LN = dict(DM, attn=dict(DM["attn"], layer_norm=True, residual=True))
 SELF = dict(MP, activation="relu", attn=dict(scope="graph", kq_dim=3, v_dim=5))
 MULTI = dict(MP, activation="relu", attn=dict(scope="graph", kq_dim=3, v_dim=5, num_heads=2, out_dim=6))
 SMALL, BIG = [11, 13, 16], "big"  # BIG: 264 graphs of 9 .. 16 nodes, more than 192 tiles (tools/dw_modes_check.py big)
+MID = "mid"                        # 150 such graphs: about 120 tiles - the merged launch with enough k-steps for stream-K
+WIDE = dict(MP, D=48, latent=200)  # hidden layers of 2 x 2 wide-kernel tiles
 
 # name, hyper-parameters, library options, trainer attributes, graph sizes ([]: the empty batch after a SMALL one)
 CASES = [
@@ -55,7 +57,17 @@ CASES = [
     ("self_attn", SELF, {}, {}, SMALL),
     ("multihead_self_attn", MULTI, {}, {}, SMALL),
     ("layered_stash", dict(MP, D=24, latent=1280, activation="relu"), {}, {}, SMALL),
-    ("mp_big", dict(MP, D=48, latent=200), {}, {}, BIG),
+    ("mp_big", WIDE, {}, {}, BIG),
+    # the wide weight-gradient kernel's shapes, forced: the summation order of a gradient is fixed by the launch plan (how
+    # the node axis is cut, which slabs the reduce adds), so any change of a plan's cut shows in these
+    *[(f"mp_units{u}", MP, dict(dw_wide_units=u), {}, SMALL) for u in (8, 13, 200)],
+    ("mp_thin_on_dw", MP, dict(dw_thin_on_dw=1), {}, SMALL),
+    ("mp_mid", WIDE, {}, {}, MID),
+    *[(f"mp_mid_units{u}", WIDE, dict(dw_wide_units=u), {}, MID) for u in (8, 13, 200)],
+    ("mp_mid_thin_on_dw", WIDE, dict(dw_thin_on_dw=1), {}, MID),
+    ("mp_mid_recompute", WIDE, {}, dict(stash_mlp_rows=False), MID),
+    *[(f"mp_big_units{u}", WIDE, dict(dw_wide_units=u), {}, BIG) for u in (8, 13, 200)],
+    ("mp_big_thin_on_dw", WIDE, dict(dw_thin_on_dw=1), {}, BIG),
     ("mp_empty", MP, {}, {}, []),
 ]
 
@@ -74,7 +86,7 @@ def route(hp, opts, attrs, sizes):
         return f"presumed streams / generic (hidden width {hp['latent']}), {stash} (layered mode), {aux}"
     if opts.get("dw_grouped"):
         return f"presumed streams / fused (dw_grouped=1), {stash}, {aux}"
-    if sizes is BIG:
+    if sizes == BIG:
         return f"presumed streams / fused (more than 192 tiles), {stash} (the library declines it above one tile per CU), {aux}"
     return f"presumed merged, {stash}"
 
@@ -89,7 +101,7 @@ def tamed(node):
 
 
 def batch(sizes, d, seed):
-    n_node = np.random.default_rng(5).integers(9, 17, size=264) if sizes is BIG else np.asarray(sizes)
+    n_node = np.random.default_rng(5).integers(9, 17, size=264 if sizes == BIG else 150) if sizes in (BIG, MID) else np.asarray(sizes)
     n_node = n_node.astype(np.int32)
     s, r, ne = senders_receivers(n_node) if len(n_node) else (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32))
     x = (np.random.default_rng(seed).standard_normal((int(n_node.sum()), d)) * 0.7).astype(np.float32)
