@@ -7,7 +7,10 @@ names, kept small) and save it where examples/train_grevnet_with_data.py --make_
 Batches come from datasets.GraphDataset (random Gaussian node features on the dataset's topologies) or, with --device_batches,
 from datasets.DeviceGraphDataset (the dataset stays on the device; a batch and both of its CSRs are one call); every iteration is
 train.EncoderTrainer.step (train-forward, binary_loss, backward, Adam); every --eval_every_n_steps a random test batch goes
-through encoder.evaluate, and the figures run_gnn.py:441-465 logs are printed.  --binary_dist_fn picks the decoder's distance
+through encoder.evaluate, and the figures run_gnn.py:441-465 logs are printed.  --denoising trains the denoising auto-encoder:
+the encoder reads the batch with edges deleted at random (--deletion_prob; datasets.NoisyGraphDataset, on the device with
+--device_batches) and is scored against the batch as it was; the log line then reads NUM_NODES:NUM_REMOVED:NUM_INCORRECT.
+--binary_dist_fn picks the decoder's distance
 function and --tune_sigmoid (with sigmoid_l2) trains its temp and shift from 10 and 1 (run_gnn.py:146-165); the function, with
 the trained values, is saved with the encoder.  --loss_type triplet trains on the sampled triplet loss instead (run_gnn.py:82-91,
 249-252: --triplet_dist_fn scores the pairs, --triplet_loss_fn margin | relative forms the terms, --num_sampling_loops rounds per
@@ -86,6 +89,11 @@ def make_parser():
     # keep the dataset on the device and assemble every batch, with both of its CSRs, there (datasets.DeviceGraphDataset);
     # the node features then come from a device generator: same distribution, other numbers than the host route's
     ap.add_argument("--device_batches", action="store_true")
+    # the denoising auto-encoder (run_gnn.py:40-41, 238): the encoder reads the batch with edges deleted at random
+    # (datasets.NoisyGraphDataset / perturb_batch: every node pair's edges go with probability --deletion_prob, self loops stay)
+    # and is scored against the batch as it was
+    ap.add_argument("--denoising", action="store_true")
+    ap.add_argument("--deletion_prob", type=float, default=0.3)
     return ap
 
 
@@ -125,18 +133,25 @@ def main():
     # the decoder's distance function: with --tune_sigmoid the token whose parameters the trainer moves, under the triplet
     # loss the one its edge-error figures are counted with (pred_adj of loss.py:268)
     dist_fn = trainer.triplet_adj_dist_fn if triplet else trainer.distance_fn
-    if F.device_batches:
+    if F.denoising:
+        dataset = D.NoisyGraphDataset(F.dataset, F.node_embedding_dim, F.deletion_prob, F.gaussian_scale, seed=F.random_seed,
+                                      device=dev if F.device_batches else None)
+    elif F.device_batches:
         dataset = D.DeviceGraphDataset(F.dataset, F.node_embedding_dim, F.gaussian_scale, seed=F.random_seed, device=dev)
     else:
         dataset = D.GraphDataset(F.dataset, F.node_embedding_dim, F.gaussian_scale, seed=F.random_seed)
 
-    def log(prefix, it, n_node, res, out_nodes=None):
+    def log(prefix, it, n_node, res, out_nodes=None, num_removed=None):
         per_graph = adj_loss.incorrect_edges_per_graph(res).cpu().numpy()
         total = float(adj_loss.total_incorrect_edges(res))
         print("*" * 100)
         print(f"iteration num: {it}")
-        print("NUM_NODES:NUM_INCORRECT")
-        print(", ".join(f"{a}:{b}" for a, b in zip(n_node.cpu().numpy(), per_graph)))
+        if num_removed is not None:      # run_gnn.py:405-413
+            print("NUM_NODES:NUM_REMOVED:NUM_INCORRECT")
+            print(", ".join(f"{a}:{b}:{c}" for a, b, c in zip(n_node.cpu().numpy(), num_removed.cpu().numpy(), per_graph)))
+        else:
+            print("NUM_NODES:NUM_INCORRECT")
+            print(", ".join(f"{a}:{b}" for a, b in zip(n_node.cpu().numpy(), per_graph)))
         print(f"{prefix}sum loss: {float(res['sum_loss'])}")
         print(f"{prefix}mean loss: {float(res['mean_loss'])}")
         if "skipped_terms" in res:
@@ -149,13 +164,17 @@ def main():
             print(f"gnn output norm:{float(out_nodes.norm(dim=1).mean())}")
 
     for iteration in range(F.num_train_iters):
-        graph = dataset.get_next_train_batch(F.train_batch_size, dev)
+        num_removed = None
+        if F.denoising:
+            graph, noisy, num_removed = dataset.get_next_train_batch(F.train_batch_size, dev)
+        else:
+            graph = dataset.get_next_train_batch(F.train_batch_size, dev)
         try:
-            res = trainer.step(graph)
+            res = trainer.step(noisy, true_graph=graph) if F.denoising else trainer.step(graph)
         except _abi.GnfError as e:
             raise SystemExit(str(e))
         if iteration % F.log_every_n_steps == 0:
-            log("", iteration, graph.n_node, res, res["gnn_output"].nodes)
+            log("", iteration, graph.n_node, res, res["gnn_output"].nodes, num_removed)
             print(f"learning rate: {trainer.current_learning_rate()}")
             if F.tune_sigmoid:
                 temp, shift = dist_fn.values()

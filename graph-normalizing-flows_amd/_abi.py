@@ -308,6 +308,21 @@ _DW_PLAN_SIGNATURES = {
     "gnf_dw_plan_describe": (C.c_int64, [C.c_int64, C.c_int32, C.POINTER(GnfMlp), C.c_int32, C.c_int64, C.c_size_t, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int64]),
 }
+# include/gnf_perturb.h (included by gnf.h, added within ABI v10): edge-deletion noise on a batch with both CSRs of the noisy batch.
+# A table of its own for the same reason.
+GNF_PERTURB_LOOPS_KEEP, GNF_PERTURB_LOOPS_DRAW = 0, 1
+
+
+class GnfPerturbSpec(C.Structure):   # include/gnf_perturb.h
+    _fields_ = [("deletion_prob", C.c_double), ("seed", C.c_uint64), ("seed_dev", C.c_void_p), ("self_loops", C.c_int32)]
+
+
+_PERTURB_SIGNATURES = {
+    "gnf_perturb_edges_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "gnf_perturb_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GnfCsr), C.POINTER(GnfCsr),
+                                    C.POINTER(GnfPerturbSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -326,6 +341,7 @@ HASH_SYMBOLS = tuple(_HASH_SIGNATURES)
 TRIPLET_SYMBOLS = tuple(_TRIPLET_SIGNATURES)
 BATCH_SYMBOLS = tuple(_BATCH_SIGNATURES)
 DW_PLAN_SYMBOLS = tuple(_DW_PLAN_SIGNATURES)
+PERTURB_SYMBOLS = tuple(_PERTURB_SIGNATURES)
 
 _lib = None
 
@@ -343,7 +359,7 @@ def lib():
                                   **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
                                   **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
                                   **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES, **_TRIPLET_SIGNATURES,
-                                  **_BATCH_SIGNATURES, **_DW_PLAN_SIGNATURES}.items():
+                                  **_BATCH_SIGNATURES, **_DW_PLAN_SIGNATURES, **_PERTURB_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

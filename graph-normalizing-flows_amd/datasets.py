@@ -11,6 +11,9 @@
                          grevnet_synthetic_data.py:17-21 and utils.py:164-183 (sender-major order).
   * DeviceGraphDataset / complete_batch - the same batches assembled on the device (include/gnf_batches.h): the dataset is
                          uploaded once, a batch and both of its CSRs come out of one gnf_batch_assemble / gnf_complete_batch.
+  * perturb_batch / NoisyGraphDataset - the denoising encoder's noisy batches (include/gnf_perturb.h; graph_data.py:206-280,
+                         which deletes nothing): edges deleted per unordered node pair by a defined integer hash, the noisy
+                         edge list and both of its CSRs from one gnf_perturb_edges on the device, numpy on the host.
   * synthetic stand-ins - protein / citeseer(ego) datasets are absent from the reference
                          (.MISSING_LARGE_BLOBS); BASELINE.md section 4 fixes the generators used instead.
 """
@@ -251,6 +254,174 @@ class DeviceGraphDataset:
 
     def test_n_nodes(self):
         return [int(self.all.n_node[i]) for i in self.test_ids]
+
+
+# ----------------------------------------------------------------------------------------------
+# Edge-deletion noise for the denoising encoder (include/gnf_perturb.h; run_gnn.py --denoising, graph_data.py:206-280)
+# ----------------------------------------------------------------------------------------------
+PERTURB_LOOPS = {"keep": 0, "draw": 1}       # GNF_PERTURB_LOOPS_KEEP / GNF_PERTURB_LOOPS_DRAW
+PERTURB_KEYS = ("senders", "receivers", "rowptr", "col", "rowptr_t", "col_t", "n_edge", "num_removed", "totals")
+_M64 = (1 << 64) - 1
+
+
+def perturb_threshold(deletion_prob):
+    """(uint64_t)(deletion_prob * 2^32) of include/gnf_perturb.h: a pair is deleted iff its draw is below it."""
+    p = float(deletion_prob)
+    if not 0.0 <= p <= 1.0:      # NaN included
+        raise ValueError(f"deletion_prob={deletion_prob!r} is not in [0, 1]")
+    return int(p * 4294967296.0)
+
+
+def perturb_draw(seed, lo, hi):
+    """The pair's 32-bit draw of include/gnf_perturb.h in numpy uint64 arithmetic (wrapping); lo <= hi are node ids."""
+    u = np.uint64
+    lo = np.atleast_1d(np.asarray(lo)).astype(u)
+    hi = np.atleast_1d(np.asarray(hi)).astype(u)
+    with np.errstate(over="ignore"):
+        x = np.full(1, int(seed) & _M64, u) ^ (u(0x9E3779B97F4A7C15) * (lo + u(1))) ^ (u(0xBF58476D1CE4E5B9) * (hi + u(1)))
+        x = x ^ (x >> u(30))
+        x = x * u(0xBF58476D1CE4E5B9)
+        x = x ^ (x >> u(27))
+        x = x * u(0x94D049BB133111EB)
+        x = x ^ (x >> u(31))
+    return (x >> u(32)).astype(np.int64)
+
+
+def perturb_keep_mask(senders, receivers, deletion_prob, seed, self_loops="keep"):
+    """bool [E]: which directed edges (batch-global ids) survive - the definition of include/gnf_perturb.h."""
+    s = np.asarray(senders, np.int64)
+    r = np.asarray(receivers, np.int64)
+    keep = perturb_draw(seed, np.minimum(s, r), np.maximum(s, r)) >= perturb_threshold(deletion_prob)
+    if PERTURB_LOOPS[self_loops] == 0:
+        keep |= s == r
+    return keep
+
+
+def perturb_arrays_host(senders, receivers, n_nodes, n_edge, deletion_prob, seed, self_loops="keep"):
+    """The host route gnf_perturb_edges is held to: filter the edge list with perturb_keep_mask, then graphs.build_csr_host by
+    receiver and by sender on what is left.  Returns the PERTURB_KEYS arrays (int32; totals int64 [2] = {E', E - E'})."""
+    from .graphs import build_csr_host
+    s = np.asarray(senders, np.int64)
+    r = np.asarray(receivers, np.int64)
+    n_edge = np.asarray(n_edge, np.int64)
+    keep = perturb_keep_mask(s, r, deletion_prob, seed, self_loops)
+    s2, r2 = s[keep], r[keep]
+    rowptr, col = build_csr_host(s2, r2, int(n_nodes))
+    rowptr_t, col_t = build_csr_host(r2, s2, int(n_nodes))
+    kept = np.bincount(np.repeat(np.arange(len(n_edge)), n_edge)[keep], minlength=len(n_edge)).astype(np.int64)
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    return dict(senders=i32(s2), receivers=i32(r2), rowptr=i32(rowptr), col=i32(col), rowptr_t=i32(rowptr_t), col_t=i32(col_t),
+                n_edge=i32(kept), num_removed=i32(n_edge - kept), totals=np.array([len(s2), len(s) - len(s2)], np.int64))
+
+
+def perturb_batch(graph, deletion_prob, seed, self_loops="keep", seed_tensor=None, exact=True):
+    """The noisy batch of the denoising encoder: `graph` with every unordered node pair's edges deleted with probability
+    deletion_prob (the definition, the self_loops modes "keep" / "draw" and the random stream: include/gnf_perturb.h).
+    Returns (noisy, num_removed): noisy shares nodes, n_node and globals with `graph` and has edge arrays of its own, with
+    edges = zeros(E'); num_removed is int32 [B] on the batch's device, deleted directed entries per graph.
+    On a HIP device one gnf_perturb_edges call makes the edge list and BOTH CSRs of the noisy batch from csr_of(graph) in both
+    orientations (cache hits on a DeviceGraphDataset batch).
+      exact=True   reads E' once (an 8-byte copy, the call's only synchronisation), narrows the tensors to E' and seeds the CSR
+                   cache for both orientations and the node-offset cache: the encoder and the trainer launch no gnf_build_csr
+                   on `noisy`.
+      exact=False  copies nothing to the host and synchronises nowhere - the capturable form.  Returns (noisy, num_removed,
+                   info): the edge tensors of noisy have the capacity E of which the first info["total_edges"] (0-d device
+                   int64) are valid, the rest unspecified; info also holds "rowptr", "col", "rowptr_t", "col_t".  No cache is
+                   seeded (as flow.decode_graphs' edge_capacity mode).
+    seed_tensor: None, or an int64 [1] tensor on the batch's device whose 64 bits are the seed, read by the kernels at run time
+    instead of `seed`: a captured call replayed after the tensor changed draws fresh noise.
+    On a CPU batch the same arrays come from perturb_arrays_host (numpy); exact is always True there and no cache is seeded."""
+    import ctypes as C
+    import torch
+    from . import _abi
+    from .graphs import (Csr, GraphsTuple, csr_desc, csr_of, node_offsets_of, seed_csr_cache, seed_node_offsets_cache)
+    loops = PERTURB_LOOPS[self_loops]
+    perturb_threshold(deletion_prob)                                 # ValueError for a bad probability, on every route
+    dev = graph.senders.device
+    b, n, e = int(graph.n_node.shape[0]), int(graph.nodes.shape[0]), int(graph.senders.shape[0])
+    if dev.type != "cuda":
+        if seed_tensor is not None:
+            seed = int(seed_tensor.reshape(-1)[0])
+        out = perturb_arrays_host(graph.senders.numpy(), graph.receivers.numpy(), n, graph.n_edge.numpy(), deletion_prob, seed,
+                                  self_loops)
+        e2 = int(out["totals"][0])
+        noisy = graph.replace(senders=torch.from_numpy(out["senders"]), receivers=torch.from_numpy(out["receivers"]),
+                              edges=torch.zeros(e2, dtype=torch.float32), n_edge=torch.from_numpy(out["n_edge"]))
+        return noisy, torch.from_numpy(out["num_removed"])
+    lib = _abi.lib()
+    csr, csr_t = csr_of(graph), csr_of(graph, by_sender=True)
+    offsets = node_offsets_of(graph)
+    ws_bytes = lib.gnf_perturb_edges_workspace_bytes(b, n, e)
+    live = b > 0 and n > 0       # otherwise the call writes rowptr[0] and totals only: everything else is zeros
+    snd, rcv, rowptr, col, rowptr_t, col_t, n_edge, removed, tot, ws = _int32_arena(
+        [e, e, n + 1, e, n + 1, e, b, b, 4, (ws_bytes + 3) // 4 + 1], dev, zero=not live)
+    totals = tot.view(torch.int64)
+    if seed_tensor is not None and (seed_tensor.device != dev or seed_tensor.dtype != torch.int64 or seed_tensor.numel() < 1):
+        raise ValueError("perturb_batch: seed_tensor is an int64 [1] tensor on the batch's device")
+    spec = _abi.GnfPerturbSpec(float(deletion_prob), int(seed) & _M64, 0 if seed_tensor is None else seed_tensor.data_ptr(), loops)
+    d, d_t = csr_desc(graph, csr, node_offsets=True), csr_desc(graph, csr_t, node_offsets=True)
+    edge_ptr = lambda t: _abi.ptr(t if e else None)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_perturb_edges(edge_ptr(graph.senders), edge_ptr(graph.receivers), _abi.ptr(graph.n_edge), C.byref(d),
+                                         C.byref(d_t), C.byref(spec), _abi.ptr(snd), _abi.ptr(rcv), _abi.ptr(rowptr),
+                                         _abi.ptr(col), _abi.ptr(rowptr_t), _abi.ptr(col_t), _abi.ptr(n_edge), _abi.ptr(removed),
+                                         _abi.ptr(totals), _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_perturb_edges")
+    if not exact:
+        noisy = GraphsTuple(nodes=graph.nodes, edges=torch.zeros(e, dtype=torch.float32, device=dev), receivers=rcv, senders=snd,
+                            globals=graph.globals, n_node=graph.n_node, n_edge=n_edge)
+        return noisy, removed, dict(total_edges=totals[0], rowptr=rowptr, col=col, rowptr_t=rowptr_t, col_t=col_t)
+    e2 = int(totals[0].item())
+    noisy = GraphsTuple(nodes=graph.nodes, edges=torch.zeros(e2, dtype=torch.float32, device=dev), receivers=rcv[:e2],
+                        senders=snd[:e2], globals=graph.globals, n_node=graph.n_node, n_edge=n_edge)
+    seed_csr_cache(noisy, Csr(rowptr, col[:e2], n, e2))
+    seed_csr_cache(noisy, Csr(rowptr_t, col_t[:e2], n, e2), by_sender=True)
+    seed_node_offsets_cache(noisy, offsets)
+    return noisy, removed
+
+
+class NoisyGraphDataset(GraphDataset):
+    """graph_data.py:206-280 for the denoising encoder (run_gnn.py --denoising): get_next_train_batch hands out
+    (true, noisy, num_removed) - the clean batch, the same batch with edges deleted by perturb_batch, and the deleted directed
+    entries per graph.  Two things the reference does not do and this class does: it ACTUALLY DELETES the edges (the
+    reference's remove_edges_from is commented out, graph_data.py:247) and it RETURNS THE NOISY BATCH (the reference returns
+    the clean batch twice, graph_data.py:279-280).  The noise seed is `seed` plus a counter of the train batches handed out, so
+    no two steps share a mask.  Test batches are clean: the reference feeds the test batch as its own noisy version
+    (run_gnn.py:445-446).
+    device=None: a GraphDataset - batches are assembled and perturbed on the host (numpy), then moved to the `device` argument
+    of the batch methods, if any.  Otherwise it wraps a DeviceGraphDataset on that device: the true batch and both of its CSRs
+    come from one gnf_batch_assemble, the noisy batch and both of its CSRs from one gnf_perturb_edges; `dataset_name` may then
+    also be an EdgeListDataset."""
+
+    def __init__(self, dataset_name, node_embedding_dim, deletion_prob=0.5, gaussian_scale=1.0, seed=12345, device=None,
+                 self_loops="keep"):
+        perturb_threshold(deletion_prob)
+        PERTURB_LOOPS[self_loops]
+        self.deletion_prob, self.self_loops, self.seed, self.calls = float(deletion_prob), self_loops, int(seed), 0
+        if device is None:
+            super().__init__(dataset_name, node_embedding_dim, gaussian_scale, seed)
+            self.on_device = None
+        else:
+            self.on_device = inner = DeviceGraphDataset(dataset_name, node_embedding_dim, gaussian_scale, seed, device)
+            self.all, self.train_ids, self.test_ids = inner.all, inner.train_ids, inner.test_ids
+            self.dim, self.scale, self.rng = inner.dim, inner.scale, inner.rng
+
+    def get_next_train_batch(self, batch_size, device=None):
+        noise_seed = (self.seed + self.calls) & _M64
+        self.calls += 1
+        if self.on_device is not None:
+            true = self.on_device.get_next_train_batch(batch_size)
+            noisy, removed = perturb_batch(true, self.deletion_prob, noise_seed, self.self_loops)
+            return true, noisy, removed
+        true = super().get_next_train_batch(batch_size)
+        noisy, removed = perturb_batch(true, self.deletion_prob, noise_seed, self.self_loops)
+        if device is not None:
+            true, noisy, removed = true.to(device), noisy.to(device), removed.to(device)
+        return true, noisy, removed
+
+    def get_next_test_batch(self, batch_size, device=None):
+        if self.on_device is not None:
+            return self.on_device.get_next_test_batch(batch_size)
+        return super().get_next_test_batch(batch_size, device)
 
 
 def fully_connected_edges(n):

@@ -534,6 +534,9 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 /* Added within ABI v10: a read-only view of the backward walk's weight-gradient launch plan, for debugging and the tests
  * (gnf_dw_plan.h) - likewise, but with no stability promise. */
 #include "gnf_dw_plan.h"
+/* Added within ABI v10: edge-deletion noise on a batch with both CSRs of the noisy batch, the producer side of the denoising
+ * encoder (gnf_perturb.h) - likewise. */
+#include "gnf_perturb.h"
 
 #ifdef __cplusplus
 }
