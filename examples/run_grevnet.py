@@ -22,7 +22,7 @@ from gnf_amd import gnn                                              # noqa: E40
 from gnf_amd.flow import sample                                      # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from driver_utils import get_learning_rate                           # noqa: E402
-from gnf_amd.grevnet_synthetic_data import DATASETS_MAP              # noqa: E402
+from gnf_amd.grevnet_synthetic_data import DATASETS_MAP, DeviceSyntheticDataset   # noqa: E402
 from gnf_amd.train import GRevNetTrainer                             # noqa: E402
 
 
@@ -64,6 +64,9 @@ def main():
     ap.add_argument("--clip_gradient_by_value", action="store_true")
     ap.add_argument("--clip_gradient_by_norm", action="store_true")
     ap.add_argument("--clip_gradient_norm", type=float, default=10.0)
+    ap.add_argument("--device_batches", action="store_true",
+                    help="make every batch on the device (DeviceSyntheticDataset: node features, topology and both CSRs from "
+                         "the kernels of include/gnf_synthetic.h, seeded with --random_seed) instead of on the host")
     F = ap.parse_args()
 
     random.seed(F.random_seed)
@@ -71,7 +74,7 @@ def main():
     torch.manual_seed(F.random_seed)
     gnn.set_random_seed(F.random_seed)
     dev = torch.device("cuda", 0)
-    dataset = DATASETS_MAP[F.dataset]
+    dataset = DeviceSyntheticDataset(F.dataset, dev, F.random_seed) if F.device_batches else DATASETS_MAP[F.dataset]
     h = F.node_embedding_dim / 2
 
     def mlp(act):                                    # run_grevnet.py:154-180 / 199-211

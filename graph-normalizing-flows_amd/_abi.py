@@ -323,6 +323,25 @@ _PERTURB_SIGNATURES = {
                                     C.POINTER(GnfPerturbSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+# include/gnf_synthetic.h (included by gnf.h, added within ABI v10): the GRevNet driver's synthetic datasets as ready batches.
+# A table of its own for the same reason.
+GNF_SYN_MOONS, GNF_SYN_MOG = 0, 1
+GNF_SYN_MAX_NODES, GNF_SYN_MAX_SETS = 1024, 8
+
+
+class GnfSyntheticSpec(C.Structure):   # include/gnf_synthetic.h
+    _fields_ = [("seed", C.c_uint64), ("seed_dev", C.c_void_p), ("kind", C.c_int32), ("rotate", C.c_int32),
+                ("noise", C.c_double), ("offsets", C.c_void_p), ("n_sets", C.c_int32), ("set_stride", C.c_int32),
+                ("set_size", C.c_int32 * GNF_SYN_MAX_SETS)]
+
+
+_SYNTHETIC_SIGNATURES = {
+    "gnf_synthetic_topology_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnf_synthetic_topology": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gnf_synthetic_nodes": (C.c_int, [C.POINTER(GnfSyntheticSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                      C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -342,6 +361,7 @@ TRIPLET_SYMBOLS = tuple(_TRIPLET_SIGNATURES)
 BATCH_SYMBOLS = tuple(_BATCH_SIGNATURES)
 DW_PLAN_SYMBOLS = tuple(_DW_PLAN_SIGNATURES)
 PERTURB_SYMBOLS = tuple(_PERTURB_SIGNATURES)
+SYNTHETIC_SYMBOLS = tuple(_SYNTHETIC_SIGNATURES)
 
 _lib = None
 
@@ -359,7 +379,8 @@ def lib():
                                   **_ENCODER_TRAIN_SIGNATURES, **_DISTANCE_SIGNATURES,
                                   **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
                                   **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES, **_TRIPLET_SIGNATURES,
-                                  **_BATCH_SIGNATURES, **_DW_PLAN_SIGNATURES, **_PERTURB_SIGNATURES}.items():
+                                  **_BATCH_SIGNATURES, **_DW_PLAN_SIGNATURES, **_PERTURB_SIGNATURES,
+                                  **_SYNTHETIC_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -537,6 +537,9 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 /* Added within ABI v10: edge-deletion noise on a batch with both CSRs of the noisy batch, the producer side of the denoising
  * encoder (gnf_perturb.h) - likewise. */
 #include "gnf_perturb.h"
+/* Added within ABI v10: the GRevNet driver's synthetic datasets generated on the device as ready batches with both CSRs
+ * (gnf_synthetic.h) - likewise. */
+#include "gnf_synthetic.h"
 
 #ifdef __cplusplus
 }
