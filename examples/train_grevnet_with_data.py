@@ -91,6 +91,9 @@ def main():
     ap.add_argument("--keep_generated", default="all", choices=["all", "largest_component", "non_isolated"])
     # uniqueness and novelty of the sampled graphs against the training graphs of --dataset (graph_stats.uniqueness_novelty)
     ap.add_argument("--report_novelty", action="store_true")
+    # degree / clustering MMD^2 of the sampled graphs against the test graphs of --dataset, beside the same scores of Erdos-Renyi
+    # and Barabasi-Albert graphs fitted to its training graphs (random_graphs.evaluate_baselines)
+    ap.add_argument("--report_baselines", action="store_true")
     # train_grevnet_with_data.py:60-61, 471-473: batches of consecutive graphs holding fewer than --max_nodes nodes
     ap.add_argument("--variable_dataset", action="store_true")
     ap.add_argument("--max_nodes", type=int, default=1500)
@@ -198,6 +201,20 @@ def main():
         print(f"sampled graphs: uniqueness {float(u['uniqueness']):.1%}, novelty {float(u['novelty']):.1%}, unique and novel "
               f"{float(u['unique_novel']):.1%} of {int(u['counts'][0])}; the {len(ds.train_ids)} training graphs of {F.dataset} "
               f"fall into {int(classes)} isomorphism classes (Weisfeiler-Lehman hash, 3 rounds)")
+    if F.report_baselines:
+        from gnf_amd.graphs import data_dicts_to_graphs_tuple
+        from gnf_amd.graph_stats import evaluate_generated, graph_stats
+        from gnf_amd.random_graphs import evaluate_baselines
+        ds = D.GraphDataset(F.dataset, 1, seed=F.random_seed)
+        train_graphs = data_dicts_to_graphs_tuple(ds.all.data_dicts(ds.train_ids, ds._features), dev)
+        test_stats = graph_stats(data_dicts_to_graphs_tuple(ds.all.data_dicts(ds.test_ids, ds._features), dev))   # scored once
+        sampled = out["kept"]["graph"] if keep is not None else out["graph"]
+        rows = {"model": evaluate_generated(sampled, test_stats),
+                **evaluate_baselines(train_graphs, test_stats, seed=F.random_seed)}
+        print(f"scores against the {len(ds.test_ids)} test graphs of {F.dataset} (MMD^2; baselines fitted to the "
+              f"{len(ds.train_ids)} training graphs):")
+        for name, row in rows.items():
+            print(f"  {name:16s} degree_mmd {float(row['degree_mmd']):.6f} clustering_mmd {float(row['clustering_mmd']):.6f}")
     if F.sample_log_prob_xs:
         for i, lp in enumerate(out["log_prob_xs_per_node"].cpu().numpy()):
             print(f"sampled graph {i}: log_prob_xs_per_node {lp:.4f}")

@@ -342,6 +342,23 @@ _SYNTHETIC_SIGNATURES = {
     "gnf_synthetic_nodes": (C.c_int, [C.POINTER(GnfSyntheticSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                       C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
+# include/gnf_random_graphs.h (included by gnf.h, added within ABI v10): G(n, p) / planted partition and Barabasi-Albert graphs as
+# edge lists with both CSRs.  A table of its own for the same reason.
+GNF_RG_PLANTED, GNF_RG_BARABASI_ALBERT = 0, 1
+GNF_RG_BA_DRAWS, GNF_RG_MAX_M, GNF_RG_BA_TABLE_MAX = 256, 64, 32768
+GNF_RG_BA_SEED_XOR = 0xA5A5A5A5A5A5A5A5
+
+
+class GnfRandomGraphSpec(C.Structure):   # include/gnf_random_graphs.h
+    _fields_ = [("seed", C.c_uint64), ("seed_dev", C.c_void_p), ("first_graph", C.c_uint64), ("model", C.c_int32),
+                ("self_loops", C.c_int32), ("thr_in", C.c_void_p), ("thr_out", C.c_void_p), ("block", C.c_void_p),
+                ("n_blocks", C.c_int32), ("max_m", C.c_int32), ("m_dev", C.c_void_p)]
+
+
+_RANDOM_GRAPH_SIGNATURES = {
+    "gnf_random_graph_edges_count": (C.c_int, [C.POINTER(GnfRandomGraphSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -362,6 +379,7 @@ BATCH_SYMBOLS = tuple(_BATCH_SIGNATURES)
 DW_PLAN_SYMBOLS = tuple(_DW_PLAN_SIGNATURES)
 PERTURB_SYMBOLS = tuple(_PERTURB_SIGNATURES)
 SYNTHETIC_SYMBOLS = tuple(_SYNTHETIC_SIGNATURES)
+RANDOM_GRAPH_SYMBOLS = tuple(_RANDOM_GRAPH_SIGNATURES)
 
 _lib = None
 
@@ -380,7 +398,7 @@ def lib():
                                   **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
                                   **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES, **_TRIPLET_SIGNATURES,
                                   **_BATCH_SIGNATURES, **_DW_PLAN_SIGNATURES, **_PERTURB_SIGNATURES,
-                                  **_SYNTHETIC_SIGNATURES}.items():
+                                  **_SYNTHETIC_SIGNATURES, **_RANDOM_GRAPH_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

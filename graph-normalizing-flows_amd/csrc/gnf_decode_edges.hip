@@ -9,29 +9,13 @@
 // d2(i, j) and d2(j, i) are the same fp32 number the edge set is symmetric, so it is the by-sender CSR as well.
 // No atomics: every word, count and edge has exactly one writer.
 // gnf_adj_edges_count_dist_f32 (include/gnf_distance.h) is pass 1 with another DistSigmoid (gnf_distance_dev.h).
+// The workspace layout, the grid and the size rules are gnf_edge_ws.h's, shared with gnf_random_graphs.hip, whose kernels are
+// another pass 1 in front of the same scan and the same pass 2.
 #include "gnf_distance_dev.h"
+#include "gnf_edge_ws.h"
 #include "gnf_graph_bitmap.h"
 
 namespace gnf {
-
-static constexpr int kEdgeTile = 16;      // rows per workgroup pass; 4 waves x 4 rows
-static constexpr int kEdgeWaveRows = 4;
-
-// caller-owned workspace of the two calls (host only): node_off int64 [B + 1] | bitmap uint64 [N][W] | rowcnt int32 [N]
-// (the scan keeps its partial sums in LDS)
-struct EdgeWs {
-    size_t node_off, bitmap, rowcnt, total;
-    int64_t W;
-};
-static EdgeWs edge_ws(int64_t n_graphs, int64_t n_nodes, int32_t max_nodes) {
-    EdgeWs L;
-    L.W = ((int64_t)max_nodes + 63) / 64;
-    L.node_off = 0;
-    L.bitmap = (size_t)(n_graphs + 1) * sizeof(int64_t);
-    L.rowcnt = L.bitmap + (size_t)n_nodes * (size_t)L.W * sizeof(uint64_t);
-    L.total = (L.rowcnt + (size_t)n_nodes * sizeof(int32_t) + 7) / 8 * 8;
-    return L;
-}
 
 // A graph's rows come from stats_graph_range (gnf_graph_bitmap.h), cut to the node buffer and to the `max_nodes` columns the
 // bitmap holds: counts that do not describe the batch (or a bound below the largest graph) lose edges, they never reach
@@ -158,26 +142,11 @@ __global__ __launch_bounds__(256) void k_edge_fill(const int64_t* __restrict__ n
     }
 }
 
-static int edge_sizes_ok(const char* what, int64_t n_graphs, int64_t n_nodes, int32_t max_nodes) {
-    if (n_graphs < 0 || n_nodes < 0 || max_nodes < 0) {
-        set_error("%s: n_graphs=%lld n_nodes=%lld max_nodes_per_graph=%d", what, (long long)n_graphs, (long long)n_nodes, max_nodes);
-        return GNF_ESHAPE;
-    }
-    if (n_nodes > 0 && n_graphs > 0 && max_nodes == 0) {
-        set_error("%s: max_nodes_per_graph=0 with %lld nodes", what, (long long)n_nodes);
-        return GNF_ESHAPE;
-    }
-    if (n_nodes * (int64_t)max_nodes > INT32_MAX) {
-        set_error("%s: n_nodes=%lld x max_nodes_per_graph=%d exceeds the int32 edge ids", what, (long long)n_nodes, max_nodes);
-        return GNF_ESHAPE;
-    }
+int launch_edge_scan(const int32_t* rowcnt, int64_t n_nodes, const int64_t* node_off, int64_t n_graphs, int32_t* rowptr,
+                     int32_t* n_edge, int64_t* total, hipStream_t st) {
+    hipLaunchKernelGGL(k_edge_scan, dim3(1), dim3(256), 0, st, rowcnt, n_nodes, node_off, n_graphs, rowptr, n_edge, total);
+    GNF_LAUNCH_CHECK("k_edge_scan");
     return GNF_OK;
-}
-
-static dim3 edge_grid(int64_t n_graphs, int32_t max_nodes) {
-    int64_t tiles = ((int64_t)max_nodes + kEdgeTile - 1) / kEdgeTile;
-    if (tiles > 65535) tiles = 65535;   // (the kernels stride over a graph's tiles)
-    return dim3((unsigned)n_graphs, (unsigned)tiles);
 }
 
 // the two counting entry points: same checks, same launches
@@ -218,10 +187,7 @@ static int edges_count(const char* what, DistSigmoid dist, const float* z, int64
                                max_nodes_per_graph, L.W, threshold, self_loops, dist, bitmap, rowcnt);
         GNF_LAUNCH_CHECK("k_edge_count");
     }
-    hipLaunchKernelGGL(k_edge_scan, dim3(1), dim3(256), 0, st, rowcnt, n_graphs > 0 ? n_nodes : 0, node_off, n_graphs, rowptr,
-                       n_edge, total);
-    GNF_LAUNCH_CHECK("k_edge_scan");
-    return GNF_OK;
+    return launch_edge_scan(rowcnt, n_graphs > 0 ? n_nodes : 0, node_off, n_graphs, rowptr, n_edge, total, st);
 }
 
 }  // namespace gnf

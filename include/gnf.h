@@ -540,6 +540,9 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 /* Added within ABI v10: the GRevNet driver's synthetic datasets generated on the device as ready batches with both CSRs
  * (gnf_synthetic.h) - likewise. */
 #include "gnf_synthetic.h"
+/* Added within ABI v10: random graph models - G(n, p), planted partition, Barabasi-Albert - generated on the device as edge
+ * lists with both CSRs, the baselines of the graph scores (gnf_random_graphs.h) - likewise. */
+#include "gnf_random_graphs.h"
 
 #ifdef __cplusplus
 }
