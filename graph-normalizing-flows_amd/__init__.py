@@ -7,6 +7,7 @@ Import as `gnf_amd` (the directory name has a hyphen; gnf_amd.py at the repo roo
     from gnf_amd.graph_stats import graph_stats, hist_mmd, evaluate_generated, graph_orbits, orbit_mmd, graph_spectra, spectral_mmd
     from gnf_amd.graph_stats import graph_components, keep_subgraphs, graph_hashes, uniqueness_novelty
     from gnf_amd.adj_loss import binary_loss, hacky_sigmoid_l2, sigmoid_l2, TunedSigmoidL2, incorrect_edges_per_graph
+    from gnf_amd.adj_loss import reconstruction_report, predicted_graph, error_graph
     from gnf_amd.triplet_loss import triplet_loss, l2, exp_l2, margin_loss, relative_loss
     from gnf_amd.gnn import TimestepGNN
     from gnf_amd.encoder import evaluate, write_embedding_chunks
@@ -17,7 +18,8 @@ from .graphs import GraphsTuple, data_dicts_to_graphs_tuple, build_csr_host, csr
 from .graph_stats import graph_stats, hist_mmd, evaluate_generated, graph_orbits, orbit_mmd, graph_spectra, spectral_mmd
 from .graph_stats import graph_components, keep_subgraphs, graph_hashes, uniqueness_novelty
 from .adj_loss import (binary_loss, hacky_sigmoid_l2, sigmoid_l2, TunedSigmoidL2, incorrect_edges_per_graph,
-                       false_positive_edges, false_negative_edges, total_incorrect_edges)
+                       false_positive_edges, false_negative_edges, total_incorrect_edges, reconstruction_report,
+                       predicted_graph, error_graph)
 from .triplet_loss import triplet_loss, margin_loss, relative_loss
 from .gnn import TimestepGNN
 from .encoder import evaluate, write_embedding_chunks
@@ -27,5 +29,6 @@ __all__ = ["GraphsTuple", "data_dicts_to_graphs_tuple", "build_csr_host", "csr_o
            "graph_stats", "hist_mmd", "evaluate_generated", "graph_orbits", "orbit_mmd", "graph_spectra", "spectral_mmd",
            "graph_components", "keep_subgraphs", "graph_hashes", "uniqueness_novelty",
            "binary_loss", "hacky_sigmoid_l2", "sigmoid_l2", "TunedSigmoidL2", "incorrect_edges_per_graph", "false_positive_edges",
-           "false_negative_edges", "total_incorrect_edges", "triplet_loss", "margin_loss", "relative_loss", "TimestepGNN", "evaluate", "write_embedding_chunks",
+           "false_negative_edges", "total_incorrect_edges", "reconstruction_report", "predicted_graph", "error_graph",
+           "triplet_loss", "margin_loss", "relative_loss", "TimestepGNN", "evaluate", "write_embedding_chunks",
            "EncoderTrainer", "encoder_learning_rate", "encoder_trainer_state", "load_encoder_trainer_state"]

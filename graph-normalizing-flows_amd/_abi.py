@@ -359,6 +359,20 @@ _RANDOM_GRAPH_SIGNATURES = {
     "gnf_random_graph_edges_count": (C.c_int, [C.POINTER(GnfRandomGraphSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
+# include/gnf_adj_report.h (included by gnf.h, added within ABI v10): the classified edge list of embeddings against a true batch
+# with its scores, and exact order statistics of a class's scores.  A table of its own for the same reason.
+GNF_SELECT_MAX_Q = 16
+_ADJ_REPORT_SIGNATURES = {
+    "gnf_adj_report_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gnf_adj_report_count_f32": (C.c_int, [C.POINTER(GnfCsr), C.POINTER(GnfDistance), C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
+    "gnf_adj_report_fill": (C.c_int, [C.POINTER(GnfDistance), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
+    "gnf_score_select_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                       C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
 # enum GnfRoute: bits of gnf_last_route()
 ROUTE_BITS = {name: 1 << k for k, name in enumerate((
     "fused_16", "fused_32", "fused_front", "fused_fixed", "fused_geo", "one_net_16", "one_net_32", "big", "big_split", "layered",
@@ -380,6 +394,7 @@ DW_PLAN_SYMBOLS = tuple(_DW_PLAN_SIGNATURES)
 PERTURB_SYMBOLS = tuple(_PERTURB_SIGNATURES)
 SYNTHETIC_SYMBOLS = tuple(_SYNTHETIC_SIGNATURES)
 RANDOM_GRAPH_SYMBOLS = tuple(_RANDOM_GRAPH_SIGNATURES)
+ADJ_REPORT_SYMBOLS = tuple(_ADJ_REPORT_SIGNATURES)
 
 _lib = None
 
@@ -398,7 +413,7 @@ def lib():
                                   **_INVERSE_PER_GRAPH_SIGNATURES, **_SPECTRA_SIGNATURES,
                                   **_COMPONENT_SIGNATURES, **_HASH_SIGNATURES, **_TRIPLET_SIGNATURES,
                                   **_BATCH_SIGNATURES, **_DW_PLAN_SIGNATURES, **_PERTURB_SIGNATURES,
-                                  **_SYNTHETIC_SIGNATURES, **_RANDOM_GRAPH_SIGNATURES}.items():
+                                  **_SYNTHETIC_SIGNATURES, **_RANDOM_GRAPH_SIGNATURES, **_ADJ_REPORT_SIGNATURES}.items():
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -7,6 +7,7 @@ The reference builds a dense [N, N] true adjacency, a dense distance_fn(nodes) a
 (loss.py:162-188), counts wrong entries on those matrices (loss.py:88-116) and lets tf.gradients differentiate through
 them.  Here the embeddings meet the true graph's receiver-sorted CSR pair by pair inside each graph; the arithmetic of a pair
 is flow.pred_adj's, so the verdict on an edge agrees with `pred_adj > 0.5` and flow.decode_graphs bit for bit.
+reconstruction_report (include/gnf_adj_report.h) says WHICH pairs are wrong and with what score: run_gnn_inference.py:107-163.
 HIP only: CPU tensors raise GnfError.
 
 Unpinned upstream facts this relies on: tf.keras.backend.binary_crossentropy of TF 1.x clips the probability to
@@ -193,6 +194,157 @@ def binary_loss(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, use_
     if want_gp:
         out["grad_params"] = gp
     return out
+
+
+# ---- run_gnn_inference.py:107-163: which pairs are wrong, and with what score ------------------------------------------------
+REPORT_CLASSES = {"correct": 1, "false_positive": 2, "false_negative": 3}
+MAX_QUANTILES = _abi.GNF_SELECT_MAX_Q
+
+
+def _quantile_list(quantiles):
+    qs = [float(q) for q in quantiles]
+    if len(qs) > MAX_QUANTILES:
+        raise ValueError(f"at most {MAX_QUANTILES} quantiles per call, got {len(qs)}")
+    for q in qs:
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"quantile {q}: in [0, 1]")
+    return qs
+
+
+def score_quantiles(score, cls, rowptr, seg_nodes, quantiles, edge_capacity=None):
+    """gnf_score_select_f32 and the host side of its rule: per segment of the edge list (seg_nodes: device int32 node offsets)
+    and for the classes 2 and 3, np.quantile's linear interpolation x[lo] + (h - lo) (x[hi] - x[lo]), h = (n - 1) q, of the
+    class's scores - the order statistics x[lo], x[hi] selected exactly on the device, the interpolation two float64 torch
+    ops on them.  Returns {"quantiles": float64 [S, 2, nq] (NaN where the class is empty), "count": int64 [S, 2], "stat":
+    float32 [S, 2, nq, 2]}; nothing is read on the host."""
+    qs = _quantile_list(quantiles)
+    dev = rowptr.device
+    if dev.type != "cuda":
+        raise _abi.GnfError("score_quantiles runs on a HIP device only (no CPU path)")
+    lib = _abi.lib()
+    n_seg, nq = int(seg_nodes.shape[0]) - 1, len(qs)
+    cap = int(score.shape[0]) if edge_capacity is None else min(int(edge_capacity), int(score.shape[0]))
+    stat = torch.empty((n_seg, 2, nq, 2), dtype=torch.float32, device=dev)
+    count = torch.empty((n_seg, 2), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_score_select_f32(_abi.ptr(score), _abi.ptr(cls), _abi.ptr(rowptr), _abi.ptr(seg_nodes), n_seg,
+                                            int(rowptr.shape[0]) - 1, cap, (C.c_double * max(nq, 1))(*qs), nq, _abi.ptr(stat),
+                                            _abi.ptr(count), _abi.stream_ptr(dev)), "gnf_score_select_f32")
+    qv = torch.empty(nq, dtype=torch.float64, device=dev)
+    for i, q in enumerate(qs):   # (fills, not a copy from the host: the call stays capturable)
+        qv[i].fill_(q)
+    h = (count - 1).clamp(min=0).to(torch.float64).unsqueeze(-1) * qv   # one fp64 product, as the device forms it
+    x = stat.to(torch.float64)
+    values = x[..., 0] + (h - torch.floor(h)) * (x[..., 1] - x[..., 0])
+    return {"quantiles": values, "count": count, "stat": stat}
+
+
+def reconstruction_report(gnn_output, graph_phs, distance_fn=scaled_hacky_sigmoid_l2, threshold=0.5,
+                          quantiles=(0, .25, .5, .75, 1), per_graph=False, edge_capacity=None, max_nodes_per_graph=None,
+                          n_node_host=None):
+    """run_gnn_inference.py:107-163 on the device (include/gnf_adj_report.h): every ordered pair (sender s, receiver r), s != r,
+    inside a graph that is a true edge of graph_phs or a predicted edge of gnn_output.nodes (score > threshold) becomes one
+    entry of an edge list - receivers ascending, senders ascending within a receiver - with its class (1 correct, 2 false
+    positive, 3 false negative: the reference's complete_mat weights) and its score, which has the bits of
+    flow.pred_adj(...)[g][r, s] under the same distance_fn.  Returns a dict of device tensors:
+      "graph"         GraphsTuple on gnn_output.nodes: the "complete" graph, int32 senders / receivers, n_edge, edges = the
+                      classes as float32
+      "cls", "score"  int32 / float32 [E]
+      "csr"           graphs.Csr over (rowptr, senders): the receiver-sorted CSR of the list
+      "class_pairs"   int64 [B, 3]: ordered pairs of each graph in class 1, 2, 3 ([:, 1:] are binary_loss' counts at 0.5)
+      "totals"        int64 [4]: entries, class 1, class 2, class 3
+      "fp_quantiles", "fn_quantiles"  float64 [nq] (per_graph: [B, nq]): np.quantile(scores of the class, quantiles) with
+                      linear interpolation, NaN for an empty class
+      "fp_count", "fn_count"          int64 0-d (per_graph: [B])
+    Two departures from the reference: the diagonal is excluded (there every node counts as a false-positive self loop of
+    score sigmoid(temp * shift)), and false negatives whose score is exactly 0 stay in the quantiles (np.nonzero drops them).
+    Without edge_capacity the call reads totals[0] once, as decode_graphs does, and allocates exactly that many entries.  With
+    edge_capacity and max_nodes_per_graph or n_node_host nothing is read on the host and the call can be captured; the edge
+    tensors then have edge_capacity entries of which the first min(totals[0], edge_capacity) are valid, rowptr / n_edge /
+    class_pairs / totals describe the untruncated list and the quantiles see the valid entries only.
+    distance_fn: binary_loss' tokens, TunedSigmoidL2 included.  HIP only."""
+    from .graphs import Csr, GraphsTuple, csr_desc, csr_of, node_offsets_of, seed_csr_cache
+    check_token(distance_fn, "reconstruction_report")    # (anything else raises before the device is looked at)
+    qs = _quantile_list(quantiles)
+    if edge_capacity is not None and int(edge_capacity) < 0:
+        raise ValueError(f"edge_capacity={edge_capacity}")
+    z = gnn_output.nodes
+    n = int(z.shape[0])
+    if int(graph_phs.nodes.shape[0]) != n:
+        raise ValueError(f"gnn_output has {n} nodes, graph_phs {int(graph_phs.nodes.shape[0])}")
+    lib = _abi.lib()
+    dev = z.device
+    if dev.type != "cuda" or graph_phs.senders.device.type != "cuda" or graph_phs.n_node.device.type != "cuda":
+        raise _abi.GnfError("reconstruction_report runs on a HIP device only (no CPU path)")
+    b = int(graph_phs.n_node.shape[0])
+    cap = _node_bound(graph_phs, max_nodes_per_graph, n_node_host, MAX_NODES_PER_GRAPH)
+    z, _, d, ld = _abi.embeddings(z, "reconstruction_report")
+    desc = csr_desc(graph_phs, csr_of(graph_phs), node_offsets=True)
+    dist = distance_desc(distance_fn, dev, "reconstruction_report")
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    n_edge = torch.empty(b, dtype=torch.int32, device=dev)
+    class_pairs = torch.empty((b, 3), dtype=torch.int64, device=dev)
+    totals = torch.empty(4, dtype=torch.int64, device=dev)
+    ws_bytes = lib.gnf_adj_report_workspace_bytes(b, n, cap)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _abi.check(lib.gnf_adj_report_count_f32(C.byref(desc), C.byref(dist), _abi.ptr(z), ld, d, cap, float(threshold),
+                                                _abi.ptr(rowptr), _abi.ptr(n_edge), _abi.ptr(class_pairs), _abi.ptr(totals),
+                                                _abi.ptr(ws), ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_report_count_f32")
+        exact = edge_capacity is None
+        e = int(totals[0].item()) if exact else int(edge_capacity)
+        senders = torch.empty(e, dtype=torch.int32, device=dev)
+        receivers = torch.empty(e, dtype=torch.int32, device=dev)
+        cls = torch.empty(e, dtype=torch.int32, device=dev)
+        score = torch.empty(e, dtype=torch.float32, device=dev)
+        _abi.check(lib.gnf_adj_report_fill(C.byref(dist), _abi.ptr(z), ld, d, b, n, cap, _abi.ptr(rowptr), e,
+                                           _abi.ptr(senders), _abi.ptr(receivers), _abi.ptr(cls), _abi.ptr(score), _abi.ptr(ws),
+                                           ws_bytes, _abi.stream_ptr(dev)), "gnf_adj_report_fill")
+    if per_graph:
+        seg = node_offsets_of(graph_phs)
+    else:
+        seg = torch.zeros(2, dtype=torch.int32, device=dev)
+        seg[1:].fill_(n)
+    sel = score_quantiles(score, cls, rowptr, seg, qs, e)
+    qv, cnt = sel["quantiles"], sel["count"]
+    if not per_graph:
+        qv, cnt = qv[0], cnt[0]
+    graph = GraphsTuple(nodes=gnn_output.nodes, edges=cls.to(torch.float32), receivers=receivers, senders=senders,
+                        globals=torch.zeros(b, dtype=torch.float32, device=dev), n_node=graph_phs.n_node, n_edge=n_edge)
+    csr = Csr(rowptr, senders, n, e)
+    if exact:
+        seed_csr_cache(graph, csr, by_sender=False)
+    return {"graph": graph, "cls": cls, "score": score, "csr": csr, "class_pairs": class_pairs, "totals": totals,
+            "fp_quantiles": qv[..., 0, :], "fn_quantiles": qv[..., 1, :], "fp_count": cnt[..., 0], "fn_count": cnt[..., 1]}
+
+
+def _report_subgraph(report, classes):
+    g = report["graph"]
+    cls = report["cls"]
+    e = int(cls.shape[0])
+    keep = torch.arange(e, device=cls.device) < report["totals"][0]   # (a capacity above the total: the tail is unspecified)
+    pick = torch.zeros_like(keep)
+    for c in classes:
+        pick |= cls == c
+    idx = torch.nonzero(keep & pick).squeeze(1)
+    n_edge = sum(report["class_pairs"][:, c - 1] for c in classes).to(torch.int32)
+    sub = g.replace(senders=g.senders[idx], receivers=g.receivers[idx], edges=g.edges[idx], n_edge=n_edge)
+    return {"graph": sub, "cls": cls[idx], "score": report["score"][idx]}
+
+
+def predicted_graph(report):
+    """run_gnn_inference.py:141-146: the predicted graph of a reconstruction_report - its entries of class 1 or 2, in order:
+    flow.decode_graphs(..., self_loops=False)'s edge list at the report's threshold.  Returns {"graph", "cls", "score"}; an
+    index selection on the device (its size is the one number read back).  n_edge is that of the untruncated list."""
+    return _report_subgraph(report, (1, 2))
+
+
+def error_graph(report, cls):
+    """the entries of one class (1, 2, 3 or a name of REPORT_CLASSES) as predicted_graph returns them"""
+    c = REPORT_CLASSES.get(cls, cls)
+    if c not in (1, 2, 3):
+        raise ValueError(f"cls={cls!r}: 1, 2, 3 or one of {sorted(REPORT_CLASSES)}")
+    return _report_subgraph(report, (c,))
 
 
 # ---- loss.py:88-116 over the result dict: the reference's figures are the ordered-pair counts halved -------------------------

@@ -20,7 +20,7 @@ from .gnn import TimestepGNN
 CHUNK_BYTES = 100e6   # generate_grevnet_training_data.py:80,90: a chunk is closed once it holds more than 100 MB of fp32
 
 
-def evaluate(encoder, graphs, distance_fn=scaled_hacky_sigmoid_l2, use_soft_labels=False, **loss_kw):
+def evaluate(encoder, graphs, distance_fn=scaled_hacky_sigmoid_l2, use_soft_labels=False, report=False, **loss_kw):
     """The quantities run_gnn.py:441-465 logs for a batch, from encoder(graphs, is_training=False) and binary_loss of its
     output against the batch's own topology.  Returns a dict of device tensors (nothing is read back):
       "gnn_output"                  the encoder's GraphsTuple
@@ -29,16 +29,24 @@ def evaluate(encoder, graphs, distance_fn=scaled_hacky_sigmoid_l2, use_soft_labe
       "incorrect_edges_per_graph"   int32 [B] (loss.py:88-95)
       "incorrect_edges_per_node"    0-d float64: total_incorrect_edges / N
       "loss"                        binary_loss' own result dict
-    loss_kw goes to binary_loss (max_nodes_per_graph or n_node_host make the call free of host synchronisation)."""
+    loss_kw goes to binary_loss (max_nodes_per_graph or n_node_host make the call free of host synchronisation).
+    report=True adds "report": adj_loss.reconstruction_report of the same output against the batch at threshold 0.5 (which
+    pairs are wrong and with what score, run_gnn_inference.py:107-163), with binary_loss' node bound; a dict is passed on as
+    that call's options (threshold, quantiles, per_graph, edge_capacity).  Without it the launches are those of before."""
     out = encoder(graphs, False)
     res = adj_loss.binary_loss(out, graphs, distance_fn=distance_fn, use_soft_labels=use_soft_labels, **loss_kw)
     total = adj_loss.total_incorrect_edges(res)
     n = int(graphs.nodes.shape[0])
-    return {"gnn_output": out, "sum_loss": res["sum_loss"], "mean_loss": res["mean_loss"], "total_incorrect_edges": total,
-            "incorrect_edges_per_node": total / float(max(n, 1)),
-            "incorrect_edges_per_graph": adj_loss.incorrect_edges_per_graph(res),
-            "false_positive_edges": adj_loss.false_positive_edges(res),
-            "false_negative_edges": adj_loss.false_negative_edges(res), "loss": res}
+    result = {"gnn_output": out, "sum_loss": res["sum_loss"], "mean_loss": res["mean_loss"], "total_incorrect_edges": total,
+              "incorrect_edges_per_node": total / float(max(n, 1)),
+              "incorrect_edges_per_graph": adj_loss.incorrect_edges_per_graph(res),
+              "false_positive_edges": adj_loss.false_positive_edges(res),
+              "false_negative_edges": adj_loss.false_negative_edges(res), "loss": res}
+    if report:
+        bound = {k: loss_kw[k] for k in ("max_nodes_per_graph", "n_node_host") if k in loss_kw}
+        options = dict(report) if isinstance(report, dict) else {}
+        result["report"] = adj_loss.reconstruction_report(out, graphs, distance_fn=distance_fn, **{**bound, **options})
+    return result
 
 
 def write_embedding_chunks(encoder, dataset, directory, num_examples, batch_size, device=None, prefix="grevnet_train",

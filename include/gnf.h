@@ -543,6 +543,9 @@ int gnf_clip_by_norm_f32(float* g, const int64_t* offsets, int32_t n_tensors, fl
 /* Added within ABI v10: random graph models - G(n, p), planted partition, Barabasi-Albert - generated on the device as edge
  * lists with both CSRs, the baselines of the graph scores (gnf_random_graphs.h) - likewise. */
 #include "gnf_random_graphs.h"
+/* Added within ABI v10: the reconstruction report - the classified edge list of embeddings against a true batch with its
+ * scores, and exact order statistics of the error classes' scores (gnf_adj_report.h) - likewise. */
+#include "gnf_adj_report.h"
 
 #ifdef __cplusplus
 }
